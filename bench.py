@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: BASELINE.json metric "decode tokens/sec/GPU + prefill TFLOPS, Qwen3-0.6B bf16".
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in the environment - what
     `python -m torch.distributed.run --nproc-per-node N bench.py ...` sets, or any other launcher; nothing here imports torch)
 
@@ -28,6 +28,13 @@ Extra objects on the JSON line:
   step_roofline    whole decode step: algorithmic bytes per token / measured step time.
   prefill          ms, TFLOP/s and fraction of the 2.5 PFLOP/s dense bf16 MFMA peak for the 128-token prompt.
   cpu_baseline     the NumPy oracle (reference-semantics CPU path) timed on this box's host cores, rank 0, N = 1.
+
+--dump-outputs DIR (rank 0) writes, after the timed steps, what the headline path handed back in its last step:
+  DIR/logits.npy   float32 [batch, vocab] logits of the last timed decode step (all rows while they fit in 48 MB, otherwise
+                   a fixed, seeded sample of rows, listed in DIR/logits_rows.npy),
+  DIR/tokens.npy   float64 [warmup + steps, batch] the greedy token log of the replayed steps (the first 4096).
+The inputs (weights, prompts) depend only on the arguments, so two builds run with the same arguments compare output for output.
+(`--dump-outputs bench_out` is ignored by git.)
 """
 
 from __future__ import annotations
@@ -117,6 +124,22 @@ def cpu_baseline(cfg, weights, prompt, n_decode: int) -> dict:
             "prefill_s": t_prefill}
 
 
+DUMP_LOGITS_BYTES = 48 << 20     # the token log is small; everything dumped stays under 64 MB
+
+
+def dump_outputs(out_dir: str, logits: np.ndarray, tokens: np.ndarray) -> None:
+    """The headline path's outputs after the timed steps, as .npy files (see the module docstring)."""
+    os.makedirs(out_dir, exist_ok=True)
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    if logits.nbytes > DUMP_LOGITS_BYTES:
+        n = DUMP_LOGITS_BYTES // logits[0].nbytes
+        rows = np.sort(np.random.default_rng(0).choice(logits.shape[0], n, replace=False))
+        np.save(os.path.join(out_dir, "logits_rows.npy"), rows.astype(np.float64))
+        logits = logits[rows]
+    np.save(os.path.join(out_dir, "logits.npy"), logits)
+    np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(tokens, dtype=np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -138,6 +161,8 @@ def main() -> None:
                     help="skip every extra leg (config 4 weak/strong; at N = 1 also context 2048 in bf16 and w8a16, config 5)")
     ap.add_argument("--config4-steps", type=int, default=32)
     ap.add_argument("--layers", type=int, default=0, help="debug only: override the layer count (result is then INVALID)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's logits and the token log as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     # ONE JSON line on stdout, whatever the libraries underneath print: RCCL writes a version banner to the process's stdout
@@ -274,6 +299,8 @@ def main() -> None:
     wall_max, dev_ms_max, tokens, gather = head["wall_s"], head["device_ms"], head["tokens"], head["gather"]
     if gather is not None:
         gather.pop("all_tokens")
+    if args.dump_outputs and cp.rank == 0:
+        dump_outputs(args.dump_outputs, eng.logits(B).to_numpy(), tokens)
     pf_ms = timed_ms(lambda: eng.prefill([int(t) for t in mine[0]], seq=0, want_last_logits=False), 5)    # slot 0's rows are rewritten with the same values
     pf_med = float(np.median(pf_ms))
     pf_flops = prefill_flops(cfg, P, all_rows=False)
