@@ -318,6 +318,19 @@ pgk_status pgk_w8a16_gemm_nk(const void* a, const uint8_t* w_nk, const void* sca
  * w_scale [ceil(N/128), K/128] bf16 (the LinearFP8 layout, linear.py:149-160); C bf16 [M,N].  K % 128 == 0. */
 pgk_status pgk_gemm_fp8_nt(const uint8_t* a_fp8, const float* a_scale, const uint8_t* w_fp8_nk, const void* w_scale,
                            void* c, int m, int n, int k, pgk_stream s);
+/* gemm_fp8_fp8_sm120 / gemm_fp8_fp8_blockwise_sm120 (src/pygpukit/ops/matmul/fp8.py:220-343, bindings
+ * native/bindings/gemm/fp8xfp8_fp8.cpp): fp8 in, fp8 out,
+ *   D[m][n] = E4M3( sum_kb scale_a[mb,kb] * scale_b[nb,kb] * sum_{k in kb} E4M3(a[m][k]) * E4M3(b[k][n]) ),
+ * mb = m/128, nb = n/128, kb = k/128.  a_mk [M,K], b_kn [K,N], d_mn [M,N]: e4m3 codes, row-major as the shapes say
+ * (the reference hands its [K,N] buffer to CUTLASS as column-major, i.e. N x K bytes; this entry follows the
+ * declared shape, like pgk_w8a16_gemm_kn).  Output: RNE with satfinite (|x| > 448 -> +-448), NaN stays NaN.
+ * scale_a / scale_b fp32, ceil(M/128)*ceil(K/128) and ceil(N/128)*ceil(K/128) elements, MN-major: (mb, kb) at
+ * kb*ceil(M/128) + mb, (nb, kb) at kb*ceil(N/128) + nb.  That layout is the default of CUTLASS's
+ * Sm1xxBlockwiseScaleConfig (fp8_cutlass.cu:84-86,261-268), taken from CUTLASS's defaults, not pinned by a
+ * reference run.  Both scales NULL = unit scales; exactly one NULL is an error.
+ * M >= 1; N, K multiples of 16 (K need not be a multiple of 128); operands 16-byte aligned. */
+pgk_status pgk_gemm_fp8_fp8_nn(const uint8_t* a_mk, const uint8_t* b_kn, uint8_t* d_mn, const float* scale_a,
+                               const float* scale_b, int m, int n, int k, pgk_stream s);
 /* Activation quantiser for pgk_gemm_fp8_nt (the fp32-in "auto-quantise" half of matmul_fp8, fp8.py:20-83):
  * per (row, 128-k block) scale = absmax/448 (1 for an all-zero block), codes = RNE e4m3 of x/scale.
  * dt = PGK_BF16 / PGK_F16 / PGK_F32. */

@@ -81,7 +81,8 @@ _PROTOS = {
     "pgk_gemm_nn": [_V, _V, _V, _I, _I, _I, _I, _V], "pgk_gemm_nt": [_V, _V, _V, _V, _I, _I, _I, _I, _V],
     "pgk_gemv": [_V, _V, _V, _I, _I, _I, _V], "pgk_gemv_fp8_bf16": [_V, _V, _V, _V, _I, _I, _I, _V],
     "pgk_w8a16_gemm_kn": [_V, _V, _V, _V, _I, _I, _I, _V], "pgk_w8a16_gemm_nk": [_V, _V, _V, _V, _I, _I, _I, _V],
-    "pgk_gemm_fp8_nt": [_V, _V, _V, _V, _V, _I, _I, _I, _V], "pgk_quantize_fp8_rows": [_V, _V, _V, _I, _I, _I, _V],
+    "pgk_gemm_fp8_nt": [_V, _V, _V, _V, _V, _I, _I, _I, _V], "pgk_gemm_fp8_fp8_nn": [_V, _V, _V, _V, _V, _I, _I, _I, _V],
+    "pgk_quantize_fp8_rows": [_V, _V, _V, _I, _I, _I, _V],
     "pgk_quantize_fp8_blocks": [_V, _V, _V, _I, _I, _V],
     "pgk_paged_attention_v1": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
     "pgk_paged_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
