@@ -450,6 +450,59 @@ pgk_status pgk_engine_state_ptr(pgk_engine e, void** tokens, void** positions);
 /* number of kernel launches one decode step enqueues (for reporting) */
 pgk_status pgk_engine_launches_per_step(pgk_engine e, int* n);
 
+/* ------------------------------------------------------------------ Mixture of Experts ------ */
+/* Routing, permutation and grouped expert GEMMs (ops_moe.hip).  Restates native/ops/moe/topk_kernels.cuh,
+ * permute_kernels.cuh, moe_kernels.cuh and native/ops/matmul/gemm/w8a16_bf16/sm120/grouped_gemm.cu.  Every entry is
+ * stream-ordered; none synchronises the host or reads a device value back to size a launch.
+ *
+ * Top-k: logits [T,E] (bf16 or fp32, E <= 256, k <= 8) -> weights [T,k] (logits dtype), indices [T,k] int32.  The k
+ * largest logits in descending order, the lowest expert index first among equal logits (the strict '>' scan of
+ * topk_with_indices_kernel, topk_kernels.cuh:49-64); NaN logits rank as -inf; the k ids are distinct.  softmax != 0
+ * replaces the values by softmax_topk over the k (fp32, topk_kernels.cuh:192-260), stored in the logits dtype.
+ * pgk_moe_softmax_topk is that second step alone, in place. */
+pgk_status pgk_moe_topk_softmax(const void* logits, void* weights, int32_t* indices, int T, int E, int k, int softmax,
+                                pgk_dtype dt, pgk_stream s);
+pgk_status pgk_moe_softmax_topk(void* weights, int T, int k, pgk_dtype dt, pgk_stream s);
+/* Permutation of the T*k (token, slot) entries by expert (moe_kernels.cuh / permute_kernels.cuh):
+ *   expert_counts [E], expert_offsets [E+1] (exclusive scan, offsets[E] = rows placed),
+ *   permute_indices [T*k]: sorted row r holds flat index token*k + slot,  reverse_perm [T*k]: flat -> sorted row,
+ *   tiles [pgk_moe_max_tiles(T,k,E)][2]: {expert, first sorted row} per 128-row piece of every non-empty expert
+ *     segment, in expert order, then {-1, 0} to the end - the table pgk_grouped_gemm_sorted reads.
+ * DETERMINISTIC, unlike the reference (whose order within an expert is whatever atomicAdd produced): within one expert the
+ * rows are in ascending flat index (token-major, then slot) - a stable counting sort, no atomic decides an order.
+ * Ids outside [0,E) are not placed (reverse_perm -1; permute_indices is -1 past offsets[E]).  workspace: pgk_moe_workspace_bytes(T,k,E) bytes of device memory. */
+int pgk_moe_max_tiles(int T, int k, int E);
+size_t pgk_moe_workspace_bytes(int T, int k, int E);
+pgk_status pgk_moe_compute_permutation(const int32_t* indices, int T, int k, int E, int32_t* expert_counts,
+                                       int32_t* expert_offsets, int32_t* permute_indices, int32_t* reverse_perm,
+                                       int32_t* tiles, void* workspace, pgk_stream s);
+/* gathered [T*k, H] = x[permute_indices[r] / k]; rows whose entry is outside [0, T*k) are zero (the permutation writes -1
+ * past offsets[E]); bf16, f16 or fp32 */
+pgk_status pgk_moe_gather(const void* x, const int32_t* permute_indices, void* gathered, int T, int k, int H, pgk_dtype dt,
+                          pgk_stream s);
+/* out [T,H] = sum over slot of weights[t,slot] * y[reverse_perm[t*k+slot]], summed in fp32 in slot order and rounded once
+ * (scatter_with_reverse_perm_kernel).  weights and out are `dt`; y is `dt` [T*k,H] when splits == 0, or fp32 slabs
+ * [splits][T*k][H] (pgk_grouped_gemm_sorted's split-K output) that are summed in slab order first. */
+pgk_status pgk_moe_scatter(const void* y, int splits, const void* weights, const int32_t* reverse_perm, void* out, int T,
+                           int k, int H, pgk_dtype dt, pgk_stream s);
+/* row_expert_ids [nrows]: e with offsets[e] <= r < offsets[e+1], -1 past offsets[E] */
+pgk_status pgk_moe_expand_expert_offsets(const int32_t* expert_offsets, int E, int32_t* row_expert_ids, int nrows, pgk_stream s);
+/* Grouped expert GEMM, C[r,:] = A[r,:] . W[e_r]^T, bf16 A and C, W stacked [E,N,K]: bf16 (fp8 == 0; K, N % 8 == 0) or
+ * fp8-e4m3 codes with bf16 128x128 block scales [E,N/128,K/128] (fp8 != 0; K, N % 128 == 0), the layout of
+ * grouped_gemm_fp8_bf16.
+ * _rows: any row order (the reference's contract, grouped_gemm.cu): fp32 dequantisation lut[code] * scale and fp32 sums;
+ *   rows whose id is outside [0,E) are zero.
+ * _sorted: rows grouped by expert (A = gathered [T*k,K], or x [T,K] read through a_map = permute_indices), driven by the
+ *   tile table.  T*k/E <= 64: weight-streaming kernel, each active expert's weight read from HBM about once per call; else
+ *   128x128 MFMA tiles.  The weight is rounded to bf16 after dequantisation (<= 2^-9 relative per weight).  splits == 0:
+ *   C bf16 [T*k,N]; splits == pgk_grouped_gemm_sorted_splits(...): fp32 slabs [splits][T*k][N] for pgk_moe_scatter. */
+pgk_status pgk_grouped_gemm_rows(const void* a, const void* w, const void* wscale, int fp8, void* c, const int32_t* row_expert_ids,
+                                 int M, int N, int K, int E, pgk_stream s);
+int pgk_grouped_gemm_sorted_splits(int T, int k, int E, int N, int K);
+pgk_status pgk_grouped_gemm_sorted(const void* a, const int32_t* a_map, const void* w, const void* wscale, int fp8, void* c,
+                                   int splits, const int32_t* expert_offsets, const int32_t* tiles, int T, int k, int E, int N,
+                                   int K, pgk_stream s);
+
 /* ------------------------------------------------------------------------ RCCL ------ */
 /* New functionality (the reference is single-GPU, docs/scheduler.md:358): data-parallel batch
  * decode over one 8xMI355X node.  One process per GPU; RCCL over xGMI only for the one-time weight

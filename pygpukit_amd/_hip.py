@@ -110,6 +110,12 @@ _PROTOS = {
     "pgk_engine_set_sampling": [_V, _F, _I, _F, C.POINTER(_F), _I, _V],
     "pgk_engine_read_clock": [_V, C.POINTER(C.c_uint64), _I, _V],
     "pgk_engine_kv_ptr": [_V, _I, c_void_pp, c_void_pp], "pgk_engine_state_ptr": [_V, c_void_pp, c_void_pp], "pgk_engine_launches_per_step": [_V, C.POINTER(_I)],
+    "pgk_moe_topk_softmax": [_V, _V, _V, _I, _I, _I, _I, _I, _V], "pgk_moe_softmax_topk": [_V, _I, _I, _I, _V],
+    "pgk_moe_compute_permutation": [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V],
+    "pgk_moe_gather": [_V, _V, _V, _I, _I, _I, _I, _V], "pgk_moe_scatter": [_V, _I, _V, _V, _V, _I, _I, _I, _I, _V],
+    "pgk_moe_expand_expert_offsets": [_V, _I, _V, _I, _V],
+    "pgk_grouped_gemm_rows": [_V, _V, _V, _I, _V, _V, _I, _I, _I, _I, _V],
+    "pgk_grouped_gemm_sorted": [_V, _V, _V, _V, _I, _V, _I, _V, _V, _I, _I, _I, _I, _I, _V],
     "pgk_comm_unique_id": [C.c_char_p], "pgk_comm_init": [c_void_pp, C.c_char_p, _I, _I], "pgk_comm_destroy": [_V],
     "pgk_comm_broadcast": [_V, _V, _Z, _I, _V], "pgk_comm_all_gather": [_V, _V, _V, _Z, _V],
     "pgk_comm_all_reduce_max_f64": [_V, _V, _I, _V], "pgk_comm_barrier": [_V, _V],
@@ -119,6 +125,8 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_paged_attention_workspace_bytes": ([_I, _I, _I, _I], C.c_size_t),
                "pgk_st_close": ([_V], None), "pgk_st_num_tensors": ([_V], C.c_int), "pgk_st_file_size": ([_V], C.c_uint64),
                "pgk_st_tensor_name": ([_V, _I], C.c_char_p),
+               "pgk_moe_max_tiles": ([_I, _I, _I], C.c_int), "pgk_moe_workspace_bytes": ([_I, _I, _I], C.c_size_t),
+               "pgk_grouped_gemm_sorted_splits": ([_I, _I, _I, _I, _I], C.c_int),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}

@@ -2,12 +2,11 @@
 
 TransformerConfig carries the dimensions; ModelSpec is the data-only description of one
 architecture family (HF tensor-name patterns + architecture flags + default hyper-parameters).
-Only dense families on the hot path are described: GPT-2, Llama, Qwen2, Qwen3 (MoE families are
-out of scope)."""
+Described: GPT-2, Llama, Qwen2, Qwen3 and the MoE families Mixtral and Qwen3-MoE (config.py:230-389)."""
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Literal
 
 
@@ -95,16 +94,38 @@ GPT2_SPEC = ModelSpec(
     norm_type="layernorm", activation="gelu", use_rope=False, use_qk_norm=False, use_position_embed=True,
     qkv_combined=True, weight_transpose=True, default_norm_eps=1e-5, default_rope_theta=10000.0, hf_model_type="gpt2")
 
+
+def _moe_spec(base: ModelSpec, name: str, mlp: str, expert: str, gate: str, up: str, down: str, eps: float, theta: float) -> ModelSpec:
+    """A decoder spec whose dense MLP is replaced by a router ({mlp}.gate) and per-expert projections."""
+    L = "model.layers.{layer}." + mlp + "."
+    E = L + expert + ".{expert}."
+    return replace(base, name=name, gate_proj=None, up_proj=None, down_proj=None, moe_gate=L + "gate.weight",
+                   expert_gate_proj=E + gate + ".weight", expert_up_proj=E + up + ".weight", expert_down_proj=E + down + ".weight",
+                   is_moe=True, default_norm_eps=eps, default_rope_theta=theta, hf_model_type=name)
+
+
+MIXTRAL_SPEC = _moe_spec(LLAMA_SPEC, "mixtral", "block_sparse_moe", "experts", "w1", "w3", "w2", eps=1e-5, theta=1000000.0)
+QWEN3_MOE_SPEC = _moe_spec(QWEN3_SPEC, "qwen3_moe", "mlp", "experts", "gate_proj", "up_proj", "down_proj", eps=1e-6, theta=10000000.0)
+
 MODEL_SPECS: dict[str, ModelSpec] = {"gpt2": GPT2_SPEC, "llama": LLAMA_SPEC, "qwen3": QWEN3_SPEC, "qwen2": QWEN2_SPEC}
+# the reference keeps these in MODEL_SPECS too; here that registry stays the dense families' (its callers and tests
+# enumerate it as such) and the MoE families sit beside it
+MOE_MODEL_SPECS: dict[str, ModelSpec] = {"mixtral": MIXTRAL_SPEC, "qwen3_moe": QWEN3_MOE_SPEC}
 
 
 def detect_model_spec(tensor_names: list[str]) -> ModelSpec:
-    """Pick the family from checkpoint tensor names (config.py:380-431): QK-norm -> Qwen3, QKV biases ->
-    Qwen2, model.embed_tokens -> Llama, wte -> GPT-2.  MoE checkpoints are rejected (out of scope)."""
+    """Pick the family from checkpoint tensor names (config.py:380-431): block_sparse_moe -> Mixtral, mlp.experts with
+    QK-norm -> Qwen3-MoE, QK-norm -> Qwen3, QKV biases -> Qwen2, model.embed_tokens -> Llama, wte -> GPT-2.  Other MoE
+    checkpoints (mlp.experts without QK-norm: Qwen2-MoE and kin) are rejected."""
     names = set(tensor_names)
-    if any("block_sparse_moe" in n or "mlp.experts" in n for n in names):
-        raise ValueError("MoE checkpoints are not supported by pygpukit_amd")
-    if any("q_norm" in n for n in names):
+    if any("block_sparse_moe" in n for n in names):
+        return MIXTRAL_SPEC
+    has_qk_norm = any("q_norm" in n for n in names)
+    if any("mlp.experts" in n for n in names):
+        if has_qk_norm:
+            return QWEN3_MOE_SPEC
+        raise ValueError("MoE checkpoint without QK-norm (mlp.experts): only Mixtral and Qwen3-MoE are supported")
+    if has_qk_norm:
         return QWEN3_SPEC
     if "model.embed_tokens.weight" in names:
         return QWEN2_SPEC if "model.layers.0.self_attn.q_proj.bias" in names else LLAMA_SPEC

@@ -2,7 +2,9 @@
 CausalTransformerModel, architecture and dimensions inferred from tensor names and shapes exactly as the reference does
 (detect_model_spec; head_dim from the QK-norm weight or the 128/64/256 probe; rope_theta / rms_norm_eps and the FP8
 `quantization_config` from a sibling config.json).  Tensors whose stored dtype equals the target dtype go from the file
-mapping straight to device memory; others are converted on the host first.  MoE checkpoints are out of scope."""
+mapping straight to device memory; others are converted on the host first.  Mixtral and Qwen3-MoE checkpoints build
+MoELayer feed-forward blocks (loader.py:111, :364-415); MoE variants with shared experts, dense layers
+(mlp_only_layers, decoder_sparse_step) or un-renormalised top-k weights are rejected."""
 
 from __future__ import annotations
 
@@ -15,8 +17,9 @@ import numpy as np
 from pygpukit_amd.core.array import GPUArray
 from pygpukit_amd.core.dtypes import bfloat16, float16, float32, uint8
 from pygpukit_amd.core.factory import from_numpy
-from pygpukit_amd.llm.config import GPT2_SPEC, LLAMA_SPEC, QWEN3_SPEC, ModelSpec, TransformerConfig, detect_model_spec
-from pygpukit_amd.llm.layers import MLP, Attention, Norm, TransformerBlock
+from pygpukit_amd.llm.config import (GPT2_SPEC, LLAMA_SPEC, MIXTRAL_SPEC, QWEN3_MOE_SPEC, QWEN3_SPEC, ModelSpec,
+                                     TransformerConfig, detect_model_spec)
+from pygpukit_amd.llm.layers import MLP, Attention, MoELayer, Norm, TransformerBlock
 from pygpukit_amd.llm.layers.linear import LinearBF16, LinearFP8
 from pygpukit_amd.llm.models.causal import CausalTransformerModel
 from pygpukit_amd.llm.safetensors import Dtype, load_safetensors
@@ -141,7 +144,10 @@ def load_model_from_safetensors(model_path: str, dtype: str = "bfloat16", spec: 
         head_dim = hidden_size // int(hf_config["n_head"])
     num_heads = q_dim // head_dim
     num_kv_heads = num_heads if spec.qkv_combined else st.tensor_info(nm(spec.k_proj, 0)).shape[0] // head_dim
-    if spec.activation == "silu":
+    moe = _moe_fields(spec, hf_config, names) if spec.is_moe else {}
+    if spec.is_moe:
+        intermediate = int(hf_config.get("intermediate_size") or moe["moe_intermediate_size"])
+    elif spec.activation == "silu":
         intermediate = st.tensor_info(nm(spec.gate_proj, 0)).shape[0]
     else:
         fc1 = st.tensor_info(nm(spec.fc1, 0)).shape
@@ -152,7 +158,7 @@ def load_model_from_safetensors(model_path: str, dtype: str = "bfloat16", spec: 
                             activation=spec.activation, use_rope=spec.use_rope,
                             max_position_embeddings=int(hf_config.get("max_position_embeddings", hf_config.get("n_positions", 2048))),
                             norm_eps=float(hf_config.get("rms_norm_eps", hf_config.get("layer_norm_epsilon", spec.default_norm_eps))),
-                            rope_theta=float(hf_config.get("rope_theta", spec.default_rope_theta)))
+                            rope_theta=float(hf_config.get("rope_theta", spec.default_rope_theta)), **moe)
     eps = cfg.norm_eps
 
     blocks = []
@@ -177,7 +183,14 @@ def load_model_from_safetensors(model_path: str, dtype: str = "bfloat16", spec: 
             attn = Attention(load_linear(nm(spec.q_proj, layer), nm(spec.q_bias, layer)), load_linear(nm(spec.k_proj, layer), nm(spec.k_bias, layer)),
                              load_linear(nm(spec.v_proj, layer), nm(spec.v_bias, layer)), load_linear(nm(spec.o_proj, layer), nm(spec.o_bias, layer)),
                              cfg, q_norm=qn, k_norm=kn)
-        if spec.activation == "silu":
+        if spec.is_moe:
+            def ex(pattern: str, e: int, layer=layer):
+                w = load_linear(pattern.format(layer=layer, expert=e))
+                return w.weight if isinstance(w, LinearBF16) else w
+            experts = [(ex(spec.expert_gate_proj, e), ex(spec.expert_up_proj, e), ex(spec.expert_down_proj, e))
+                       for e in range(cfg.num_experts)]
+            mlp = MoELayer(cfg, load_tensor(nm(spec.moe_gate, layer)), experts)
+        elif spec.activation == "silu":
             g, u_, d = (load_linear(nm(spec.gate_proj, layer)), load_linear(nm(spec.up_proj, layer)), load_linear(nm(spec.down_proj, layer)))
             if isinstance(g, LinearBF16) and isinstance(u_, LinearBF16) and g.bias is None and u_.bias is None:
                 g, u_ = g.weight, u_.weight                               # lets MLP fuse gate|up into one matrix
@@ -191,6 +204,26 @@ def load_model_from_safetensors(model_path: str, dtype: str = "bfloat16", spec: 
     lm_head = try_load(spec.lm_head) if spec.lm_head else None            # tied embeddings when absent
     position_embed = try_load(spec.position_embed) if spec.use_position_embed else None
     return CausalTransformerModel(cfg, load_tensor(spec.embed_tokens), blocks, final_norm, lm_head, position_embed, spec)
+
+
+def _moe_fields(spec: ModelSpec, hf_config: dict, names: set[str]) -> dict:
+    """num_experts / num_experts_per_tok / moe_intermediate_size from config.json (Mixtral: num_local_experts and
+    intermediate_size; Qwen3-MoE: num_experts and moe_intermediate_size), after rejecting what MoELayer does not do."""
+    if any("shared_expert" in n for n in names) or hf_config.get("shared_expert_intermediate_size"):
+        raise ValueError("MoE checkpoints with shared experts are not supported")
+    if hf_config.get("mlp_only_layers"):
+        raise ValueError("MoE checkpoints with dense layers (mlp_only_layers) are not supported")
+    if int(hf_config.get("decoder_sparse_step", 1)) != 1:
+        raise ValueError("MoE checkpoints with decoder_sparse_step != 1 are not supported")
+    if spec.name == "qwen3_moe" and hf_config.get("norm_topk_prob") is False:
+        raise ValueError("MoE checkpoints with norm_topk_prob: false are not supported (the top-k weights are renormalised)")
+    E = hf_config.get("num_local_experts", hf_config.get("num_experts"))
+    k = hf_config.get("num_experts_per_tok")
+    inter = hf_config.get("moe_intermediate_size", hf_config.get("intermediate_size"))
+    if E is None or k is None or inter is None:
+        raise ValueError("MoE checkpoint: config.json must give num_local_experts / num_experts, num_experts_per_tok and "
+                         "moe_intermediate_size / intermediate_size")
+    return dict(num_experts=int(E), num_experts_per_tok=int(k), moe_intermediate_size=int(inter))
 
 
 def _bf16_array(bits: np.ndarray) -> GPUArray:
@@ -218,5 +251,13 @@ def load_qwen3_from_safetensors(model_path: str, dtype: str = "bfloat16") -> Cau
     return load_model_from_safetensors(model_path, dtype=dtype, spec=QWEN3_SPEC)
 
 
+def load_mixtral_from_safetensors(model_path: str, dtype: str = "bfloat16") -> CausalTransformerModel:
+    return load_model_from_safetensors(model_path, dtype=dtype, spec=MIXTRAL_SPEC)
+
+
+def load_qwen3_moe_from_safetensors(model_path: str, dtype: str = "bfloat16") -> CausalTransformerModel:
+    return load_model_from_safetensors(model_path, dtype=dtype, spec=QWEN3_MOE_SPEC)
+
+
 __all__ = ["load_model_from_safetensors", "load_gpt2_from_safetensors", "load_llama_from_safetensors", "load_qwen3_from_safetensors",
-           "FP8QuantConfig"]
+           "load_mixtral_from_safetensors", "load_qwen3_moe_from_safetensors", "FP8QuantConfig"]

@@ -194,6 +194,8 @@ class CausalTransformerModel:
         from pygpukit_amd.llm.layers.linear import LinearFP8
 
         c = self.config
+        if c.is_moe:
+            raise NotImplementedError("the native engine covers dense models")
         if c.norm_type != "rmsnorm" or c.activation != "silu" or not c.use_rope or self.position_embed is not None:
             raise NotImplementedError("the native engine covers RMSNorm + SwiGLU + RoPE models (Llama / Qwen families)")
         if self.embed_tokens.dtype != bfloat16:
