@@ -341,6 +341,33 @@ pgk_status pgk_quantize_fp8_rows(const void* x, uint8_t* out_fp8, float* out_sca
 pgk_status pgk_quantize_fp8_blocks(const void* w_bf16, uint8_t* out_fp8, void* out_scale_bf16, int n, int k,
                                    pgk_stream s);
 
+/* ----------------------------------------------------------------------- NVF4 ------ */
+/* NVF4 (native/ops/matmul/gemv/w4a16_bf16/sm120/nvf4.cuh:36-110): a 4-bit code c has sign bit 3 and magnitude
+ * {0, .5, 1, 1.5, 2, 3, 4, 6}[c & 7]; a byte holds k (even) in its low nibble, k+1 in its high nibble.  Weights:
+ * data [K/2, N] (byte (k/2)*N + n), scale [ceil(K/32), N] (byte (k/32)*N + n) with a scale byte s worth
+ * (1 + (s&7)/8) * 2^(((s>>3)&15) - 7); bit 7 is ignored. */
+/* quantize_bf16_to_nvf4 (nvf4_kernels.cu:239-320): x_kn bf16 [K,N] -> data + scale, per (column, 32-row block):
+ * scale = max|x|/6 (1 when max|x| <= 1e-8), encoded as above (exponent and mantissa clamped, never rounded up
+ * past mantissa 7), codes = the threshold chain 0.25 .. 5.0 of x * (1 / decoded scale), ties away from zero,
+ * NaN -> +6.  K even (the reference writes past the data for odd K). */
+pgk_status pgk_quantize_nvf4(const void* x_kn, uint8_t* data, uint8_t* scale, int k, int n, pgk_stream s);
+/* gemv_nvf4_bf16_sm120 (nvf4_kernels.cu:19-235): C[n] = bf16(alpha * sum_k a[k] * e2m1(k,n) * scale(k/32,n)),
+ * fp32 accumulation in a fixed order (no atomics).  a bf16 [K], C bf16 [N]; K even, any K % 32.  workspace:
+ * pgk_gemv_nvf4_workspace_bytes(k, n) bytes (0: may be NULL) for the partial sums of a K split. */
+size_t pgk_gemv_nvf4_workspace_bytes(int k, int n);
+pgk_status pgk_gemv_nvf4_bf16(const void* a, const uint8_t* data, const uint8_t* scale, void* c, void* workspace, int k,
+                              int n, float alpha, pgk_stream s);
+/* The operand packer of gemm_nvf4_bf16_sm120 (nvf4_cutlass.cu:157-317): unit-scale e2m1 of bf16 (thresholds
+ * 0.25 .. 5.0 on |x|, ties away from zero, NaN -> +0, +-inf -> +-6) packed K-contiguous into out [rows, Kp/2],
+ * Kp = k rounded up to a multiple of 128, zero nibbles past k.  transpose = 0: x is [rows, k] (A); transpose = 1:
+ * x is [k, rows] (B [K,N], rows = N).  k % 32 == 0; out 16-byte aligned (x too when transpose = 0). */
+pgk_status pgk_quantize_e2m1_unit(const void* x, uint8_t* out, int rows, int k, int transpose, pgk_stream s);
+/* D[m][n] = bf16(sum_k e2m1(a[m][k]) * e2m1(b[n][k])) on operands packed by pgk_quantize_e2m1_unit, exact in fp32
+ * for K < 116000 (v_mfma_scale_f32_16x16x128_f8f6f4, e2m1 operands, unit scales).  kp % 128 == 0; d bf16 [M,N]. */
+pgk_status pgk_gemm_fp4_nt(const uint8_t* a_packed, const uint8_t* b_packed, void* d, int m, int n, int kp, pgk_stream s);
+/* Bytes of the packed A and B of one gemm_nvf4_bf16_sm120 call: (m + n) * Kp/2 (A first, B at m * Kp/2). */
+size_t pgk_gemm_nvf4_workspace_bytes(int m, int n, int k);
+
 /* ------------------------------------------------------------------- attention ------ */
 /* ops.cuh:287-290 sdpa_causal(Q[Hq,q,D], K[Hkv,kv,D], V, scale<=0 -> 1/sqrt(D)), mask
  * kv_pos < (kv_len - q_len) + q_pos + 1.  Strides are in elements so both the reference's

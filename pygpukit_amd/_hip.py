@@ -84,6 +84,8 @@ _PROTOS = {
     "pgk_gemm_fp8_nt": [_V, _V, _V, _V, _V, _I, _I, _I, _V], "pgk_gemm_fp8_fp8_nn": [_V, _V, _V, _V, _V, _I, _I, _I, _V],
     "pgk_quantize_fp8_rows": [_V, _V, _V, _I, _I, _I, _V],
     "pgk_quantize_fp8_blocks": [_V, _V, _V, _I, _I, _V],
+    "pgk_quantize_nvf4": [_V, _V, _V, _I, _I, _V], "pgk_gemv_nvf4_bf16": [_V, _V, _V, _V, _V, _I, _I, _F, _V],
+    "pgk_quantize_e2m1_unit": [_V, _V, _I, _I, _I, _V], "pgk_gemm_fp4_nt": [_V, _V, _V, _I, _I, _I, _V],
     "pgk_paged_attention_v1": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
     "pgk_paged_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
     "pgk_scatter_last_token_logits": [_V, _V, _V, _V, _I, _I, _I, _V], "pgk_prepare_position_ids": [_V, _V, _V, _V, _V, _I, _V],
@@ -127,6 +129,8 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_st_tensor_name": ([_V, _I], C.c_char_p),
                "pgk_moe_max_tiles": ([_I, _I, _I], C.c_int), "pgk_moe_workspace_bytes": ([_I, _I, _I], C.c_size_t),
                "pgk_grouped_gemm_sorted_splits": ([_I, _I, _I, _I, _I], C.c_int),
+               "pgk_gemv_nvf4_workspace_bytes": ([_I, _I], C.c_size_t),
+               "pgk_gemm_nvf4_workspace_bytes": ([_I, _I, _I], C.c_size_t),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}
