@@ -351,6 +351,10 @@ pgk_status pgk_quantize_fp8_blocks(const void* w_bf16, uint8_t* out_fp8, void* o
  * past mantissa 7), codes = the threshold chain 0.25 .. 5.0 of x * (1 / decoded scale), ties away from zero,
  * NaN -> +6.  K even (the reference writes past the data for odd K). */
 pgk_status pgk_quantize_nvf4(const void* x_kn, uint8_t* data, uint8_t* scale, int k, int n, pgk_stream s);
+/* The engine's NK layout of the same format (this project's, not the reference's): x_nk bf16 [N,K] -> data [N, K/2]
+ * (byte j of row n holds k = 2j in its low nibble, 2j+1 in its high nibble) and scale [N, K/32].  Its bytes are the
+ * transpose of pgk_quantize_nvf4 on x_nk^T (same arithmetic per 32-k block).  K % 32 == 0; x_nk and data 16-byte aligned. */
+pgk_status pgk_quantize_nvf4_nk(const void* x_nk, uint8_t* data, uint8_t* scale, int n, int k, pgk_stream s);
 /* gemv_nvf4_bf16_sm120 (nvf4_kernels.cu:19-235): C[n] = bf16(alpha * sum_k a[k] * e2m1(k,n) * scale(k/32,n)),
  * fp32 accumulation in a fixed order (no atomics).  a bf16 [K], C bf16 [N]; K even, any K % 32.  workspace:
  * pgk_gemv_nvf4_workspace_bytes(k, n) bytes (0: may be NULL) for the partial sums of a K split. */
@@ -399,14 +403,19 @@ typedef struct {
     float norm_eps, rope_theta;
     int weight_format;    /* 0 = bf16 linears, 1 = fp8-e4m3 linears with 128x128 bf16 block scales (w8a16),
                            * 2 = as 1, and prefill of > 128 tokens also quantises activations per row per 128 k
-                           *     and runs the projections on the fp8 x fp8 MFMA GEMM (decode stays w8a16) */
+                           *     and runs the projections on the fp8 x fp8 MFMA GEMM (decode stays w8a16),
+                           * 3 = NVF4 linears (w4a16) in the NK layout of pgk_quantize_nvf4_nk: w_* = uint8 codes
+                           *     [N, K/2] (16-byte aligned), s_* = uint8 scale bytes [N, K/32] (required).  Decode
+                           *     streams the codes (GEMV chunks of <= 8 sequences); prefill dequantises one layer at a
+                           *     time into an engine scratch (counted by pgk_engine_bytes) and runs the bf16 GEMMs.
+                           *     Formats 1-3 need hidden_size and intermediate_size multiples of 128. */
     int use_qk_norm;
 } pgk_model_config_t;
 
 typedef struct {
     const void* attn_norm;          /* [H] bf16 */
     const void* w_qkv;              /* [(Hq+2Hkv)*D, H] bf16 or u8 */
-    const void* s_qkv;              /* fp8 block scales or NULL */
+    const void* s_qkv;              /* fp8 block scales, NVF4 scale bytes [N, K/32] (format 3), or NULL */
     const void* q_norm; const void* k_norm;   /* [D] bf16 or NULL */
     const void* w_o;  const void* s_o;        /* [H, Hq*D] */
     const void* mlp_norm;           /* [H] */

@@ -84,7 +84,7 @@ _PROTOS = {
     "pgk_gemm_fp8_nt": [_V, _V, _V, _V, _V, _I, _I, _I, _V], "pgk_gemm_fp8_fp8_nn": [_V, _V, _V, _V, _V, _I, _I, _I, _V],
     "pgk_quantize_fp8_rows": [_V, _V, _V, _I, _I, _I, _V],
     "pgk_quantize_fp8_blocks": [_V, _V, _V, _I, _I, _V],
-    "pgk_quantize_nvf4": [_V, _V, _V, _I, _I, _V], "pgk_gemv_nvf4_bf16": [_V, _V, _V, _V, _V, _I, _I, _F, _V],
+    "pgk_quantize_nvf4": [_V, _V, _V, _I, _I, _V], "pgk_quantize_nvf4_nk": [_V, _V, _V, _I, _I, _V], "pgk_gemv_nvf4_bf16": [_V, _V, _V, _V, _V, _I, _I, _F, _V],
     "pgk_quantize_e2m1_unit": [_V, _V, _I, _I, _I, _V], "pgk_gemm_fp4_nt": [_V, _V, _V, _I, _I, _I, _V],
     "pgk_paged_attention_v1": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
     "pgk_paged_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],

@@ -61,6 +61,7 @@ pgk_status gemm_fp8_swiglu_nt(const uint8_t* a, const float* sa, const uint8_t* 
                               int K, hipStream_t st);
 pgk_status wsgemm_nt(const bf16* a, int lda, const void* w, const bf16* wscale, bool fp8, void* c, const bf16* bias, int mode,
                      int splits, int M, int N, int K, hipStream_t st);
+pgk_status dequant_nvf4_nk(const uint8_t* data, const uint8_t* scale, bf16* out, int n, int k, hipStream_t st);   // ops_nvf4.hip
 
 // --------------------------------------------------------------------------------------------
 // Fused GEMV kernel: prologue builds x[M][K] in LDS, body streams W, epilogue consumes y.
@@ -88,7 +89,11 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
     const TLStamp tls(tl);
     constexpr int NW = WTraits<WT>::NW;
     constexpr bool FP8 = std::is_same<WT, fp8e4m3>::value;
-    constexpr int KC = C * 64 * NW;           // compile-time K (0 = runtime)
+    constexpr bool NV4 = std::is_same<WT, nvf4x2>::value;   // wscale_ then holds the uint8 scale bytes [N, K/32]
+    // NVF4: C counts 1024-k units (32 lanes x 32 k); an odd C leaves the upper half-wave of the last chunk without a k of
+    // its own - it re-reads the lower half's and weighs it 0
+    constexpr int KC = NV4 ? C * 1024 : C * 64 * NW;   // compile-time K (0 = runtime)
+    constexpr int CL = NV4 ? (C + 1) / 2 : C;          // 16-byte chunks per lane and row
     constexpr int KJ = KC / 256;              // activation elements per thread
     extern __shared__ __attribute__((aligned(16))) char smem[];
     XT* xs = reinterpret_cast<XT*>(smem);  // [M][K]
@@ -106,8 +111,8 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
         else return min(n0 + r, N - 1);
     };
 
-    uint4 pre[R][C > 0 ? C : 1];
-    float psc[R][C > 0 ? C : 1];
+    uint4 pre[R][CL > 0 ? CL : 1];
+    float psc[R][CL > 0 ? CL : 1];
     float resv[R][M];
     if constexpr (C > 0) {
         // ---- all global loads of the first trip, issued back to back; nothing is waited for until the prologue's ALU ----
@@ -121,6 +126,17 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int row = row_of(nf, r);
+                if constexpr (NV4) {
+                    const uint8_t* wr = reinterpret_cast<const uint8_t*>(w_) + (size_t)row * (KC >> 1);
+                    const uint8_t* sr = reinterpret_cast<const uint8_t*>(wscale_) + (size_t)row * (KC >> 5);
+#pragma unroll
+                    for (int c = 0; c < CL; ++c) {
+                        const int k0 = lane * NW + c * 64 * NW, kk = k0 < KC ? k0 : k0 - 1024;
+                        pre[r][c] = load_nt16(wr + (kk >> 1));
+                        psc[r][c] = k0 < KC ? nvf4_scale_value(sr[kk >> 5]) : 0.f;
+                    }
+                    continue;
+                }
                 const WT* wr = reinterpret_cast<const WT*>(w_) + (size_t)row * KC;
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
@@ -149,10 +165,15 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
             if constexpr (VW == 4) *reinterpret_cast<float4*>(base + run0(v)) = make_float4(src[0], src[1], src[2], src[3]);
             else *reinterpret_cast<float2*>(base + run0(v)) = make_float2(src[0], src[1]);
         };
-        auto stx = [&](int m, int v, const float* src) {        // the LDS image of row m
-            if constexpr (std::is_same<XT, float>::value) strun(reinterpret_cast<float*>(xs) + (size_t)m * KC, v, src);
-            else if constexpr (VW == 4) *reinterpret_cast<uint2*>(xs + (size_t)m * KC + run0(v)) = make_uint2(pack_bf16x2(src[0], src[1]), pack_bf16x2(src[2], src[3]));
-            else *reinterpret_cast<uint32_t*>(xs + (size_t)m * KC + run0(v)) = pack_bf16x2(src[0], src[1]);
+        auto stx = [&](int m, int v, const float* src) {        // the LDS image of row m (NVF4: swizzled, a run stays in one group)
+            const int at = NV4 ? nvf4_xpos<XT>(run0(v), KC) : run0(v);
+            if constexpr (std::is_same<XT, float>::value) {
+                float* d = reinterpret_cast<float*>(xs) + (size_t)m * KC + at;
+                if constexpr (VW == 4) *reinterpret_cast<float4*>(d) = make_float4(src[0], src[1], src[2], src[3]);
+                else *reinterpret_cast<float2*>(d) = make_float2(src[0], src[1]);
+            }
+            else if constexpr (VW == 4) *reinterpret_cast<uint2*>(xs + (size_t)m * KC + at) = make_uint2(pack_bf16x2(src[0], src[1]), pack_bf16x2(src[2], src[3]));
+            else *reinterpret_cast<uint32_t*>(xs + (size_t)m * KC + at) = pack_bf16x2(src[0], src[1]);
         };
         // ---- activation loads ----
         if constexpr (EPI == EPI_RESID) {
@@ -273,11 +294,17 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
                 for (int i = threadIdx.x; i < K; i += 256) {
                     const float v = xin(i);
                     if constexpr (PRO == PRO_NORM_SUM) { if (blockIdx.x == 0) a.h_out[(size_t)m * K + i] = v; }
-                    store_x<XT>(xs, m * K + i, v * inv * to_f(gamma_[i]));
+                    store_x<XT>(xs, m * K + (NV4 ? nvf4_xpos<XT>(i, K) : i), v * inv * to_f(gamma_[i]));
                 }
             }
         } else if constexpr (PRO == PRO_PLAIN) {
-            for (int i = threadIdx.x; i < M * K; i += 256) store_x<XT>(xs, i, x_[i]);
+            if constexpr (NV4) {
+#pragma unroll
+                for (int m = 0; m < M; ++m)
+                    for (int i = threadIdx.x; i < K; i += 256) store_x<XT>(xs, m * K + nvf4_xpos<XT>(i, K), x_[(size_t)m * K + i]);
+            } else {
+                for (int i = threadIdx.x; i < M * K; i += 256) store_x<XT>(xs, i, x_[i]);
+            }
         }
     }
     __syncthreads();
@@ -298,7 +325,7 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
         if (C > 0 && g == wave) {
             // consume the preloaded chunks
 #pragma unroll
-            for (int c = 0; c < (C > 0 ? C : 1); ++c) {
+            for (int c = 0; c < (C > 0 ? CL : 1); ++c) {
                 const int k0 = lane * NW + c * 64 * NW;
                 if constexpr (std::is_same<WT, bf16>::value && std::is_same<XT, bf16>::value) {
                     uint4 xr[M];
@@ -310,6 +337,22 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
                         for (int m = 0; m < M; ++m) acc[r][m] = dot8_bf16(pre[r][c], xr[m], acc[r][m]);
                     continue;
                 }
+                if constexpr (NV4) {
+                    uint4 raw[R];
+                    float p[R][M];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        raw[r] = pre[r][c];
+#pragma unroll
+                        for (int m = 0; m < M; ++m) p[r][m] = 0.f;
+                    }
+                    nvf4_dot32<XT, M, R>(raw, xs, K, k0 < KC ? k0 : k0 - 1024, p);
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int m = 0; m < M; ++m) acc[r][m] = fmaf(psc[r][c], p[r][m], acc[r][m]);
+                    continue;
+                } else {
                 float xf[M][NW];
 #pragma unroll
                 for (int m = 0; m < M; ++m) XLoad<XT, NW>::load(xs + (size_t)m * K + k0, xf[m]);
@@ -330,7 +373,18 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
                         }
                     }
                 }
+                }
             }
+        } else if constexpr (NV4) {
+            const uint8_t* wrow[R];
+            const uint8_t* srow[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int row = row_of(n0, r);
+                wrow[r] = reinterpret_cast<const uint8_t*>(w_) + (size_t)row * (K >> 1);
+                srow[r] = reinterpret_cast<const uint8_t*>(wscale_) + (size_t)row * (K >> 5);
+            }
+            gemv_rows_nvf4<XT, M, R>(wrow, srow, xs, K, K, lane, acc);
         } else {
             const WT* wrow[R];
             const bf16* srow[R];
@@ -1579,6 +1633,9 @@ struct Engine {
     bf16* packed_lm = nullptr;      // fragment-major lm_head for the batched (3..64 sequences) lm_head kernels; PGK_PACKED_LMHEAD=0: none
     float* dec_slabs = nullptr;     // 17..64 sequences on the packed kernels: split-K slabs of o_proj / down_proj [splits][M][H] (PGK_PACKED_DECODE=0: engine_batched kernels)
     bool packed_decode = false;
+    // NVF4 engines (weight_format 3): ONE layer's linears dequantised to row-major bf16 [qkv | o | gate_up | down], refilled
+    // by the prefill in front of every layer's projections (never a copy of all layers)
+    bf16* nv_deq = nullptr;
     // prefill workspace (grown on demand, outside capture)
     void* pf = nullptr;
     size_t pf_bytes = 0;
@@ -1631,19 +1688,26 @@ static pgk_status launch_fused_c(const FusedArgs& a, int n_out, hipStream_t st, 
 template <class WT, class XT, int M, int R, int PRO, int EPI>
 static pgk_status launch_fused(const FusedArgs& a, int n_out, hipStream_t st, int force_grid = 0) {
     constexpr int NW = WTraits<WT>::NW;
-    const int c = (a.K % (64 * NW) == 0) ? a.K / (64 * NW) : 0;
+    constexpr bool NV4 = std::is_same<WT, nvf4x2>::value;   // NVF4: C in 1024-k units, (C + 1) / 2 chunks per lane
+    constexpr int UNIT = NV4 ? 1024 : 64 * NW;
+    const int c = (a.K % UNIT == 0) ? a.K / UNIT : 0;
     constexpr int BUDGET = 12 / R;  // R*C*4 preload VGPRs <= 48
     if constexpr (1 <= BUDGET) { if (c == 1) return launch_fused_c<WT, XT, M, R, PRO, EPI, 1>(a, n_out, st, force_grid); }
-    if constexpr (2 <= BUDGET) { if (c == 2) return launch_fused_c<WT, XT, M, R, PRO, EPI, 2>(a, n_out, st, force_grid); }
-    if constexpr (3 <= BUDGET) { if (c == 3) return launch_fused_c<WT, XT, M, R, PRO, EPI, 3>(a, n_out, st, force_grid); }
-    if constexpr (4 <= BUDGET) { if (c == 4) return launch_fused_c<WT, XT, M, R, PRO, EPI, 4>(a, n_out, st, force_grid); }
-    if constexpr (6 <= BUDGET) { if (c == 6) return launch_fused_c<WT, XT, M, R, PRO, EPI, 6>(a, n_out, st, force_grid); }
+    if constexpr ((NV4 ? 1 : 2) <= BUDGET) { if (c == 2) return launch_fused_c<WT, XT, M, R, PRO, EPI, 2>(a, n_out, st, force_grid); }
+    if constexpr ((NV4 ? 2 : 3) <= BUDGET) { if (c == 3) return launch_fused_c<WT, XT, M, R, PRO, EPI, 3>(a, n_out, st, force_grid); }
+    if constexpr ((NV4 ? 2 : 4) <= BUDGET) { if (c == 4) return launch_fused_c<WT, XT, M, R, PRO, EPI, 4>(a, n_out, st, force_grid); }
+    if constexpr ((NV4 ? 3 : 6) <= BUDGET) { if (c == 6) return launch_fused_c<WT, XT, M, R, PRO, EPI, 6>(a, n_out, st, force_grid); }
     return launch_fused_c<WT, XT, M, R, PRO, EPI, 0>(a, n_out, st, force_grid);
 }
 
 // rows-per-wave heuristic: enough workgroups to cover 256 CUs even for the N = hidden projections
 template <class WT, class XT, int M, int PRO, int EPI>
 static pgk_status launch_fused_auto(const FusedArgs& a, int n_out, hipStream_t st) {
+    if constexpr (std::is_same<WT, nvf4x2>::value && M >= 4) {
+        // NVF4, 4 / 8 sequences: 4 rows per wave hold 2 x R x M partial sums besides the activation fragments - 190 to 256
+        // VGPRs, one wave per SIMD; 2 rows per wave stay near the bf16 kernels' ~120
+        return launch_fused<WT, XT, M, 2, PRO, EPI>(a, n_out, st);
+    }
     if constexpr (EPI == EPI_SWIGLU) {
         // One sequence, mid-sized gate/up (Qwen3-0.6B: 3072 pairs): 3 pairs per wave = 256 workgroups, one per CU.  Every
         // workgroup's prologue re-reads h and the 8 o_proj partial vectors (36 KB from L2); with 768 two-pair workgroups that
@@ -1763,7 +1827,8 @@ static pgk_status launch_attn(Engine* e, int layer, int b0, int m, bool fused, b
         mark(KC_OPROJ);
         a.rows_per_block = e->moproj_rows;
         const dim3 g2((c.hidden_size / e->moproj_rows) * c.num_kv_heads, 1, m);
-        const bool f8 = c.weight_format != 0;
+        PGK_REQUIRE(c.weight_format != 3, "engine: merged o_proj has no NVF4 form");
+        const bool f8 = c.weight_format == 1 || c.weight_format == 2;
 #define PGK_MO(GG)                                                                                             \
     case GG:                                                                                                   \
         he = f8 ? launch_k(attn_merge_oproj_kernel<D, GG, true>, g2, dim3(256), 0, st, a)                       \
@@ -2084,13 +2149,17 @@ static pgk_status decode_step_impl(Engine* e, int batch, hipStream_t st, int* la
         // kernels exist for M = 1, 2, 4, 8 only, so 3 / 5 / 6 / 7 sequences would take two or three weight passes there
         // (measured: 7 sequences 2.46 ms against 1.05).  GEMV stays for exactly 1, 2 and 4 (0.70 / 0.93 / 0.82 ms).
         const bool mfma_ok = e->batched_mfma && (rem >= e->batched_min || (e->batched_min == 5 && rem == 3));
-        if (mfma_ok) {
+        if constexpr (std::is_same<WT, nvf4x2>::value) {
+            // NVF4 (w4a16): GEMV chunks of <= 8 sequences only, each re-reading the weights; batched_mfma is off for it
+        } else if (mfma_ok) {
             const int m = rem > e->batched_max ? e->batched_max : rem;
             if (m > 16 && e->packed_decode) r = decode_chunk_packed(e, b0, m, rem == m, st, launches, short_ctx);
             else r = decode_chunk_batched<WT>(e, b0, m, rem == m, st, launches, short_ctx);
             b0 += m;
+            if (r != PGK_OK) return r;
+            continue;
         }
-        else if (rem >= 8) { r = decode_chunk<WT, bf16, 8>(e, b0, rem == 8, st, launches, short_ctx); b0 += 8; }
+        if (rem >= 8) { r = decode_chunk<WT, bf16, 8>(e, b0, rem == 8, st, launches, short_ctx); b0 += 8; }
         else if (rem >= 4) { r = decode_chunk<WT, bf16, 4>(e, b0, rem == 4, st, launches, short_ctx); b0 += 4; }
         else if (rem >= 2) { r = decode_chunk<WT, float, 2>(e, b0, rem == 2, st, launches, short_ctx); b0 += 2; }
         else { r = decode_chunk<WT, float, 1>(e, b0, true, st, launches, short_ctx); b0 += 1; }
@@ -2102,6 +2171,7 @@ static pgk_status decode_step_impl(Engine* e, int batch, hipStream_t st, int* la
 // short_ctx: the step's launch sequence for contexts <= SHORT_CTX (ignored - long sequence - when the engine has no such path)
 static pgk_status decode_step(Engine* e, int batch, hipStream_t st, int* launches, bool short_ctx) {
     short_ctx = short_ctx && e->short_path;
+    if (e->cfg.weight_format == 3) return decode_step_impl<nvf4x2>(e, batch, st, launches, short_ctx);
     if (e->cfg.weight_format != 0) return decode_step_impl<fp8e4m3>(e, batch, st, launches, short_ctx);
     return decode_step_impl<bf16>(e, batch, st, launches, short_ctx);
 }
@@ -2159,7 +2229,21 @@ pgk_status pgk_engine_create(const pgk_model_config_t* cfg, const void* embed, c
     PGK_REQUIRE(G >= 1, "pgk_engine_create: GQA group %d", G);
     PGK_REQUIRE(c.hidden_size % 16 == 0 && c.intermediate_size % 16 == 0, "pgk_engine_create: sizes must be multiples of 16");
     PGK_REQUIRE(c.weight_format == 0 || (c.hidden_size % 128 == 0 && c.intermediate_size % 128 == 0),
-                "pgk_engine_create: fp8 weights need 128-multiple dims");
+                "pgk_engine_create: %s weights need hidden_size and intermediate_size multiples of 128 (got %d, %d)",
+                c.weight_format == 3 ? "NVF4" : "fp8", c.hidden_size, c.intermediate_size);
+    PGK_REQUIRE(c.weight_format >= 0 && c.weight_format <= 3, "pgk_engine_create: weight_format %d not in {0,1,2,3}", c.weight_format);
+    if (c.weight_format == 3) {
+        // NVF4: every linear needs its codes and scale bytes, 16-byte aligned rows (K/2 bytes each, K % 32 == 0 by the checks above)
+        for (int l = 0; l < c.num_layers; ++l) {
+            const pgk_layer_weights_t& L = layers[l];
+            const void* ptrs[8] = {L.w_qkv, L.s_qkv, L.w_o, L.s_o, L.w_gate_up, L.s_gate_up, L.w_down, L.s_down};
+            for (int i = 0; i < 8; ++i)
+                PGK_REQUIRE(ptrs[i], "pgk_engine_create: NVF4 layer %d is missing its %s %s", l, i % 2 ? "scales" : "codes",
+                            i < 2 ? "qkv" : i < 4 ? "o" : i < 6 ? "gate_up" : "down");
+            for (int i = 0; i < 8; i += 2)
+                PGK_REQUIRE(((uintptr_t)ptrs[i] & 15) == 0, "pgk_engine_create: NVF4 layer %d codes must be 16-byte aligned", l);
+        }
+    }
     PGK_REQUIRE(c.max_batch >= 1 && c.max_seq_len >= 1 && c.num_layers >= 1, "pgk_engine_create: bad sizes");
     Engine* e = new Engine();
     e->cfg = c;
@@ -2199,7 +2283,8 @@ pgk_status pgk_engine_create(const pgk_model_config_t* cfg, const void* embed, c
         while (rows2 < rpp2) rows2 *= 2;
         const char* emo = getenv("PGK_MERGED_OPROJ");
         e->merged_oproj = !(emo && atoi(emo) == 0) && (G == 1 || G == 2 || G == 4) && lpw >= 8 && lpw <= 64 && 256 % lpw == 0 &&
-                          rows2 % rpp2 == 0 && c.hidden_size % rows2 == 0 && (c.weight_format == 0 || (gd % 128 == 0 || 128 % gd == 0));
+                          rows2 % rpp2 == 0 && c.hidden_size % rows2 == 0 && (c.weight_format == 0 || (gd % 128 == 0 || 128 % gd == 0)) &&
+                          c.weight_format != 3;   // NVF4: the merge kernel + the o_proj GEMV
         e->moproj_rows = rows2;
     }
     const int B = c.max_batch, H = c.hidden_size, D = c.head_dim;
@@ -2236,7 +2321,8 @@ pgk_status pgk_engine_create(const pgk_model_config_t* cfg, const void* embed, c
         // fragments in registers) or an LDS image of K x 16 bf16 that fits (K <= 4096); Llama-3-8B's down_proj
         // (K = 14336) does neither, so such models decode batches in GEMV chunks of 8 / 4 / 2 / 1
         auto k_ok = [](int K) { return K % 128 == 0 && K <= 4096; };
-        e->batched_mfma = !(ev && atoi(ev) == 0) && k_ok(c.hidden_size) && k_ok(c.intermediate_size) && k_ok(c.num_heads * c.head_dim);
+        e->batched_mfma = !(ev && atoi(ev) == 0) && k_ok(c.hidden_size) && k_ok(c.intermediate_size) && k_ok(c.num_heads * c.head_dim) &&
+                          c.weight_format != 3;   // NVF4: no batched-MFMA form (yet) - batches run as GEMV chunks of <= 8
         // 17..64 sequences in one weight pass (batched_mt_kernel) need K = 128 S with S instantiated; otherwise chunks of 16
         auto k_tiled = [](int K) { const int s = K / 128; return K % 128 == 0 && (s == 2 || s == 4 || s == 8 || s == 16 || s == 24 || s == 32); };
         e->batched_max = (k_tiled(c.hidden_size) && k_tiled(c.intermediate_size) && k_tiled(c.num_heads * c.head_dim)) ? 64 : 16;
@@ -2245,6 +2331,10 @@ pgk_status pgk_engine_create(const pgk_model_config_t* cfg, const void* embed, c
     A((void**)&e->amax_val, (size_t)B * e->lm_cap * 4, &e->ws_bytes);
     A((void**)&e->amax_idx, (size_t)B * e->lm_cap * 4, &e->ws_bytes);
     A((void**)&e->clk_log, (size_t)e->log_cap * 16, &e->ws_bytes);
+    if (c.weight_format == 3) {
+        const size_t QDn = (size_t)c.num_heads * D, I = c.intermediate_size;
+        A((void**)&e->nv_deq, ((size_t)e->qkv_dim() * H + (size_t)H * QDn + 2 * I * H + (size_t)H * I) * 2, &e->ws_bytes);
+    }
     {
         // Second, fragment-major copy of the bf16 layer weights: what the short-prompt prefill streams (ops_pkgemm.hip).
         // Costs the layers' bytes again; skipped when that is more than a quarter of the device's free memory.
@@ -2376,7 +2466,9 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
     // dequantisation pass in front of the 256-tile kernel
     const bool pkd = !ws && c.weight_format == 1 && e->packed_have && engine_gemm_packed_ok(n, NQKV, H) && engine_gemm_packed_ok(n, H, QD) &&
                      engine_gemm_packed_ok(n, 2 * I, H) && engine_gemm_packed_ok(n, H, I);
-    const bool gsplit = !ws && (c.weight_format == 0 || pkd);
+    const bool nv4 = c.weight_format == 3;       // NVF4: each layer's linears dequantised to bf16 (e->nv_deq), then the bf16 engine's path
+    const bool w16 = c.weight_format == 0 || nv4; // the projections read bf16 row-major weights
+    const bool gsplit = !ws && (w16 || pkd);
     const int g_so = gsplit ? engine_gemm_pick_splits(n, H, QD) : 1, g_sd = gsplit ? engine_gemm_pick_splits(n, H, I) : 1;
     const bool use_slabs = ws || g_so > 1 || g_sd > 1;
     size_t slab_elems = (size_t)(s_o > s_d ? s_o : s_d) * n * H;
@@ -2402,7 +2494,7 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
         PGK_REQUIRE(h_tokens[i] >= 0 && h_tokens[i] < c.vocab_size, "pgk_engine_prefill: token %d out of range", h_tokens[i]);
     PGK_CHECK_HIP(hipMemcpyAsync(e->pf_tokens, h_tokens, (size_t)n * 4, hipMemcpyHostToDevice, st));
     PGK_CHECK_HIP(hipStreamSynchronize(st));  // h_tokens may be pageable: make the copy complete before returning control
-    const bool fp8 = c.weight_format != 0;
+    const bool fp8 = c.weight_format == 1 || c.weight_format == 2;
     const bool fp8act = c.weight_format == 2 && n > 128;   // fp8 x fp8 MFMA projections, activations quantised on the fly
     char* p = (char*)e->pf;
     float* h32 = (float*)p; p += (size_t)n * H * 4;
@@ -2428,7 +2520,7 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
     const bool fuse_sw16 = !fp8act && !ws && fuse_epi && engine_gemm_swiglu_ok(n, I, H, fp8 && !pkd);
     // per-head norm + RoPE + cache write in the QKV GEMM's epilogue (bf16 weights, head_dim 128, 128-tile kernel: tile column = head)
     const bool fuse_heads8 = fuse_q && D == 128 && gemm_fp8_qkv_heads_ok(n, NQKV, H);      // fp8 x fp8: x's codes are already in q8
-    const bool fuse_heads = fuse_heads8 || (!ws && !pk && fuse_epi && (c.weight_format == 0 || pkd) && D == 128 && engine_gemm_qkv_heads_ok(n, NQKV, H));
+    const bool fuse_heads = fuse_heads8 || (!ws && !pk && fuse_epi && (w16 || pkd) && D == 128 && engine_gemm_qkv_heads_ok(n, NQKV, H));
     auto proj_accum = [&](const bf16* x_in, const void* w, const void* sc, int N_, int K_, int splits, const bf16* wp = nullptr) -> pgk_status {
         if (fp8act) {
             if (x_in)
@@ -2474,7 +2566,21 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
     const int kv_len = start_pos + n;
     int ss_n = 0;    // partial sums per row in pk_ss (carried norms)
     for (int l = 0; l < c.num_layers; ++l) {
-        const auto& L = e->layers[l];
+        pgk_layer_weights_t Lq = e->layers[l];
+        if (nv4) {
+            // this layer's codes x scales -> bf16 [qkv | o | gate_up | down] in e->nv_deq (exact), read by the projections below
+            bf16* d = e->nv_deq;
+            const struct { const void* w; const void* s; int N, K; } m4[4] = {
+                {Lq.w_qkv, Lq.s_qkv, NQKV, H}, {Lq.w_o, Lq.s_o, H, QD}, {Lq.w_gate_up, Lq.s_gate_up, 2 * I, H}, {Lq.w_down, Lq.s_down, H, I}};
+            const void** dst[4] = {&Lq.w_qkv, &Lq.w_o, &Lq.w_gate_up, &Lq.w_down};
+            for (int i = 0; i < 4; ++i) {
+                if (pgk_status r = dequant_nvf4_nk((const uint8_t*)m4[i].w, (const uint8_t*)m4[i].s, d, m4[i].N, m4[i].K, st)) return r;
+                *dst[i] = d;
+                d += (size_t)m4[i].N * m4[i].K;
+            }
+            Lq.s_qkv = Lq.s_o = Lq.s_gate_up = Lq.s_down = nullptr;
+        }
+        const auto& L = Lq;
         bf16* kc = e->kcache + (size_t)l * e->kv_layer_elems() + (size_t)seq * c.num_kv_heads * c.max_seq_len * D;
         bf16* vc = e->vcache + (size_t)l * e->kv_layer_elems() + (size_t)seq * c.num_kv_heads * c.max_seq_len * D;
         // packed path with carried norms: layer 0 normalises with a launch; afterwards x holds bf16(h * gamma) and pk_ss the

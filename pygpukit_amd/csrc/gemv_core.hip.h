@@ -206,4 +206,107 @@ __device__ __forceinline__ void gemv_rows_fp8(const fp8e4m3* const (&wrow)[R], c
     }
 }
 
+// ---- NVF4 (w4a16): e2m1 codes, one scale byte per 32 k ------------------------------------------------------------
+// Engine layout NK: data [N, K/2] (byte j of a row holds k = 2j in its low nibble, 2j+1 in its high nibble) and
+// scale [N, K/32].  A lane's 16-byte load is 32 k of one row, so it carries exactly one scale byte.
+struct nvf4x2 { uint8_t b; };   // tag type of the engine's NVF4 weights (two codes per byte)
+template <> struct WTraits<nvf4x2> { static constexpr int NW = 32; };
+
+// exact decode of a scale byte: exponent field e -> 2^(e-7), mantissa m -> 1 + m/8 (always a normal fp32)
+__device__ __forceinline__ float nvf4_scale_value(uint32_t s) {
+    return __uint_as_float(((((s >> 3) & 15u) + 120u) << 23) | ((s & 7u) << 20));
+}
+
+// byte B of a dword: (k, k+1) at unit scale.  The conversion's scale operand acts as a power of two (an E8M0 MX scale),
+// so 1.0 leaves the e2m1 value as it is and the block's scale byte is applied once per 32 k by the caller.
+template <int B> __device__ __forceinline__ f32x2 nvf4_pair_f32(uint32_t w) { return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, B); }
+template <int B> __device__ __forceinline__ bf16x2_t nvf4_pair_bf16(uint32_t w) { return __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, B); }
+
+// Activation image in LDS for NVF4 (row m at xs + m * K): a lane owns 32 consecutive k, so reading them in place would
+// stride 64 B (bf16) / 128 B (fp32) across the lanes of a ds_read_b128 - 4- / 8-way bank conflicts on every read.  The
+// image is stored swizzled instead: k goes to group g = (k % 32) / G (G = 16 bytes of XT), and group g of every 32-k block
+// is contiguous, so group g of the wave's 64 blocks is 64 adjacent 16-byte pieces.
+template <class XT> __device__ __forceinline__ int nvf4_xpos(int k, int K) {
+    constexpr int G = 16 / (int)sizeof(XT), NG = 32 / G;
+    return ((k & 31) / G) * (K / NG) + (k >> 5) * G + (k & (G - 1));
+}
+
+// p[r][m] += sum over the 32 k of word block k0 of e2m1(raw[r]) * x[m][k]  (unit scale; e2m1 x bf16 products are exact
+// in fp32; x is the swizzled image of nvf4_xpos, row stride ldx = K).  bf16 activations: the codes widen to bf16 pairs and v_dot2c_f32_bf16 takes the packed LDS words as they
+// are - 2 products per instruction and no unpacking, what keeps M = 4 / 8 from going VALU-bound; fp32 activations
+// (M = 1 / 2): fp32 pairs and FMAs.
+template <class XT, int M, int R>
+__device__ __forceinline__ void nvf4_dot32(const uint4 (&raw)[R], const XT* xs, int ldx, int k0, float (&p)[R][M]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (std::is_same<XT, bf16>::value) {
+            uint4 xr[M];
+#pragma unroll
+            for (int m = 0; m < M; ++m) xr[m] = *reinterpret_cast<const uint4*>(xs + (size_t)m * ldx + i * (ldx >> 2) + (k0 >> 5) * 8);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const uint32_t w = i == 0 ? raw[r].x : i == 1 ? raw[r].y : i == 2 ? raw[r].z : raw[r].w;
+                const bf16x2_t b0 = nvf4_pair_bf16<0>(w), b1 = nvf4_pair_bf16<1>(w), b2 = nvf4_pair_bf16<2>(w), b3 = nvf4_pair_bf16<3>(w);
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    float t = p[r][m];
+                    t = __builtin_amdgcn_fdot2_f32_bf16(b0, __builtin_bit_cast(bf16x2_t, xr[m].x), t, false);
+                    t = __builtin_amdgcn_fdot2_f32_bf16(b1, __builtin_bit_cast(bf16x2_t, xr[m].y), t, false);
+                    t = __builtin_amdgcn_fdot2_f32_bf16(b2, __builtin_bit_cast(bf16x2_t, xr[m].z), t, false);
+                    t = __builtin_amdgcn_fdot2_f32_bf16(b3, __builtin_bit_cast(bf16x2_t, xr[m].w), t, false);
+                    p[r][m] = t;
+                }
+            }
+        } else {
+            float xf[M][8];
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                float lo[4], hi[4];
+                XLoad<XT, 4>::load(xs + (size_t)m * ldx + (2 * i) * (ldx >> 3) + (k0 >> 5) * 4, lo);
+                XLoad<XT, 4>::load(xs + (size_t)m * ldx + (2 * i + 1) * (ldx >> 3) + (k0 >> 5) * 4, hi);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { xf[m][j] = lo[j]; xf[m][4 + j] = hi[j]; }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const uint32_t w = i == 0 ? raw[r].x : i == 1 ? raw[r].y : i == 2 ? raw[r].z : raw[r].w;
+                const f32x2 f0 = nvf4_pair_f32<0>(w), f1 = nvf4_pair_f32<1>(w), f2 = nvf4_pair_f32<2>(w), f3 = nvf4_pair_f32<3>(w);
+                const float wf[8] = {f0.x, f0.y, f1.x, f1.y, f2.x, f2.y, f3.x, f3.y};
+#pragma unroll
+                for (int m = 0; m < M; ++m)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) p[r][m] = fmaf(wf[j], xf[m][j], p[r][m]);
+            }
+        }
+    }
+}
+
+// NVF4 variant of gemv_rows: wrow[r] = row r's data bytes, srow[r] = its scale bytes; K % 32 == 0.  Each 32-k partial is
+// summed at unit scale, then multiplied by its scale byte's value once.
+template <class XT, int M, int R>
+__device__ __forceinline__ void gemv_rows_nvf4(const uint8_t* const (&wrow)[R], const uint8_t* const (&srow)[R], const XT* xs, int ldx,
+                                               int K, int lane, float (&acc)[R][M]) {
+    constexpr int NW = 32, UNROLL = M <= 2 ? 2 : 1;   // 4 / 8 activation rows: one trip at a time (registers)
+#pragma unroll UNROLL
+    for (int k0 = lane * NW; k0 < K; k0 += 64 * NW) {
+        uint4 raw[R];
+        float sc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            raw[r] = load_nt16(wrow[r] + (k0 >> 1));
+            sc[r] = nvf4_scale_value(srow[r][k0 >> 5]);
+        }
+        float p[R][M];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int m = 0; m < M; ++m) p[r][m] = 0.f;
+        nvf4_dot32<XT, M, R>(raw, xs, ldx, k0, p);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int m = 0; m < M; ++m) acc[r][m] = fmaf(sc[r], p[r][m], acc[r][m]);
+    }
+}
+
 }  // namespace pgk

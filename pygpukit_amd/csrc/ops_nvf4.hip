@@ -27,10 +27,7 @@ typedef int i32x8_n __attribute__((ext_vector_type(8)));
 typedef float f32x4_n __attribute__((ext_vector_type(4)));
 typedef float f32x2_n __attribute__((ext_vector_type(2)));
 
-// exact decode of a scale byte: exponent field e -> 2^(e-7), mantissa m -> 1 + m/8 (always a normal fp32)
-__device__ __forceinline__ float nvf4_scale_value(uint32_t s) {
-    return __uint_as_float(((((s >> 3) & 15u) + 120u) << 23) | ((s & 7u) << 20));
-}
+// nvf4_scale_value (the exact decode of a scale byte) lives in gemv_core.hip.h, shared with the engine's decode kernels.
 
 // ---- weight quantiser (nvf4_kernels.cu:239-320) ---------------------------------------------------------------
 
@@ -50,18 +47,8 @@ __device__ __forceinline__ uint32_t nvf4_code_scaled(float v) {
     return sign | c;
 }
 
-__global__ __launch_bounds__(256) void quantize_nvf4_kernel(const bf16* x, uint8_t* data, uint8_t* scale, int K, int N) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    const int sb = blockIdx.y;
-    if (n >= N) return;
-    const int k0 = sb * 32, len = min(32, K - k0);   // K is even, so len is too
-    float v[32];
-    float max_abs = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-        v[i] = i < len ? to_f(x[(size_t)(k0 + i) * N + n]) : 0.f;
-        max_abs = fmaxf(max_abs, fabsf(v[i]));   // fmaxf drops NaN
-    }
+// the scale byte of a block whose largest magnitude is max_abs (NaN already dropped)
+__device__ __forceinline__ uint32_t nvf4_scale_byte(float max_abs) {
     // correctly rounded division (no fast-math in this build): scale = max_abs / 6
     const float s = max_abs > 1e-8f ? max_abs / 6.0f : 1.0f;
     int e = 0;
@@ -74,7 +61,22 @@ __global__ __launch_bounds__(256) void quantize_nvf4_kernel(const bf16* x, uint8
     // clamp in float before the conversion: norm = inf (an inf in the block) must give 7, and (int)inf is undefined
     const int mant = (int)fminf(fmaxf(rintf((norm - 1.0f) * 8.0f), 0.f), 7.f);
     const int eb = min(max(e + 7, 0), 15);
-    const uint32_t sbyte = ((uint32_t)eb << 3) | (uint32_t)mant;
+    return ((uint32_t)eb << 3) | (uint32_t)mant;
+}
+
+__global__ __launch_bounds__(256) void quantize_nvf4_kernel(const bf16* x, uint8_t* data, uint8_t* scale, int K, int N) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int sb = blockIdx.y;
+    if (n >= N) return;
+    const int k0 = sb * 32, len = min(32, K - k0);   // K is even, so len is too
+    float v[32];
+    float max_abs = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        v[i] = i < len ? to_f(x[(size_t)(k0 + i) * N + n]) : 0.f;
+        max_abs = fmaxf(max_abs, fabsf(v[i]));   // fmaxf drops NaN
+    }
+    const uint32_t sbyte = nvf4_scale_byte(max_abs);
     scale[(size_t)sb * N + n] = (uint8_t)sbyte;
     const float inv = 1.0f / nvf4_scale_value(sbyte);
 #pragma unroll
@@ -82,6 +84,65 @@ __global__ __launch_bounds__(256) void quantize_nvf4_kernel(const bf16* x, uint8
         if (i < len)
             data[(size_t)((k0 + i) >> 1) * N + n] = (uint8_t)(nvf4_code_scaled(v[i] * inv) | (nvf4_code_scaled(v[i + 1] * inv) << 4));
     }
+}
+
+// ---- engine layout NK (ours): data [N, K/2], scale [N, K/32], K % 32 == 0 ---------------------------------------------
+// Block i (row i / (K/32), k-block i % (K/32)) is data bytes [16 i, 16 i + 16), scale byte i and bf16 elements
+// [32 i, 32 i + 32) of the row-major [N, K] matrix: the three arrays are indexed by the same flat block number.
+
+// The quantiser: the bytes of quantize_nvf4_kernel on x^T, transposed (same block arithmetic, one thread per block).
+__global__ __launch_bounds__(256) void quantize_nvf4_nk_kernel(const bf16* x, uint8_t* data, uint8_t* scale, long long nblk) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nblk) return;
+    float v[32];
+    float max_abs = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float t[8];
+        WTraits<bf16>::decode(*reinterpret_cast<const uint4*>(x + i * 32 + 8 * q), t);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            v[8 * q + j] = t[j];
+            max_abs = fmaxf(max_abs, fabsf(t[j]));   // fmaxf drops NaN
+        }
+    }
+    const uint32_t sbyte = nvf4_scale_byte(max_abs);
+    scale[i] = (uint8_t)sbyte;
+    const float inv = 1.0f / nvf4_scale_value(sbyte);
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 32; ++j) w[j >> 3] |= nvf4_code_scaled(v[j] * inv) << (4 * (j & 7));
+    *reinterpret_cast<uint4*>(data + i * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// bf16 [N, K] = code x scale (exact: an e2m1 value has 2 significant bits, a scale byte 4) - the engine's prefill
+// dequantises one layer at a time with this, right before that layer's projections.
+__global__ __launch_bounds__(256) void dequant_nvf4_nk_kernel(const uint8_t* data, const uint8_t* scale, bf16* out, long long nblk) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nblk) return;
+    const uint4 d = load_nt16(data + i * 16);
+    const float s = nvf4_scale_value(scale[i]);
+    const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+    uint32_t o[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const f32x2 f0 = nvf4_pair_f32<0>(w[q]), f1 = nvf4_pair_f32<1>(w[q]), f2 = nvf4_pair_f32<2>(w[q]), f3 = nvf4_pair_f32<3>(w[q]);
+        o[4 * q + 0] = pack_bf16x2(f0.x * s, f0.y * s);
+        o[4 * q + 1] = pack_bf16x2(f1.x * s, f1.y * s);
+        o[4 * q + 2] = pack_bf16x2(f2.x * s, f2.y * s);
+        o[4 * q + 3] = pack_bf16x2(f3.x * s, f3.y * s);
+    }
+    uint4* dst = reinterpret_cast<uint4*>(out + i * 32);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+}
+
+pgk_status dequant_nvf4_nk(const uint8_t* data, const uint8_t* scale, bf16* out, int n, int k, hipStream_t st) {
+    PGK_REQUIRE(data && scale && out && n >= 1 && k >= 32 && k % 32 == 0, "dequant_nvf4_nk: bad arguments (n=%d k=%d)", n, k);
+    const long long nblk = (long long)n * (k / 32);
+    dequant_nvf4_nk_kernel<<<(unsigned)ceil_div(nblk, 256LL), 256, 0, st>>>(data, scale, out, nblk);
+    PGK_CHECK_HIP(hipGetLastError());
+    return PGK_OK;
 }
 
 // ---- weight-only GEMV (nvf4_kernels.cu:19-235) ------------------------------------------------------------------
@@ -350,6 +411,16 @@ pgk_status pgk_quantize_nvf4(const void* x_kn, uint8_t* data, uint8_t* scale, in
     PGK_REQUIRE(x_kn && data && scale, "pgk_quantize_nvf4: null argument");
     PGK_REQUIRE(k >= 2 && k % 2 == 0 && n >= 1, "pgk_quantize_nvf4: k=%d must be positive and even (n=%d)", k, n);
     quantize_nvf4_kernel<<<dim3(ceil_div(n, 256), ceil_div(k, 32)), 256, 0, resolve_stream(s)>>>((const bf16*)x_kn, data, scale, k, n);
+    PGK_CHECK_HIP(hipGetLastError());
+    return PGK_OK;
+}
+
+pgk_status pgk_quantize_nvf4_nk(const void* x_nk, uint8_t* data, uint8_t* scale, int n, int k, pgk_stream s) {
+    PGK_REQUIRE(x_nk && data && scale, "pgk_quantize_nvf4_nk: null argument");
+    PGK_REQUIRE(n >= 1 && k >= 32 && k % 32 == 0, "pgk_quantize_nvf4_nk: k=%d must be a positive multiple of 32 (n=%d)", k, n);
+    PGK_REQUIRE(((uintptr_t)x_nk & 15) == 0 && ((uintptr_t)data & 15) == 0, "pgk_quantize_nvf4_nk: input and data must be 16-byte aligned");
+    const long long nblk = (long long)n * (k / 32);
+    quantize_nvf4_nk_kernel<<<(unsigned)ceil_div(nblk, 256LL), 256, 0, resolve_stream(s)>>>((const bf16*)x_nk, data, scale, nblk);
     PGK_CHECK_HIP(hipGetLastError());
     return PGK_OK;
 }

@@ -45,8 +45,9 @@ class DecodeBatch(DecodeStrategy):
         return self.step_batch(token_ids, start_position, context_len, None)
 
     # ---- independent sequences on the native engine ----
-    def init_graph(self, max_seq_len: int = 512) -> None:
-        self._engine = self.model.build_engine(max_seq_len=max_seq_len, max_batch=self.batch_size)
+    def init_graph(self, max_seq_len: int = 512, *, weight_format: str | None = None) -> None:
+        """weight_format: passed to model.build_engine ("nvf4": 4-bit linears quantised on the device)."""
+        self._engine = self.model.build_engine(max_seq_len=max_seq_len, max_batch=self.batch_size, weight_format=weight_format)
         self._engine.capture(self.batch_size)
         self._graph_ready = True
 

@@ -25,8 +25,9 @@ class DecodeM1Graph(DecodeStrategy):
         raise NotImplementedError("DecodeM1Graph does not support non-graph decode. Use DecodeM1, or call "
                                   "init_graph() and step_graph().")
 
-    def init_graph(self, max_seq_len: int = 512) -> None:
-        self._engine = self.model.build_engine(max_seq_len=max_seq_len, max_batch=1)
+    def init_graph(self, max_seq_len: int = 512, *, weight_format: str | None = None) -> None:
+        """weight_format: passed to model.build_engine ("nvf4": 4-bit linears quantised on the device)."""
+        self._engine = self.model.build_engine(max_seq_len=max_seq_len, max_batch=1, weight_format=weight_format)
         self._engine.capture(1)
         self._graph_max_seq_len = max_seq_len
         self._decode_buffers = None

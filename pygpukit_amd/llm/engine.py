@@ -13,7 +13,39 @@ import numpy as np
 
 from pygpukit_amd import _hip
 from pygpukit_amd.core.array import GPUArray
-from pygpukit_amd.core.dtypes import bfloat16, float32
+from pygpukit_amd.core.dtypes import bfloat16, float32, uint8
+
+WEIGHT_FORMATS = {"bf16": 0, "fp8": 1, "fp8a8": 2, "nvf4": 3}
+
+_LINEARS = ("w_qkv", "w_o", "w_gate_up", "w_down")
+
+
+def linear_shapes(config: dict) -> dict[str, tuple[int, int]]:
+    """[N, K] of each fused layer linear of an engine with this config."""
+    H, D, I = config["hidden_size"], config["head_dim"], config["intermediate_size"]
+    Hq, Hkv = config["num_heads"], config["num_kv_heads"]
+    return {"w_qkv": ((Hq + 2 * Hkv) * D, H), "w_o": (H, Hq * D), "w_gate_up": (2 * I, H), "w_down": (H, I)}
+
+
+def check_nvf4_layers(config: dict, layers: list[dict]) -> None:
+    """Host-side checks of NVF4 (weight_format "nvf4") layer dicts, before anything reaches the device: each linear
+    w_* [N, K] is uint8 codes [N, K/2] with uint8 scale bytes s_* [N, K/32] (quantize_bf16_to_nvf4_nk's NK layout),
+    and hidden_size / intermediate_size are multiples of 128.  Only .dtype and .shape of the arrays are read."""
+    H, I = config["hidden_size"], config["intermediate_size"]
+    if H % 128 or I % 128:
+        raise ValueError(f"Engine(weight_format='nvf4'): hidden_size {H} and intermediate_size {I} must be multiples of 128")
+    if len(layers) != config["num_layers"]:
+        raise ValueError(f"Engine: {len(layers)} layer dicts for num_layers={config['num_layers']}")
+    for i, lw in enumerate(layers):
+        for name, (N, K) in linear_shapes(config).items():
+            sname = "s" + name[1:]
+            w, s = lw.get(name), lw.get(sname)
+            if w is None or s is None:
+                raise ValueError(f"Engine(weight_format='nvf4'): layer {i} needs both {name} and {sname}")
+            if w.dtype != uint8 or tuple(w.shape) != (N, K // 2):
+                raise ValueError(f"Engine(weight_format='nvf4'): layer {i} {name} must be uint8 [{N}, {K // 2}], got {w.dtype} {tuple(w.shape)}")
+            if s.dtype != uint8 or tuple(s.shape) != (N, K // 32):
+                raise ValueError(f"Engine(weight_format='nvf4'): layer {i} {sname} must be uint8 [{N}, {K // 32}], got {s.dtype} {tuple(s.shape)}")
 
 
 class Engine:
@@ -21,7 +53,12 @@ class Engine:
                  *, max_seq_len: int = 512, max_batch: int = 1, weight_format: str = "bf16", use_qk_norm: bool = True):
         """config: vocab_size, hidden_size, num_layers, num_heads, num_kv_heads, head_dim, intermediate_size,
         norm_eps, rope_theta.  layers[i]: GPUArrays attn_norm, w_qkv [(Hq+2Hkv)D, H], q_norm, k_norm, w_o,
-        mlp_norm, w_gate_up [2I, H], w_down (+ s_qkv, s_o, s_gate_up, s_down for fp8)."""
+        mlp_norm, w_gate_up [2I, H], w_down (+ s_qkv, s_o, s_gate_up, s_down for fp8).  weight_format "nvf4": each w_* is
+        uint8 codes [N, K/2] and each s_* uint8 scale bytes [N, K/32] (ops.quantize_bf16_to_nvf4_nk), w4a16."""
+        if weight_format not in WEIGHT_FORMATS:
+            raise ValueError(f"Engine: weight_format {weight_format!r} not in {sorted(WEIGHT_FORMATS)}")
+        if weight_format == "nvf4":
+            check_nvf4_layers(config, layers)
         _hip.require_device()
         self.config = dict(config)
         self.max_seq_len, self.max_batch = max_seq_len, max_batch
@@ -29,7 +66,7 @@ class Engine:
         self._keep = [embed, final_norm, lm_head, layers]  # keep the weights alive
         mc = _hip.ModelConfig(config["vocab_size"], config["hidden_size"], config["num_layers"], config["num_heads"],
                               config["num_kv_heads"], config["head_dim"], config["intermediate_size"], max_seq_len, max_batch,
-                              float(config["norm_eps"]), float(config["rope_theta"]), {"bf16": 0, "fp8": 1, "fp8a8": 2}[weight_format],
+                              float(config["norm_eps"]), float(config["rope_theta"]), WEIGHT_FORMATS[weight_format],
                               1 if use_qk_norm else 0)
         for a in (embed, final_norm):
             if a.dtype != bfloat16:

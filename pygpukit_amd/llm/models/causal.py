@@ -187,9 +187,11 @@ class CausalTransformerModel:
             b.attn._v_cache.copy_from_numpy(v)
 
     # ------------------------------------------------------------------ native engine
-    def build_engine(self, max_seq_len: int = 512, max_batch: int = 1):
+    def build_engine(self, max_seq_len: int = 512, max_batch: int = 1, *, weight_format: str | None = None):
         """Hand this model's weights (zero copy) to the native decode/prefill engine.  Requires bf16 or fp8
-        linears, RMSNorm, SwiGLU, RoPE and no biases (Llama / Qwen3 families)."""
+        linears, RMSNorm, SwiGLU, RoPE and no biases (Llama / Qwen3 families).  weight_format="nvf4": the fused
+        qkv / o / gate_up / down weights of a bf16 model are quantised on the device to NVF4 (w4a16) arrays that the
+        engine keeps alive; embedding, norms and lm_head stay bf16.  None: the model's own format."""
         from pygpukit_amd.llm.engine import Engine
         from pygpukit_amd.llm.layers.linear import LinearFP8
 
@@ -200,6 +202,13 @@ class CausalTransformerModel:
             raise NotImplementedError("the native engine covers RMSNorm + SwiGLU + RoPE models (Llama / Qwen families)")
         if self.embed_tokens.dtype != bfloat16:
             raise NotImplementedError("the native engine needs bfloat16 weights")
+        if weight_format not in (None, "bf16", "nvf4"):
+            raise ValueError(f"build_engine: weight_format {weight_format!r} not in (None, 'bf16', 'nvf4')")
+        if weight_format == "nvf4":
+            H, I = c.hidden_size, self.blocks[0].mlp.intermediate_size
+            if H % 128 or I % 128:
+                raise ValueError(f"build_engine(weight_format='nvf4'): hidden_size {H} and intermediate_size {I} must be "
+                                 "multiples of 128")
         layers, fp8 = [], False
         for b in self.blocks:
             a, m = b.attn, b.mlp
@@ -212,12 +221,20 @@ class CausalTransformerModel:
                                q_norm=a.q_norm.weight if a.q_norm else None, k_norm=a.k_norm.weight if a.k_norm else None,
                                w_o=a.o_proj.weight, mlp_norm=b.mlp_norm.weight, w_gate_up=m.gate_up_proj.weight,
                                w_down=m.down_proj.weight))
+        if weight_format == "nvf4":
+            from pygpukit_amd.ops.matmul.nvf4 import quantize_nvf4_nk
+
+            for lw in layers:
+                for name in ("w_qkv", "w_o", "w_gate_up", "w_down"):
+                    if lw[name].dtype != bfloat16:
+                        raise NotImplementedError(f"build_engine(weight_format='nvf4') quantises bfloat16 linears, got {lw[name].dtype}")
+                    lw[name], lw["s" + name[1:]] = quantize_nvf4_nk(lw[name])
         eps = self.blocks[0].attn_norm.eps
         cfg = dict(vocab_size=self.embed_tokens.shape[0], hidden_size=c.hidden_size, num_layers=len(self.blocks),
                    num_heads=c.num_heads, num_kv_heads=c.num_kv_heads, head_dim=c.head_dim,
                    intermediate_size=self.blocks[0].mlp.intermediate_size, norm_eps=eps, rope_theta=c.rope_theta)
         return Engine(cfg, self.embed_tokens, layers, self.final_norm.weight, self._lm_head, max_seq_len=max_seq_len,
-                      max_batch=max_batch, weight_format="fp8" if fp8 else "bf16",
+                      max_batch=max_batch, weight_format=weight_format or ("fp8" if fp8 else "bf16"),
                       use_qk_norm=self.blocks[0].attn.q_norm is not None)
 
 

@@ -22,6 +22,7 @@ def _bf16(x: np.ndarray) -> GPUArray:
 def engine_layer_arrays(lw: dict, weight_format: str = "bf16") -> dict:
     """One layer of the oracle's weight dict (q,k,v,o,gate,up,down,*_norm as fp32 ndarrays) -> engine layout."""
     from pygpukit_amd.ops.matmul.fp8 import quantize_fp8_blocks
+    from pygpukit_amd.ops.matmul.nvf4 import quantize_nvf4_nk
 
     out = {"attn_norm": _bf16(lw["attn_norm"]), "mlp_norm": _bf16(lw["mlp_norm"]),
            "q_norm": _bf16(lw["q_norm"]) if "q_norm" in lw else None, "k_norm": _bf16(lw["k_norm"]) if "k_norm" in lw else None}
@@ -32,6 +33,9 @@ def engine_layer_arrays(lw: dict, weight_format: str = "bf16") -> dict:
             # block-quantised on the device (pgk_quantize_fp8_blocks: value-identical to the oracle's host quantiser,
             # tests/test_gpu_ops.py::test_quantize_fp8_blocks_matches_oracle) - seconds instead of minutes at 0.6B+
             out[name], out["s" + name[1:]] = quantize_fp8_blocks(_bf16(m))
+        elif weight_format == "nvf4":
+            # the fused matrix, quantised on the device into the engine's NK layout (codes [N, K/2], scales [N, K/32])
+            out[name], out["s" + name[1:]] = quantize_nvf4_nk(_bf16(m))
         else:
             out[name] = _bf16(m)
     return out

@@ -13,7 +13,8 @@ from pygpukit_amd.ops.matmul import (batched_matmul, gemm_w8a16_init_lut, gemv_b
                                     grouped_gemm_fp8_bf16_sm120, grouped_gemm_init_lut, nvf4_get_sizes, gemv_nvf4_get_sizes,
                                     quantize_bf16_to_nvf4, matmul_nvf4_bf16_sm120, gemm_nvf4_bf16_sm120, gemv_nvf4_bf16,
                                     gemv_nvf4_bf16_sm120, nvf4_bf16_sm120_available, gemm_nvf4_bf16_sm120_available,
-                                    gemv_nvf4_available, gemv_nvf4_bf16_sm120_available)
+                                    gemv_nvf4_available, gemv_nvf4_bf16_sm120_available, nvf4_nk_get_sizes,
+                                    quantize_bf16_to_nvf4_nk, quantize_nvf4_nk)
 from pygpukit_amd.ops.moe import (moe_compute_permutation, moe_expand_expert_offsets, moe_gather, moe_scatter, moe_softmax_topk,
                                   moe_topk_softmax, moe_topk_with_indices)
 from pygpukit_amd.ops.nn import (bias_add_inplace, geglu, gelu, glu_packed, layernorm, relu2, rmsnorm, rmsnorm_residual, rope_inplace,

@@ -29,6 +29,12 @@ def nvf4_get_sizes(K: int, N: int) -> tuple[int, int]:
 gemv_nvf4_get_sizes = nvf4_get_sizes
 
 
+def nvf4_nk_get_sizes(N: int, K: int) -> tuple[int, int]:
+    """(data_size, scale_size) in bytes of NVF4 weights for an [N, K] matrix in the engine's NK layout: data [N, K/2],
+    scale [N, K/32] (K % 32 == 0).  The layout is this project's (the reference has only [K/2, N] / [K/32, N])."""
+    return N * (K // 2), N * (K // 32)
+
+
 def nvf4_bf16_sm120_available() -> bool:
     """The FP4 MFMA GEMM runs on every gfx950 this backend targets (as fp8_available)."""
     return True
@@ -69,6 +75,38 @@ def quantize_bf16_to_nvf4(input: GPUArray, out_data: GPUArray, out_scale: GPUArr
     if K == 0 or N == 0:
         return
     call("pgk_quantize_nvf4", input._p, out_data._p, out_scale._p, K, N, None)
+
+
+def quantize_bf16_to_nvf4_nk(input: GPUArray, out_data: GPUArray, out_scale: GPUArray) -> None:
+    """Quantise bf16 weights W [N, K] (PyTorch [out, in]) into the engine's NK layout: data uint8 [N, K/2] (byte j of a
+    row holds k = 2j in its low nibble, 2j+1 in its high nibble) and scale uint8 [N, K/32].  The bytes are the transpose
+    of quantize_bf16_to_nvf4(W.T)'s, the reference's arithmetic included.  K must be a positive multiple of 32.
+    This op is this project's: the reference has no NK layout."""
+    if input.ndim != 2:
+        raise ValueError(f"quantize_bf16_to_nvf4_nk requires 2D input, got {input.ndim}D")
+    if input.dtype != bfloat16:
+        raise ValueError(f"quantize_bf16_to_nvf4_nk requires bfloat16 input, got {input.dtype}")
+    N, K = input.shape
+    if K % 32 or K == 0:
+        raise ValueError(f"quantize_bf16_to_nvf4_nk: K={K} must be a positive multiple of 32")
+    if out_data.dtype != uint8 or out_scale.dtype != uint8:
+        raise ValueError(f"quantize_bf16_to_nvf4_nk: out_data / out_scale must be uint8, got {out_data.dtype} / {out_scale.dtype}")
+    expected_data_size, expected_scale_size = nvf4_nk_get_sizes(N, K)
+    if _flat_size(out_data) < expected_data_size:
+        raise ValueError(f"out_data buffer too small: {_flat_size(out_data)} < {expected_data_size}")
+    if _flat_size(out_scale) < expected_scale_size:
+        raise ValueError(f"out_scale buffer too small: {_flat_size(out_scale)} < {expected_scale_size}")
+    if N == 0:
+        return
+    call("pgk_quantize_nvf4_nk", input._p, out_data._p, out_scale._p, N, K, None)
+
+
+def quantize_nvf4_nk(w: GPUArray) -> tuple[GPUArray, GPUArray]:
+    """W bf16 [N, K] -> freshly allocated (data uint8 [N, K/2], scale uint8 [N, K/32]) by quantize_bf16_to_nvf4_nk."""
+    N, K = w.shape
+    data, scale = GPUArray((N, K // 2), uint8), GPUArray((N, K // 32), uint8)
+    quantize_bf16_to_nvf4_nk(w, data, scale)
+    return data, scale
 
 
 def gemv_nvf4_bf16(a: GPUArray, b_data: GPUArray, b_scale: GPUArray, *, out: GPUArray | None = None,
@@ -138,6 +176,7 @@ def matmul_nvf4_bf16_sm120(a: GPUArray, b: GPUArray, *, out: GPUArray | None = N
 
 gemm_nvf4_bf16_sm120 = matmul_nvf4_bf16_sm120
 
-__all__ = ["nvf4_get_sizes", "gemv_nvf4_get_sizes", "quantize_bf16_to_nvf4", "matmul_nvf4_bf16_sm120", "gemm_nvf4_bf16_sm120",
+__all__ = ["nvf4_get_sizes", "gemv_nvf4_get_sizes", "quantize_bf16_to_nvf4", "nvf4_nk_get_sizes", "quantize_bf16_to_nvf4_nk",
+           "quantize_nvf4_nk", "matmul_nvf4_bf16_sm120", "gemm_nvf4_bf16_sm120",
            "gemv_nvf4_bf16", "gemv_nvf4_bf16_sm120", "nvf4_bf16_sm120_available", "gemm_nvf4_bf16_sm120_available",
            "gemv_nvf4_available", "gemv_nvf4_bf16_sm120_available"]
