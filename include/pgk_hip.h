@@ -72,6 +72,9 @@ typedef struct {
     int l2_bytes;
 } pgk_device_props_t;
 pgk_status pgk_device_props(int dev, pgk_device_props_t* out);
+/* The current device's gfx target as a number: the decimal digits after "gfx" in its architecture name (950 on
+ * MI355X).  Stands where the reference reports an SM version. */
+pgk_status pgk_device_arch(int* gfx);
 pgk_status pgk_mem_info(size_t* free_bytes, size_t* total_bytes);
 
 /* ---------------------------------------------------------------------- memory ------ */
@@ -381,6 +384,22 @@ pgk_status pgk_sdpa_causal(const void* q, const void* k, const void* v, void* ou
                            int kv_len, int d, float scale, int64_t q_stride_h, int64_t q_stride_s,
                            int64_t kv_stride_h, int64_t kv_stride_s, int64_t o_stride_h, int64_t o_stride_s,
                            pgk_dtype dt, pgk_stream s);
+/* sdpa_causal_fp8 (src/pygpukit/ops/nn/attention.py:238-347; flash_attention_3_fp8_sm120.cuh): the same op with the
+ * first product in fp8.  Q (per query head) and K (per kv head) are quantised to e4m3 with one power-of-two scale
+ * per head (pgk_quantize_fp8_per_head), s = scale * 2^(eq+ek) * sum_d q8 * k8 in fp32, softmax in fp32, P.V with
+ * V unquantised in bf16, bf16 out.  Arguments as pgk_sdpa_causal; dt must be PGK_BF16 and d 128 (anything else is
+ * PGK_ERR_INVALID with a message); pointers 16-byte aligned, strides multiples of 8 elements.  Workspaces come
+ * from the pool (stream-ordered). */
+pgk_status pgk_sdpa_causal_fp8(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len,
+                               int kv_len, int d, float scale, int64_t q_stride_h, int64_t q_stride_s,
+                               int64_t kv_stride_h, int64_t kv_stride_s, int64_t o_stride_h, int64_t o_stride_s,
+                               pgk_dtype dt, pgk_stream s);
+/* quantize_to_fp8_e4m3_per_head_kernel (flash_attention_3_fp8_sm120.cuh:475-547): x bf16 [heads, rows, 128] with
+ * (head, row) strides in elements -> codes u8 [heads, rows, 128] (contiguous) and one UE8M0 byte per head.
+ * a = max|x_h|; e = 0 when a == 0, else the smallest integer with 448 * 2^e >= a, clamped to [-127, 127];
+ * scale byte = e + 127; code = RNE satfinite e4m3 of x * 2^-e (an exact multiply: bit-reproducible). */
+pgk_status pgk_quantize_fp8_per_head(const void* x, uint8_t* codes, uint8_t* scale_bytes, int heads, int rows, int d,
+                                     int64_t stride_h, int64_t stride_s, pgk_dtype dt, pgk_stream s);
 /* ops.cuh:294-300 sdpa_causal_fixed_cache / _ptr: Q[Hq,q_len,D] over the first context_len rows of
  * cache[Hc,max_seq,D].  ctx_buf (device int32) overrides h_context_len when non-NULL.  q_len == 1
  * uses split-KV flash-decoding (replaces native/ops/nn/flash_decoding.cuh:75-377, fp16-only there);

@@ -139,6 +139,17 @@ pgk_status pgk_device_set(int dev) { PGK_CHECK_HIP(hipSetDevice(dev)); return PG
 pgk_status pgk_device_get(int* dev) { PGK_REQUIRE(dev, "null"); PGK_CHECK_HIP(hipGetDevice(dev)); return PGK_OK; }
 pgk_status pgk_device_sync(void) { PGK_CHECK_HIP(hipDeviceSynchronize()); return PGK_OK; }
 
+pgk_status pgk_device_arch(int* gfx) {
+    PGK_REQUIRE(gfx, "pgk_device_arch: null output");
+    int dev = 0;
+    hipDeviceProp_t p;
+    PGK_CHECK_HIP(hipGetDevice(&dev));
+    PGK_CHECK_HIP(hipGetDeviceProperties(&p, dev));
+    PGK_REQUIRE(strncmp(p.gcnArchName, "gfx", 3) == 0, "pgk_device_arch: unexpected architecture name '%s'", p.gcnArchName);
+    *gfx = (int)strtol(p.gcnArchName + 3, nullptr, 10);
+    return PGK_OK;
+}
+
 pgk_status pgk_device_props(int dev, pgk_device_props_t* out) {
     PGK_REQUIRE(out, "pgk_device_props: null output");
     hipDeviceProp_t p;
