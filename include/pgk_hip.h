@@ -400,6 +400,26 @@ pgk_status pgk_sdpa_causal_fp8(const void* q, const void* k, const void* v, void
  * scale byte = e + 127; code = RNE satfinite e4m3 of x * 2^-e (an exact multiply: bit-reproducible). */
 pgk_status pgk_quantize_fp8_per_head(const void* x, uint8_t* codes, uint8_t* scale_bytes, int heads, int rows, int d,
                                      int64_t stride_h, int64_t stride_s, pgk_dtype dt, pgk_stream s);
+/* ---- Llama-4 attention (src/pygpukit/ops/nn/llama4.py; native/ops/nn/llama4_kernels.cuh) ----
+ * t(pos) = log1pf(floorf((float)(pos + 1) / floor_scale)) * attn_scale + 1, every step rounded to fp32 in that order
+ * (log1pf correctly rounded, no FMA contraction).  `pos_dt` is the element type of `positions`: PGK_I64 (the
+ * reference's) or PGK_I32.
+ * l2norm: out = in * rsqrt(mean(in^2) + eps) over the last dimension, no gamma; f32 / f16 / bf16, fp32 sums, any
+ * features >= 1; in == out allowed. */
+pgk_status pgk_l2norm(const void* in, void* out, int rows, int features, float eps, pgk_dtype dt, pgk_stream s);
+/* irope_scale_q: out[s][h][:] = q[s][h][:] * t(positions[s]); Q [seq_len, n_heads, head_dim] f16 / bf16 (fp32 multiply,
+ * one RNE rounding). */
+pgk_status pgk_irope_scale_q(const void* q, const void* positions, void* out, int seq_len, int n_heads, int head_dim,
+                             float attn_scale, float floor_scale, pgk_dtype pos_dt, pgk_dtype dt, pgk_stream s);
+/* sdpa_irope: softmax(Q.K^T * t(positions[i]) / sqrt(d) + mask) . V; query row i sees kv j exactly when
+ * j <= i + causal_offset and j < kv_len (kv_len may be smaller or larger than q_len).  Strides in elements as in
+ * pgk_sdpa_causal.  f16 / bf16, d 64 or 128, hq % hkv == 0, q_len >= 1, kv_len >= 1, causal_offset >= 0, pointers
+ * 16-byte aligned and strides multiples of 8 elements: anything else is PGK_ERR_INVALID with a message (the
+ * reference's kernel returns NaN rows for a negative offset).  Workspaces come from the pool (stream-ordered). */
+pgk_status pgk_sdpa_irope(const void* q, const void* k, const void* v, const void* positions, void* out, int hq, int hkv,
+                          int q_len, int kv_len, int d, float attn_scale, float floor_scale, int causal_offset,
+                          int64_t q_stride_h, int64_t q_stride_s, int64_t kv_stride_h, int64_t kv_stride_s,
+                          int64_t o_stride_h, int64_t o_stride_s, pgk_dtype pos_dt, pgk_dtype dt, pgk_stream s);
 /* ops.cuh:294-300 sdpa_causal_fixed_cache / _ptr: Q[Hq,q_len,D] over the first context_len rows of
  * cache[Hc,max_seq,D].  ctx_buf (device int32) overrides h_context_len when non-NULL.  q_len == 1
  * uses split-KV flash-decoding (replaces native/ops/nn/flash_decoding.cuh:75-377, fp16-only there);

@@ -30,6 +30,33 @@ struct FlashStrides { long long qh, qs, kh, ks, oh, os; };
 
 constexpr int FL_BQ = 128, FL_BKV = 64, FL_THREADS = 256;
 
+// Llama-4 iRoPE temperature of a query position (reference: native/ops/nn/llama4_kernels.cuh:228):
+//   t = log1pf(floorf((float)(pos + 1) / floor_scale)) * attn_scale + 1, every step rounded to fp32 in that order.
+// log1pf is taken as the CORRECTLY ROUNDED value (evaluated in double, rounded once) and the multiply-add is not
+// contracted into an FMA, so a host restatement that rounds after every step reproduces t bit for bit whatever
+// libm it runs on.  One evaluation per query row, outside every loop.
+__device__ __forceinline__ float irope_temperature(long long pos, float attn_scale, float floor_scale) {
+#pragma clang fp contract(off)
+    const float steps = floorf((float)(pos + 1) / floor_scale);
+    const float lg = (float)log1p((double)steps);
+    const float scaled = lg * attn_scale;
+    return scaled + 1.0f;
+}
+__device__ __forceinline__ long long irope_position(const void* positions, int i, int pos_is_i64) {
+    return pos_is_i64 ? (long long)static_cast<const int64_t*>(positions)[i] : (long long)static_cast<const int32_t*>(positions)[i];
+}
+
+// Optional last argument of flash_fwd_kernel (ops_flash.hip).  FlashPlain: sdpa_causal, mask offset kv_len - q_len, one
+// scale for every row.  FlashIrope: sdpa_irope (ops_llama4.hip), the row's temperature folded into the Q premultiply and
+// a free mask offset.
+struct FlashPlain {};
+struct FlashIrope {
+    const void* positions;   // [q_len] int64 or int32
+    float attn_scale, floor_scale;
+    int causal_offset;       // row i sees kv j <= i + causal_offset
+    int pos_is_i64;
+};
+
 // V^T image: [D][64 kv] 16-bit = 128-byte rows, 8-byte chunk c8 (0..15) of row d at d*128 + ((c8 ^ ((d>>1) & 15)) << 3):
 // the 32 rows a half-wave reads at one c8 then fall on 32 different bank pairs
 __device__ __forceinline__ int fl_v_off(int d, int c8) { return d * 128 + ((c8 ^ ((d >> 1) & 15)) << 3); }

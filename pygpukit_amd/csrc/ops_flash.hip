@@ -17,6 +17,8 @@
 // Workgroups are ordered heavy-first (causal: late query tiles see more keys) and all query heads of a kv head
 // share id % Hkv, i.e. an XCD when Hkv is a multiple of 8, so the K/V stream of a head is served by one L2.
 // Mask: kv_pos <= (kv_len - q_len) + q_pos  (reference: native/ops/nn/attention_kernels.cuh:32-148).
+// The same kernel is Llama-4's sdpa_irope (pgk_sdpa_irope, ops_llama4.hip) when its last argument is a FlashIrope: the
+// row's temperature joins the Q premultiply and the mask offset is an argument, kv_pos <= causal_offset + q_pos.
 
 #include "flash_common.hip.h"
 
@@ -25,10 +27,12 @@ namespace pgk {
 // K image: [64 kv][D] 16-bit, 16-byte chunk c (0..D/8-1) of row r at r*2D + ((c ^ (r & (D/8-1))) << 4)
 template <int D> __device__ __forceinline__ int fl_k_off(int r, int c) { return r * (2 * D) + ((c ^ (r & (D / 8 - 1))) << 4); }
 
-template <class T, int D>
+// X = FlashPlain: sdpa_causal.  X = FlashIrope: sdpa_irope - the two differences are `if constexpr (IROPE)` below.
+template <class T, int D, class X = FlashPlain>
 __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, const T* k, const T* vt, T* out, int hq, int hkv,
                                                               int q_len, int kv_len, int kv_pad, float scale_log2e, FlashStrides sd,
-                                                              FlashSplit sp) {
+                                                              FlashSplit sp, X ex) {
+    constexpr bool IROPE = std::is_same<X, FlashIrope>::value;
     constexpr int NC = D / 8;            // 16-byte chunks per K row
     constexpr int KS = D / 16;           // k-steps of Q.K^T
     constexpr int DT = D / 32;           // 32-row tiles of O^T
@@ -55,7 +59,9 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
     const int split = order % sp.nsplit;
     const int qt = nqt - 1 - order / sp.nsplit;
     const int qw0 = qt * FL_BQ + wid * 32;          // first query row of this wave
-    const int causal_off = kv_len - q_len;
+    int mask_off = kv_len - q_len;
+    if constexpr (IROPE) mask_off = ex.causal_offset;
+    const int causal_off = mask_off;
     const T* qh = q + (size_t)head * sd.qh;
     const T* kh = k + (size_t)kvh * sd.kh;
     const T* vh = vt + (size_t)kvh * D * kv_pad;
@@ -66,6 +72,10 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
         // Q is pre-multiplied by scale * log2(e) here (one rounding to 16 bits more, inside the 1e-2 bar): the scores come
         // out of the MFMA already in the exp2 domain and the per-tile scaling pass (32 multiplies per lane) disappears
         const T* qrow = qh + (size_t)min(qw0 + ql, q_len - 1) * sd.qs + 8 * h;
+        // iRoPE: the row's temperature t(positions[row]) rides in the same multiply - still one rounding to 16 bits
+        float qmul = scale_log2e;
+        if constexpr (IROPE)
+            qmul *= irope_temperature(irope_position(ex.positions, min(qw0 + ql, q_len - 1), ex.pos_is_i64), ex.attn_scale, ex.floor_scale);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             Vec<T> v;
@@ -73,7 +83,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
             float f[8];
             v.to_float(f);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] *= scale_log2e;
+            for (int j = 0; j < 8; ++j) f[j] *= qmul;
             v.from_float(f);
             qf[ks] = v.raw;
         }
@@ -270,7 +280,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
     const int qrow = qw0 + ql;
-    if constexpr (std::is_same<T, bf16>::value && D == 128) {
+    if constexpr (std::is_same<T, bf16>::value && D == 128 && !IROPE) {
         if (sp.q8 != nullptr && sp.nsplit == 1) {       // workgroup-uniform
             // the lane's 64 dims (the partner lane ^ 32 holds the other 64), rounded to bf16 as the plain store would
             float amax = 0.f;
@@ -316,12 +326,14 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
     }
 }
 
-template <class T, int D>
+// kv_seen: the keys the heaviest query tile walks (sdpa_causal: all of them; sdpa_irope: min(kv_len, causal_offset + q_len))
+template <class T, int D, class X = FlashPlain>
 static pgk_status flash_launch(const T* q, const T* k, const T* v, T* out, int hq, int hkv, int q_len, int kv_len, float scale,
-                               const FlashStrides& sd, hipStream_t st, uint8_t* q8 = nullptr, float* q8s = nullptr) {
+                               const FlashStrides& sd, hipStream_t st, uint8_t* q8 = nullptr, float* q8s = nullptr, X ex = X{},
+                               int kv_seen = 0) {
     const int kv_pad = ceil_div(kv_len, 64) * 64;
     const int nqt = ceil_div(q_len, FL_BQ);
-    const int nsplit = flash_nsplit(nqt, hq, kv_len);
+    const int nsplit = flash_nsplit(nqt, hq, kv_seen > 0 ? kv_seen : kv_len);
     const size_t vt_bytes = (size_t)hkv * D * kv_pad * sizeof(T);
     const size_t po_bytes = nsplit > 1 ? (size_t)nsplit * q_len * hq * D * sizeof(T) : 0;
     const size_t ml_bytes = nsplit > 1 ? (size_t)nsplit * hq * q_len * 2 * sizeof(float) : 0;
@@ -338,12 +350,12 @@ static pgk_status flash_launch(const T* q, const T* k, const T* v, T* out, int h
     constexpr size_t LDS = 2 * (size_t)(64 * D * 2) + 2 * (size_t)(D * 128);
     static bool attr_done = false;
     if (LDS > 48 * 1024 && !attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd_kernel<T, D>),
+        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd_kernel<T, D, X>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
         attr_done = true;
     }
-    flash_fwd_kernel<T, D><<<nqt * hq * nsplit, FL_THREADS, LDS, st>>>(q, k, (const T*)vt, out, hq, hkv, q_len, kv_len, kv_pad,
-                                                                      scale * 1.4426950408889634f, sd, sp);
+    flash_fwd_kernel<T, D, X><<<nqt * hq * nsplit, FL_THREADS, LDS, st>>>(q, k, (const T*)vt, out, hq, hkv, q_len, kv_len, kv_pad,
+                                                                         scale * 1.4426950408889634f, sd, sp, ex);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && nsplit > 1) {
         const size_t work = (size_t)q_len * hq * (D / 8);
@@ -366,6 +378,27 @@ pgk_status flash_prefill(const void* q, const void* k, const void* v, void* out,
     }
     if (d == 128) return flash_launch<f16, 128>((const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, hq, hkv, q_len, kv_len, scale, sd, st);
     return flash_launch<f16, 64>((const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, hq, hkv, q_len, kv_len, scale, sd, st);
+}
+
+// entry used by pgk_sdpa_irope (ops_llama4.hip), which has checked the arguments: scale is 1/sqrt(d); row i sees
+// kv j <= i + causal_offset (>= 0), so an offset beyond kv_len masks nothing and is clamped to it
+pgk_status flash_prefill_irope(const void* q, const void* k, const void* v, const void* positions, void* out, int hq, int hkv, int q_len,
+                               int kv_len, int d, float attn_scale, float floor_scale, int causal_offset, long long qh, long long qs,
+                               long long kh, long long ks, long long oh, long long os, int pos_is_i64, int dt16, hipStream_t st) {
+    const FlashStrides sd{qh, qs, kh, ks, oh, os};
+    const int off = causal_offset < kv_len ? causal_offset : kv_len;
+    const FlashIrope ex{positions, attn_scale, floor_scale, off, pos_is_i64};
+    const float scale = 1.0f / sqrtf((float)d);
+    const int kv_seen = (long long)off + q_len < kv_len ? off + q_len : kv_len;
+#define PGK_IROPE_CASE(T, DD) \
+    return flash_launch<T, DD, FlashIrope>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st, nullptr, nullptr, ex, kv_seen)
+    if (dt16 == 0) {
+        if (d == 128) PGK_IROPE_CASE(bf16, 128);
+        PGK_IROPE_CASE(bf16, 64);
+    }
+    if (d == 128) PGK_IROPE_CASE(f16, 128);
+    PGK_IROPE_CASE(f16, 64);
+#undef PGK_IROPE_CASE
 }
 
 // engine entry (fp8 x fp8 prefill, bf16, head_dim 128, q_len > 128): causal attention whose result leaves as the o_proj's fp8
