@@ -420,6 +420,24 @@ pgk_status pgk_sdpa_irope(const void* q, const void* k, const void* v, const voi
                           int q_len, int kv_len, int d, float attn_scale, float floor_scale, int causal_offset,
                           int64_t q_stride_h, int64_t q_stride_s, int64_t kv_stride_h, int64_t kv_stride_s,
                           int64_t o_stride_h, int64_t o_stride_s, pgk_dtype pos_dt, pgk_dtype dt, pgk_stream s);
+/* [build-defined: the reference has no cached Llama-4 path]  llama4_qk_norm_cache_write: one launch over the projection
+ * buffers q [seq, hq*d], k / v [seq, hkv*d] (row-major) and the caches [hkv, max_seq, d] (pgk_kv_cache_write's
+ * un-expanded layout): with qk_norm != 0 every Q head row is l2-normalised in place and every K head row is normalised
+ * on its way to k_cache[h][pos0 + s] (k itself is not written); V goes to v_cache[h][pos0 + s].  The normalisation is
+ * pgk_l2norm's, bit for bit.  pos0 = pos_buf[0] (device int32) when pos_buf is non-NULL, else h_pos.  Rows with
+ * pos0 + s outside [0, max_seq) are not written; a host position with h_pos + seq > max_seq is PGK_ERR_INVALID.
+ * f16 / bf16, d 64 or 128, 16-byte aligned pointers, seq >= 1.  No allocation, no sync. */
+pgk_status pgk_llama4_qk_norm_cache_write(void* q, const void* k, const void* v, void* k_cache, void* v_cache, int seq, int hq,
+                                          int hkv, int max_seq, int d, float eps, int qk_norm, int h_pos,
+                                          const int32_t* pos_buf, pgk_dtype dt, pgk_stream s);
+/* [build-defined] sdpa_irope_fixed_cache: split-KV flash-decoding of one query row Q [hq, 1, d] over rows 0 .. pos of the
+ * caches [hkv, max_seq, d] = pgk_sdpa_irope(Q, cache[:, :pos+1], positions = [pos], causal_offset = pos); pos = pos_buf[0]
+ * when pos_buf is non-NULL (clamped to the cache on the device), else h_pos (outside [0, max_seq): PGK_ERR_INVALID).
+ * t(pos) / sqrt(d) multiplies the fp32 q values: Q * t is never rounded to 16 bits.  `workspace` must hold
+ * pgk_sdpa_decode_workspace_bytes(hq, d, max_seq).  f16 / bf16, d 64 or 128, hq % hkv == 0.  No allocation, no sync. */
+pgk_status pgk_sdpa_irope_fixed_cache(const void* q, const void* k_cache, const void* v_cache, void* out, int hq, int hkv,
+                                      int max_seq, int d, float attn_scale, float floor_scale, int h_pos,
+                                      const int32_t* pos_buf, void* workspace, pgk_dtype dt, pgk_stream s);
 /* ops.cuh:294-300 sdpa_causal_fixed_cache / _ptr: Q[Hq,q_len,D] over the first context_len rows of
  * cache[Hc,max_seq,D].  ctx_buf (device int32) overrides h_context_len when non-NULL.  q_len == 1
  * uses split-KV flash-decoding (replaces native/ops/nn/flash_decoding.cuh:75-377, fp16-only there);

@@ -104,6 +104,8 @@ _PROTOS = {
     "pgk_quantize_fp8_per_head": [_V, _V, _V, _I, _I, _I, _I64, _I64, _I, _V], "pgk_device_arch": [C.POINTER(_I)],
     "pgk_l2norm": [_V, _V, _I, _I, _F, _I, _V], "pgk_irope_scale_q": [_V, _V, _V, _I, _I, _I, _F, _F, _I, _I, _V],
     "pgk_sdpa_irope": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _F, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _V],
+    "pgk_llama4_qk_norm_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _I, _V, _I, _V],
+    "pgk_sdpa_irope_fixed_cache": [_V, _V, _V, _V, _I, _I, _I, _I, _F, _F, _I, _V, _V, _I, _V],
     "pgk_sdpa_fixed_cache": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _V, _V, _I, _V],
     "pgk_engine_create": [C.POINTER(ModelConfig), _V, _V, _V, C.POINTER(LayerWeights), c_void_pp],
     "pgk_engine_destroy": [_V], "pgk_engine_bytes": [_V, C.POINTER(_Z), C.POINTER(_Z)],

@@ -326,6 +326,14 @@ __device__ __forceinline__ float decode_combine(const float* recs, int nsplit, i
     return l > 0.f ? o / l : 0.f;
 }
 
+// Phase 2 of the op-level split-KV decode: one block per query head merges the head's `nsplit` chunk records.
+template <class T, int D>
+__global__ void decode_phase2_kernel(const float* ws, T* out, int nsplit) {
+    const int h = blockIdx.x;
+    for (int d = threadIdx.x; d < D; d += blockDim.x)
+        out[(size_t)h * D + d] = from_f<T>(decode_combine<D>(ws + (size_t)h * nsplit * (D + 2), nsplit, d));
+}
+
 // Chunking rule shared by producer and consumer: nsplit fixed at capture time from max_seq,
 // chunk length derived from the live context length (read from device memory under a graph).
 __device__ __host__ __forceinline__ int decode_chunk_len(int ctx, int nsplit, int gran = 32) {

@@ -384,14 +384,7 @@ __global__ __launch_bounds__(256) void decode_phase1_kernel(const T* q, const T*
     decode_block_merge<D, G>(st, lds, ws + ((size_t)h0 * nsplit + blockIdx.x) * RS, (size_t)nsplit * RS, lane, wid);
 }
 
-template <class T, int D>
-__global__ void decode_phase2_kernel(const float* ws, T* out, int nsplit) {
-    const int h = blockIdx.x;
-    for (int d = threadIdx.x; d < D; d += blockDim.x)
-        out[(size_t)h * D + d] = from_f<T>(decode_combine<D>(ws + (size_t)h * nsplit * (D + 2), nsplit, d));
-}
-
-static int decode_nsplit(int max_seq) {
+int decode_nsplit(int max_seq) {        // also the split count of pgk_sdpa_irope_fixed_cache (ops_llama4.hip)
     int n = (max_seq + 255) / 256;  // ~256 positions per chunk at full context
     if (n < 1) n = 1;
     return n > 64 ? 64 : n;

@@ -2,13 +2,18 @@
 //   pgk_l2norm         y = x * rsqrt(mean(x^2) + eps) over the last dimension, no gamma (Llama4TextL2Norm)
 //   pgk_irope_scale_q  Q[s][h][:] *= t(positions[s])                            (the stand-alone temperature scaling)
 //   pgk_sdpa_irope     softmax(Q.K^T * t(positions[i]) / sqrt(d) + mask) . V    (mask: kv j <= i + causal_offset)
+//   pgk_llama4_qk_norm_cache_write   l2norm(Q) in place, l2norm(K) -> k_cache rows, V -> v_cache rows: one launch
+//   pgk_sdpa_irope_fixed_cache       sdpa_irope of ONE query row over cache rows 0 .. pos (split-KV flash-decoding)
 // The attention itself is flash_fwd_kernel<T, D, FlashIrope> of ops_flash.hip: the reference runs one block per (head,
 // query row) over a kv_len-float score array; here the temperature is one more factor in the Q premultiply of the MFMA
 // flash kernel and the mask offset is an argument, so sdpa_irope runs at sdpa_causal's speed.
 
+#include "attn_core.hip.h"
 #include "flash_common.hip.h"
 
 namespace pgk {
+
+int decode_nsplit(int max_seq);         // ops_attention.hip: the split count pgk_sdpa_decode_workspace_bytes sizes for
 
 pgk_status flash_prefill_irope(const void* q, const void* k, const void* v, const void* positions, void* out, int hq, int hkv, int q_len,
                                int kv_len, int d, float attn_scale, float floor_scale, int causal_offset, long long qh, long long qs,
@@ -18,6 +23,20 @@ pgk_status flash_prefill_irope(const void* q, const void* k, const void* v, cons
 // features 64 / 128 (the model's [S * H, head_dim] case): a row is held by the LANES = features / Vec<T>::N lanes that one
 // 16-byte load each covers (8 .. 32), a wave takes 64 / LANES rows, the sum of squares is a DPP reduction inside the group.
 // in == out is fine: a lane writes only what it has read.
+// f: this lane's N values of a row of F that LANES = F / N consecutive lanes hold together -> the normalised values.
+// Every lane of the wave must call it (the sum of squares is a DPP reduction inside the group).
+template <int F, int N>
+__device__ __forceinline__ void l2norm_row_values(float (&f)[N], float eps) {
+    constexpr int LANES = F / N;
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < N; ++j) ss += f[j] * f[j];
+    ss = group_sum<LANES>(ss);
+    const float inv = 1.0f / sqrtf(ss / F + eps);
+#pragma unroll
+    for (int j = 0; j < N; ++j) f[j] *= inv;
+}
+
 template <class T, int F>
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(const T* x, T* out, int rows, float eps) {
     constexpr int N = Vec<T>::N, LANES = F / N;
@@ -30,13 +49,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const T* x, T* out, in
     v.raw = make_uint4(0, 0, 0, 0);
     if (on) v.load(x + row * F + c * N);
     v.to_float(f);
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < N; ++j) ss += f[j] * f[j];
-    ss = group_sum<LANES>(ss);                // every lane of the wave takes part
-    const float inv = 1.0f / sqrtf(ss / F + eps);
-#pragma unroll
-    for (int j = 0; j < N; ++j) f[j] *= inv;
+    l2norm_row_values<F, N>(f, eps);          // every lane of the wave takes part
     v.from_float(f);
     if (on) v.store(out + row * F + c * N);
 }
@@ -112,6 +125,99 @@ static pgk_status launch_irope_scale_q(const void* q, const void* positions, voi
     return PGK_OK;
 }
 
+// ---- llama4_qk_norm_cache_write --------------------------------------------------------------------------------------
+// One lane-group (D / 8 lanes, a 16-byte access each) per head row of the S x (Hq + 2 Hkv) head rows of q | k | v:
+//   Q head  : normalised in place                                   (l2norm_rows_kernel's arithmetic: l2norm_row_values)
+//   K head  : normalised, written to k_cache[h][pos0 + s]            (k itself is left as projected)
+//   V head  : copied to v_cache[h][pos0 + s]
+// A row pos0 + s outside [0, max_seq) is not written (a device-resident position is not checked by the host).
+template <class T, int D>
+__global__ __launch_bounds__(256) void qk_norm_cache_write_kernel(T* q, const T* k, const T* v, T* k_cache, T* v_cache, int seq, int hq,
+                                                                  int hkv, int max_seq, float eps, int qk_norm, int host_pos,
+                                                                  const int32_t* pos_buf) {
+    constexpr int N = Vec<T>::N, LANES = D / N;
+    const int per_row = hq + 2 * hkv;
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long item = gid / LANES;
+    const int c = (int)(gid % LANES);
+    const bool on = item < (long long)seq * per_row;      // whole groups: 256 % LANES == 0
+    const int s = on ? (int)(item / per_row) : 0, j = on ? (int)(item % per_row) : 0;
+    const bool is_q = j < hq, is_k = !is_q && j < hq + hkv;
+    const int h = is_q ? j : (is_k ? j - hq : j - hq - hkv);
+    const T* src = is_q ? q + ((size_t)s * hq + h) * D : (is_k ? k : v) + ((size_t)s * hkv + h) * D;
+    Vec<T> x;
+    x.raw = make_uint4(0, 0, 0, 0);
+    if (on) x.load(src + c * N);
+    float f[N];
+    x.to_float(f);
+    l2norm_row_values<D, N>(f, eps);                      // every lane of the wave takes part, V rows and idle lanes too
+    if (qk_norm && (is_q || is_k)) x.from_float(f);       // V rows, and everything without qk_norm, keep their bits
+    if (!on) return;
+    if (is_q) {
+        if (qk_norm) x.store(q + ((size_t)s * hq + h) * D + c * N);
+        return;
+    }
+    const long long row = (long long)(pos_buf ? pos_buf[0] : host_pos) + s;
+    if (row < 0 || row >= max_seq) return;                // never write outside the cache
+    x.store((is_k ? k_cache : v_cache) + ((size_t)h * max_seq + (size_t)row) * D + c * N);
+}
+
+// ---- sdpa_irope_fixed_cache ------------------------------------------------------------------------------------------
+// decode_phase1_kernel of ops_attention.hip with the query's temperature: the position comes from the host or from
+// pos_buf[0], the context is rows 0 .. pos (clamped to the cache), and t(pos) * scale multiplies the fp32 q values -
+// Q * t is never rounded to 16 bits.  Same chunking, records and phase 2 as pgk_sdpa_fixed_cache.
+template <class T, int D, int G>
+__global__ __launch_bounds__(256) void irope_decode_phase1_kernel(const T* q, const T* kc, const T* vc, float* ws, int hq, int hkv,
+                                                                  int max_seq, float scale, float attn_scale, float floor_scale,
+                                                                  int host_pos, const int32_t* pos_buf, int nsplit) {
+    constexpr int LPR = D / 8, PPW = 64 / LPR, RS = D + 2;
+    __shared__ float lds[4 * PPW * G * RS];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int pos = max(pos_buf ? pos_buf[0] : host_pos, 0);
+    const int ctx = min(pos, max_seq - 1) + 1;
+    const float qmul = irope_temperature(pos, attn_scale, floor_scale) * scale;
+    const int h0 = blockIdx.y * G;                  // G consecutive query heads of one kv head (G divides Hq / Hkv)
+    const int kv_head = h0 / (hq / hkv);
+    const int chunk = decode_chunk_len(ctx, nsplit);
+    const int c0 = min(blockIdx.x * chunk, ctx), c1 = min(c0 + chunk, ctx);
+    float qf[G][8];
+    const int sub = lane % LPR;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        KVLoad<T>::load8(q + (size_t)(h0 + g) * D + sub * 8, qf[g]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[g][j] *= qmul;
+    }
+    DecodeState<G> st;
+    st.init();
+    decode_walk<T, D, G>(kc + (size_t)kv_head * max_seq * D, vc + (size_t)kv_head * max_seq * D, c0, c1, qf, lane, wid, st);
+    decode_block_merge<D, G>(st, lds, ws + ((size_t)h0 * nsplit + blockIdx.x) * RS, (size_t)nsplit * RS, lane, wid);
+}
+
+template <class T, int D>
+static pgk_status launch_irope_decode(const void* q, const void* kc, const void* vc, void* out, float* ws, int hq, int hkv, int max_seq,
+                                      float attn_scale, float floor_scale, int host_pos, const int32_t* pos_buf, hipStream_t st) {
+    const int nsplit = decode_nsplit(max_seq), rep = hq / hkv;
+    const float scale = 1.0f / sqrtf((float)D);
+    // Every K / V row is read once per group of G query heads.  1 / 2 / 4 as in pgk_sdpa_fixed_cache; 5 serves Llama-4
+    // Scout's Hq / Hkv = 40 / 8 in one pass, but only where its grid still has a workgroup per CU (256): with fewer the
+    // walk is latency-bound and G = 1's five times as many workgroups win (measured at 40 / 8 heads, D = 128: 8.4 against
+    // 13.7 us in a cache of 512 rows, 17.3 against 19.9 at 4096; 47.3 against 46.0 at 16384, 96.1 against 86.8 at 65536).
+    int G = rep % 4 == 0 ? 4 : rep % 2 == 0 ? 2 : 1;
+    if (G == 1 && rep % 5 == 0 && (long long)nsplit * (hq / 5) >= 256) G = 5;
+    const dim3 grid(nsplit, hq / G);
+#define PGK_IROPE_DEC(GG)                                                                                                              \
+    case GG:                                                                                                                           \
+        irope_decode_phase1_kernel<T, D, GG><<<grid, 256, 0, st>>>((const T*)q, (const T*)kc, (const T*)vc, ws, hq, hkv, max_seq, scale, \
+                                                                   attn_scale, floor_scale, host_pos, pos_buf, nsplit);               \
+        break;
+    switch (G) { PGK_IROPE_DEC(1) PGK_IROPE_DEC(2) PGK_IROPE_DEC(4) PGK_IROPE_DEC(5) }
+#undef PGK_IROPE_DEC
+    decode_phase2_kernel<T, D><<<hq, D, 0, st>>>(ws, (T*)out, nsplit);
+    PGK_LAUNCH_CHECK();
+    return PGK_OK;
+}
+
 }  // namespace pgk
 
 using namespace pgk;
@@ -160,6 +266,53 @@ pgk_status pgk_sdpa_irope(const void* q, const void* k, const void* v, const voi
     return flash_prefill_irope(q, k, v, positions, out, hq, hkv, q_len, kv_len, d, attn_scale, floor_scale, causal_offset, q_stride_h,
                                q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s, pos_dt == PGK_I64, dt == PGK_BF16 ? 0 : 1,
                                resolve_stream(s));
+}
+
+pgk_status pgk_llama4_qk_norm_cache_write(void* q, const void* k, const void* v, void* k_cache, void* v_cache, int seq, int hq, int hkv,
+                                          int max_seq, int d, float eps, int qk_norm, int h_pos, const int32_t* pos_buf, pgk_dtype dt,
+                                          pgk_stream s) {
+    PGK_REQUIRE(q && k && v && k_cache && v_cache, "pgk_llama4_qk_norm_cache_write: null pointer");
+    PGK_REQUIRE(dt == PGK_BF16 || dt == PGK_F16, "pgk_llama4_qk_norm_cache_write: float16 / bfloat16 only (dtype %d)", (int)dt);
+    PGK_REQUIRE(d == 64 || d == 128, "pgk_llama4_qk_norm_cache_write: head_dim must be 64 or 128 (got %d)", d);
+    PGK_REQUIRE(hq > 0 && hkv > 0 && hq % hkv == 0, "pgk_llama4_qk_norm_cache_write: n_heads mismatch (Hq=%d, Hkv=%d)", hq, hkv);
+    PGK_REQUIRE(seq >= 1 && max_seq >= 1, "pgk_llama4_qk_norm_cache_write: bad shape seq=%d max_seq=%d", seq, max_seq);
+    PGK_REQUIRE(pos_buf || (h_pos >= 0 && (long long)h_pos + seq <= max_seq), "pgk_llama4_qk_norm_cache_write: rows %d..%lld outside cache of %d",
+                h_pos, (long long)h_pos + seq, max_seq);
+    PGK_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(k_cache) && aligned16(v_cache),
+                "pgk_llama4_qk_norm_cache_write: pointers must be 16-byte aligned");
+    const long long lanes = (long long)seq * (hq + 2 * hkv) * (d / 8);
+    PGK_REQUIRE((lanes + 255) / 256 < (1LL << 31), "pgk_llama4_qk_norm_cache_write: too many rows");
+    hipStream_t st = resolve_stream(s);
+    const unsigned grid = (unsigned)((lanes + 255) / 256);
+#define PGK_PREP(T, DD)                                                                                                                  \
+    qk_norm_cache_write_kernel<T, DD><<<grid, 256, 0, st>>>((T*)q, (const T*)k, (const T*)v, (T*)k_cache, (T*)v_cache, seq, hq, hkv, max_seq, \
+                                                            eps, qk_norm, h_pos, pos_buf)
+    if (dt == PGK_BF16) { if (d == 128) PGK_PREP(bf16, 128); else PGK_PREP(bf16, 64); }
+    else { if (d == 128) PGK_PREP(f16, 128); else PGK_PREP(f16, 64); }
+#undef PGK_PREP
+    PGK_LAUNCH_CHECK();
+    return PGK_OK;
+}
+
+pgk_status pgk_sdpa_irope_fixed_cache(const void* q, const void* k_cache, const void* v_cache, void* out, int hq, int hkv, int max_seq,
+                                      int d, float attn_scale, float floor_scale, int h_pos, const int32_t* pos_buf, void* workspace,
+                                      pgk_dtype dt, pgk_stream s) {
+    PGK_REQUIRE(q && k_cache && v_cache && out && workspace, "pgk_sdpa_irope_fixed_cache: null pointer");
+    PGK_REQUIRE(dt == PGK_BF16 || dt == PGK_F16, "pgk_sdpa_irope_fixed_cache: float16 / bfloat16 only (dtype %d)", (int)dt);
+    PGK_REQUIRE(d == 64 || d == 128, "pgk_sdpa_irope_fixed_cache: head_dim must be 64 or 128 (got %d)", d);
+    PGK_REQUIRE(hq > 0 && hkv > 0 && hq % hkv == 0, "pgk_sdpa_irope_fixed_cache: n_heads mismatch (Hq=%d, Hkv=%d)", hq, hkv);
+    PGK_REQUIRE(max_seq >= 1, "pgk_sdpa_irope_fixed_cache: max_seq=%d", max_seq);
+    PGK_REQUIRE(pos_buf || (h_pos >= 0 && h_pos < max_seq), "pgk_sdpa_irope_fixed_cache: position %d outside cache of %d rows", h_pos, max_seq);
+    PGK_REQUIRE(floor_scale > 0.f, "pgk_sdpa_irope_fixed_cache: floor_scale must be positive");
+    PGK_REQUIRE(aligned16(q) && aligned16(k_cache) && aligned16(v_cache), "pgk_sdpa_irope_fixed_cache: pointers must be 16-byte aligned");
+    hipStream_t st = resolve_stream(s);
+    float* ws = (float*)workspace;
+    if (dt == PGK_BF16) {
+        if (d == 128) return launch_irope_decode<bf16, 128>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
+        return launch_irope_decode<bf16, 64>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
+    }
+    if (d == 128) return launch_irope_decode<f16, 128>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
+    return launch_irope_decode<f16, 64>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
 }
 
 }  // extern "C"

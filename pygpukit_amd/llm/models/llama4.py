@@ -8,7 +8,13 @@ reference; the data movement is this project's:
   * attention reads Q, K, V in their [S, H*D] projection layout through sdpa_irope_strided and writes [S, Hq*D]: no
     [S,H,D] <-> [H,S,D] transposes, and the L2 norm runs in place on the projection buffers;
   * the embedding rows are gathered on the device.
-`generate` re-runs `forward` on the growing sequence, like the reference (no KV cache for this model yet)."""
+`generate` re-runs `forward` on the growing sequence, like the reference, unless use_cache=True.
+
+KV-cache decode (build-defined; the reference has none for this model): `init_fixed_cache` allocates per-layer caches
+[Hkv, max_seq, D] and the one-token buffers, `prefill_fixed_cache` runs `forward`'s op sequence with attention reading
+the cache (so a prompt may come in chunks), `decode_step` runs one token through the _ptr ops on the persistent buffers
+(token id and position live in device memory), and `capture_decode` / `decode_step_graph` replay that step as one graph.
+Per layer a cached step is llama4_qk_norm_cache_write + sdpa_irope_fixed_cache between the projections."""
 
 from __future__ import annotations
 
@@ -20,10 +26,13 @@ from pathlib import Path
 import numpy as np
 
 from pygpukit_amd.core.array import GPUArray
-from pygpukit_amd.core.dtypes import bfloat16, float16, float32
+from pygpukit_amd.core.dtypes import bfloat16, float16, float32, int32
 from pygpukit_amd.core.factory import from_numpy
-from pygpukit_amd.ops.basic import add, embedding_lookup_batch, matmul_nt, rmsnorm, swiglu
-from pygpukit_amd.ops.nn import l2norm, sdpa_irope_strided
+from pygpukit_amd.core.stream import CudaGraph
+from pygpukit_amd.ops.basic import add, add_inplace, embedding_lookup_batch, embedding_lookup_ptr, matmul_nt, rmsnorm, swiglu
+from pygpukit_amd.ops.nn import (l2norm, llama4_qk_norm_cache_write, llama4_qk_norm_cache_write_ptr, sdpa_irope_fixed_cache_ptr,
+                                 sdpa_irope_strided)
+from pygpukit_amd.ops.nn.attention import _workspace
 
 
 @dataclass
@@ -65,6 +74,41 @@ class Llama4Attention:
         self.num_heads = config.num_attention_heads
         self.num_kv_heads = config.num_key_value_heads
         self.head_dim = config.head_dim
+        self._k_cache: GPUArray | None = None       # [Hkv, max_seq, D], init_fixed_cache
+        self._v_cache: GPUArray | None = None
+
+    def init_fixed_cache(self, max_seq_len: int, dtype) -> None:
+        shape = (self.num_kv_heads, max_seq_len, self.head_dim)
+        self._k_cache, self._v_cache = GPUArray(shape, dtype), GPUArray(shape, dtype)
+        self._k_cache.fill_zeros()
+        self._v_cache.fill_zeros()
+
+    def _qk_norm_args(self) -> dict:
+        return dict(num_heads=self.num_heads, num_kv_heads=self.num_kv_heads, head_dim=self.head_dim, eps=self.config.rms_norm_eps,
+                    qk_norm=self.config.use_qk_norm)
+
+    def prefill_fixed_cache(self, hidden: GPUArray, positions: GPUArray, start_pos: int) -> GPUArray:
+        """`forward` for rows start_pos .. start_pos+S-1 with K / V going to the cache and attention reading it."""
+        S, Hq, Hkv, D = hidden.shape[0], self.num_heads, self.num_kv_heads, self.head_dim
+        q = matmul_nt(hidden, self.q_proj)
+        k = matmul_nt(hidden, self.k_proj)
+        v = matmul_nt(hidden, self.v_proj)
+        llama4_qk_norm_cache_write(q, k, v, self._k_cache, self._v_cache, start_pos, **self._qk_norm_args())
+        attn = GPUArray((S, Hq * D), hidden.dtype)
+        max_seq = self._k_cache.shape[1]
+        sdpa_irope_strided(q, self._k_cache, self._v_cache, positions, attn, Hq, Hkv, S, start_pos + S, D, (D, Hq * D), (max_seq * D, D),
+                           (D, Hq * D), attn_scale=self.config.attn_scale, floor_scale=self.config.floor_scale, causal_offset=start_pos)
+        return matmul_nt(attn, self.o_proj)
+
+    def decode_fixed_cache(self, b: "_DecodeBuffers") -> None:
+        """One token: b.normed -> b.proj, through the cache row at b.position_buf[0].  Writes only persistent buffers."""
+        matmul_nt(b.normed, self.q_proj, out=b.q)
+        matmul_nt(b.normed, self.k_proj, out=b.k)
+        matmul_nt(b.normed, self.v_proj, out=b.v)
+        llama4_qk_norm_cache_write_ptr(b.q, b.k, b.v, self._k_cache, self._v_cache, b.position_buf, **self._qk_norm_args())
+        sdpa_irope_fixed_cache_ptr(b.q_heads, self._k_cache, self._v_cache, b.attn_heads, b.position_buf, self.config.attn_scale,
+                                   self.config.floor_scale)
+        matmul_nt(b.attn, self.o_proj, out=b.proj)
 
     def forward(self, hidden: GPUArray, positions: GPUArray) -> GPUArray:
         """hidden [seq_len, hidden_size], positions [seq_len] int64 / int32 -> [seq_len, hidden_size]."""
@@ -93,6 +137,13 @@ class Llama4MLP:
         up = matmul_nt(hidden, self.up_proj)
         return matmul_nt(swiglu(gate, up, out=gate), self.down_proj)
 
+    def decode_fixed_cache(self, b: "_DecodeBuffers") -> None:
+        """One token: b.normed -> b.proj."""
+        matmul_nt(b.normed, self.gate_proj, out=b.gate)
+        matmul_nt(b.normed, self.up_proj, out=b.up)
+        swiglu(b.gate, b.up, out=b.gate)
+        matmul_nt(b.gate, self.down_proj, out=b.proj)
+
 
 class Llama4Block:
     """Single Llama 4 transformer block."""
@@ -109,6 +160,38 @@ class Llama4Block:
         normed = rmsnorm(hidden, self.post_attn_norm_weight, self.rms_norm_eps)
         return add(hidden, self.mlp.forward(normed))
 
+    def prefill_fixed_cache(self, hidden: GPUArray, positions: GPUArray, start_pos: int) -> GPUArray:
+        normed = rmsnorm(hidden, self.input_norm_weight, self.rms_norm_eps)
+        hidden = add(hidden, self.attn.prefill_fixed_cache(normed, positions, start_pos))
+        normed = rmsnorm(hidden, self.post_attn_norm_weight, self.rms_norm_eps)
+        return add(hidden, self.mlp.forward(normed))
+
+    def decode_fixed_cache(self, b: "_DecodeBuffers") -> None:
+        """One token, b.hidden updated in place."""
+        rmsnorm(b.hidden, self.input_norm_weight, self.rms_norm_eps, out=b.normed)
+        self.attn.decode_fixed_cache(b)
+        add_inplace(b.hidden, b.proj)
+        rmsnorm(b.hidden, self.post_attn_norm_weight, self.rms_norm_eps, out=b.normed)
+        self.mlp.decode_fixed_cache(b)
+        add_inplace(b.hidden, b.proj)
+
+
+class _DecodeBuffers:
+    """The persistent buffers of the one-token step: token id and position (one int32[2] array, so the host updates both
+    with a single 8-byte copy) and every activation."""
+
+    def __init__(self, config: Llama4Config, dtype):
+        H, Hq, Hkv, D = config.hidden_size, config.num_attention_heads, config.num_key_value_heads, config.head_dim
+        self.state = GPUArray((2,), int32)
+        self.state.fill_zeros()
+        self.token_id_buf, self.position_buf = self.state._view(0, (1,)), self.state._view(1, (1,))
+        self.hidden, self.normed, self.proj = (GPUArray((1, H), dtype) for _ in range(3))
+        self.q, self.attn = GPUArray((1, Hq * D), dtype), GPUArray((1, Hq * D), dtype)
+        self.k, self.v = GPUArray((1, Hkv * D), dtype), GPUArray((1, Hkv * D), dtype)
+        self.q_heads, self.attn_heads = self.q.view((Hq, 1, D)), self.attn.view((Hq, 1, D))
+        self.gate, self.up = GPUArray((1, config.intermediate_size), dtype), GPUArray((1, config.intermediate_size), dtype)
+        self.logits = GPUArray((1, config.vocab_size), dtype)
+
 
 class Llama4Model:
     """Llama 4 text model for inference."""
@@ -120,22 +203,107 @@ class Llama4Model:
         self.blocks = blocks
         self.final_norm_weight = final_norm_weight
         self.lm_head = lm_head
+        self.max_cache_len = 0                          # rows of the fixed caches; 0: init_fixed_cache not called
+        self._decode: _DecodeBuffers | None = None
+        self._graph: CudaGraph | None = None
 
-    def forward(self, input_ids: np.ndarray) -> GPUArray:
-        """input_ids [seq_len] -> logits [seq_len, vocab_size]."""
+    def _embed(self, input_ids, name: str) -> tuple[GPUArray, int]:
         ids = np.asarray(input_ids).astype(np.int64).ravel()
         S = int(ids.shape[0])
         if S < 1:
-            raise ValueError("Llama4Model.forward: empty input_ids")
+            raise ValueError(f"Llama4Model.{name}: empty input_ids")
         if ids.min() < 0 or ids.max() >= self.embed_tokens.shape[0]:
-            raise ValueError(f"Llama4Model.forward: token id outside [0, {self.embed_tokens.shape[0]})")
+            raise ValueError(f"Llama4Model.{name}: token id outside [0, {self.embed_tokens.shape[0]})")
         hidden = GPUArray((S, self.embed_tokens.shape[1]), self.embed_tokens.dtype)
         embedding_lookup_batch(self.embed_tokens, hidden, from_numpy(ids.astype(np.int32)), S)
+        return hidden, S
+
+    def forward(self, input_ids: np.ndarray) -> GPUArray:
+        """input_ids [seq_len] -> logits [seq_len, vocab_size]."""
+        hidden, S = self._embed(input_ids, "forward")
         positions = from_numpy(np.arange(S, dtype=np.int64))
         for block in self.blocks:
             hidden = block.forward(hidden, positions)
         hidden = rmsnorm(hidden, self.final_norm_weight, self.config.rms_norm_eps)
         return matmul_nt(hidden, self.lm_head)
+
+    # ---- KV-cache decode -----------------------------------------------------------------------------------------
+    def init_fixed_cache(self, max_seq_len: int) -> None:
+        """Allocate (zeroed) per-layer K / V caches [Hkv, max_seq_len, D] in the model dtype and the one-token buffers.
+        A captured decode graph addresses the old caches, so it is dropped: capture_decode() again."""
+        if max_seq_len < 1:
+            raise ValueError(f"Llama4Model.init_fixed_cache: max_seq_len must be >= 1, got {max_seq_len}")
+        dtype = self.embed_tokens.dtype
+        for block in self.blocks:
+            block.attn.init_fixed_cache(int(max_seq_len), dtype)
+        self._decode = _DecodeBuffers(self.config, dtype)
+        c = self.config
+        _workspace(c.num_attention_heads, c.head_dim, int(max_seq_len))     # the attention op must not allocate under capture
+        self.max_cache_len = int(max_seq_len)
+        self._graph = None
+
+    def _require_cache(self, name: str) -> _DecodeBuffers:
+        if self._decode is None:
+            raise RuntimeError(f"Llama4Model.{name}: call init_fixed_cache() first")
+        return self._decode
+
+    def prefill_fixed_cache(self, input_ids: np.ndarray, start_pos: int = 0) -> GPUArray:
+        """input_ids [S] at positions start_pos .. start_pos+S-1 -> logits [S, vocab_size]; K / V of these rows are left
+        in the caches and attention reads cache rows 0 .. start_pos+S-1, so a prompt may be fed in several chunks."""
+        self._require_cache("prefill_fixed_cache")
+        hidden, S = self._embed(input_ids, "prefill_fixed_cache")
+        if start_pos < 0 or start_pos + S > self.max_cache_len:
+            raise ValueError(f"Llama4Model.prefill_fixed_cache: rows {start_pos}..{start_pos + S} outside the cache of "
+                             f"{self.max_cache_len} rows")
+        positions = from_numpy(np.arange(start_pos, start_pos + S, dtype=np.int64))
+        for block in self.blocks:
+            hidden = block.prefill_fixed_cache(hidden, positions, int(start_pos))
+        hidden = rmsnorm(hidden, self.final_norm_weight, self.config.rms_norm_eps)
+        return matmul_nt(hidden, self.lm_head)
+
+    def _set_state(self, token_id: int, position: int, name: str) -> _DecodeBuffers:
+        b = self._require_cache(name)
+        if not 0 <= token_id < self.embed_tokens.shape[0]:
+            raise ValueError(f"Llama4Model.{name}: token id {token_id} outside [0, {self.embed_tokens.shape[0]})")
+        if not 0 <= position < self.max_cache_len:
+            raise ValueError(f"Llama4Model.{name}: position {position} outside the cache of {self.max_cache_len} rows")
+        b.state.copy_from_numpy(np.array([token_id, position], np.int32))     # the step's only host-to-device copy
+        return b
+
+    def _decode_ops(self, b: _DecodeBuffers) -> None:
+        """The one-token step on the persistent buffers: no allocation, no host value - safe to capture."""
+        embedding_lookup_ptr(self.embed_tokens, b.hidden, b.token_id_buf)
+        for block in self.blocks:
+            block.decode_fixed_cache(b)
+        rmsnorm(b.hidden, self.final_norm_weight, self.config.rms_norm_eps, out=b.normed)
+        matmul_nt(b.normed, self.lm_head, out=b.logits)
+
+    def decode_step(self, token_id: int, position: int) -> GPUArray:
+        """token_id at `position` against cache rows 0 .. position-1 (its own row is written first) -> logits
+        [1, vocab_size]: the model's persistent buffer, valid until the next step."""
+        b = self._set_state(int(token_id), int(position), "decode_step")
+        self._decode_ops(b)
+        return b.logits
+
+    def capture_decode(self) -> None:
+        """Capture the whole one-token step (embedding -> every block -> final norm -> lm_head) as one graph on one stream."""
+        b = self._require_cache("capture_decode")
+        graph = CudaGraph()
+        graph.begin_capture()
+        try:
+            self._decode_ops(b)
+        finally:
+            graph.end_capture()
+        self._graph = graph
+
+    def decode_step_graph(self, token_id: int, position: int) -> GPUArray:
+        """decode_step as the 8-byte state upload + one graph replay; same logits buffer."""
+        if self._graph is None:
+            raise RuntimeError("Llama4Model.decode_step_graph: nothing captured for the current caches - call capture_decode() "
+                               "(again after init_fixed_cache)")
+        b = self._set_state(int(token_id), int(position), "decode_step_graph")
+        self._graph.replay()
+        return b.logits
 
     @classmethod
     def from_safetensors(cls, model_path: str | Path) -> "Llama4Model":
@@ -173,17 +341,39 @@ class Llama4Model:
         return cls(config, embed_tokens, blocks, final_norm, lm_head)
 
 
-def generate(model: Llama4Model, input_ids: np.ndarray, max_new_tokens: int = 50, eos_token_id: int | list[int] = 200001) -> np.ndarray:
-    """Greedy generation; returns the token ids including the input."""
+def _argmax_last(logits: GPUArray) -> int:
+    last = logits.to_numpy()[-1]
+    if last.dtype == np.uint16:     # bfloat16 words
+        last = (last.astype(np.uint32) << 16).view(np.float32)
+    return int(np.argmax(last))
+
+
+def generate(model: Llama4Model, input_ids: np.ndarray, max_new_tokens: int = 50, eos_token_id: int | list[int] = 200001, *,
+             use_cache: bool = False, use_graph: bool = False) -> np.ndarray:
+    """Greedy generation; returns the token ids including the input.  use_cache=True prefills the fixed caches (allocated
+    here if the model has none with room for len(input_ids) + max_new_tokens rows) and decodes one token per step;
+    use_graph=True (with use_cache) decodes through the captured step."""
     eos_token_ids = {eos_token_id} if isinstance(eos_token_id, int) else set(eos_token_id)
     current_ids = [int(t) for t in input_ids]
-    for _ in range(max_new_tokens):
-        logits = model.forward(np.array(current_ids, dtype=np.int64))
-        last = logits.to_numpy()[-1]
-        if last.dtype == np.uint16:     # bfloat16 words
-            last = (last.astype(np.uint32) << 16).view(np.float32)
-        next_token = int(np.argmax(last))
+    if use_graph and not use_cache:
+        raise ValueError("generate: use_graph=True needs use_cache=True")
+    if not use_cache:
+        for _ in range(max_new_tokens):
+            next_token = _argmax_last(model.forward(np.array(current_ids, dtype=np.int64)))
+            current_ids.append(next_token)
+            if next_token in eos_token_ids:
+                break
+        return np.array(current_ids, dtype=np.int64)
+    if max_new_tokens < 1:
+        return np.array(current_ids, dtype=np.int64)
+    if model.max_cache_len < len(current_ids) + max_new_tokens:
+        model.init_fixed_cache(len(current_ids) + max_new_tokens)
+    if use_graph and model._graph is None:
+        model.capture_decode()
+    step = model.decode_step_graph if use_graph else model.decode_step
+    next_token = _argmax_last(model.prefill_fixed_cache(np.array(current_ids, dtype=np.int64)))
+    current_ids.append(next_token)
+    while len(current_ids) - len(input_ids) < max_new_tokens and next_token not in eos_token_ids:
+        next_token = _argmax_last(step(next_token, len(current_ids) - 1))
         current_ids.append(next_token)
-        if next_token in eos_token_ids:
-            break
     return np.array(current_ids, dtype=np.int64)

@@ -3,7 +3,8 @@ from pygpukit_amd.ops.nn.attention import (fa3_fp8_available, get_sm_version, qu
                                           sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr, sdpa_causal_fp8,
                                           sdpa_causal_fp8_strided, sdpa_causal_strided)
 from pygpukit_amd.ops.nn.fused import geglu, glu_packed, rmsnorm_residual, swiglu
-from pygpukit_amd.ops.nn.llama4 import irope_scale_q, l2norm, sdpa_irope, sdpa_irope_strided
+from pygpukit_amd.ops.nn.llama4 import (irope_scale_q, l2norm, llama4_qk_norm_cache_write, llama4_qk_norm_cache_write_ptr,
+                                        sdpa_irope, sdpa_irope_fixed_cache, sdpa_irope_fixed_cache_ptr, sdpa_irope_strided)
 from pygpukit_amd.ops.nn.linear import bias_add_inplace, slice_rows_range_ptr, split_qkv_batch
 from pygpukit_amd.ops.nn.norm import layernorm, rmsnorm
 from pygpukit_amd.ops.nn.rope import rope_inplace, rope_inplace_f32table
@@ -12,4 +13,5 @@ __all__ = ["gelu", "silu", "sigmoid", "tanh", "relu2", "sdpa_causal", "sdpa_caus
            "sdpa_causal_fixed_cache_ptr", "sdpa_causal_strided", "sdpa_causal_fp8", "sdpa_causal_fp8_strided", "fa3_fp8_available",
            "get_sm_version", "quantize_fp8_per_head", "rmsnorm_residual", "swiglu", "geglu", "glu_packed",
            "bias_add_inplace", "split_qkv_batch", "slice_rows_range_ptr", "layernorm", "rmsnorm", "rope_inplace",
-           "rope_inplace_f32table", "l2norm", "irope_scale_q", "sdpa_irope", "sdpa_irope_strided"]
+           "rope_inplace_f32table", "l2norm", "irope_scale_q", "sdpa_irope", "sdpa_irope_strided", "llama4_qk_norm_cache_write",
+           "llama4_qk_norm_cache_write_ptr", "sdpa_irope_fixed_cache", "sdpa_irope_fixed_cache_ptr"]
