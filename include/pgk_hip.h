@@ -438,6 +438,35 @@ pgk_status pgk_llama4_qk_norm_cache_write(void* q, const void* k, const void* v,
 pgk_status pgk_sdpa_irope_fixed_cache(const void* q, const void* k_cache, const void* v_cache, void* out, int hq, int hkv,
                                       int max_seq, int d, float attn_scale, float floor_scale, int h_pos,
                                       const int32_t* pos_buf, void* workspace, pgk_dtype dt, pgk_stream s);
+/* ---- positional encodings beside RoPE (reference: ops/nn/rope.py:386-653; the tables are built on the host) ----
+ * pope_inplace: q [seq, hq, d] and k [seq, hk, d] (f32 / f16 / bf16, the same type) += encoding[start_pos + s][:], encoding
+ * fp32 [max_seq, d]: one fp32 add, one RNE rounding.  start_pos < 0 or start_pos + seq > max_seq is PGK_ERR_INVALID. */
+pgk_status pgk_pope_inplace(void* q, void* k, const void* encoding, int seq, int hq, int hk, int d, int start_pos, int max_seq,
+                            pgk_dtype dt, pgk_stream s);
+/* alibi_compute_bias: bias fp32 [num_heads, seq_len, seq_len] = -slopes[h] * (i - j) (one fp32 multiply; positive for
+ * j > i), or -1e9 for j > i when `causal`.  slopes fp32 [num_heads]. */
+pgk_status pgk_alibi_compute_bias(const void* slopes, void* bias, int seq_len, int num_heads, int causal, pgk_stream s);
+/* alibi_add_bias: scores fp32 [batch, num_heads, q_len, kv_len] -= slopes[h] * (start_pos + i - j) for every j, product and
+ * difference rounded separately (no FMA).  scores_dt / slopes_dt other than PGK_F32, or n_slopes != num_heads, is
+ * PGK_ERR_INVALID. */
+pgk_status pgk_alibi_add_bias(void* scores, const void* slopes, int batch, int num_heads, int q_len, int kv_len, int start_pos,
+                              pgk_dtype scores_dt, pgk_dtype slopes_dt, int n_slopes, pgk_stream s);
+/* [build-defined: the reference only materialises the bias]  sdpa_alibi: with off = kv_len - q_len,
+ *   out[h][i] = softmax_j(q[h][i] . k[h / rep][j] * scale - slopes[h] * (off + i - j), over j <= off + i) . v[h / rep]
+ * on the MFMA flash-prefill kernel; slopes fp32 [hq], one per QUERY head; scale <= 0 means 1 / sqrt(d).  Strides in elements
+ * as in pgk_sdpa_causal.  f16 / bf16, d 64 or 128, hq % hkv == 0, kv_len >= q_len >= 1, pointers 16-byte aligned and strides
+ * non-negative multiples of 8 elements: anything else is PGK_ERR_INVALID with a message.  Workspaces come from the pool. */
+pgk_status pgk_sdpa_alibi(const void* q, const void* k, const void* v, const void* slopes, void* out, int hq, int hkv, int q_len,
+                          int kv_len, int d, float scale, int64_t q_stride_h, int64_t q_stride_s, int64_t kv_stride_h,
+                          int64_t kv_stride_s, int64_t o_stride_h, int64_t o_stride_s, pgk_dtype dt, pgk_stream s);
+/* [build-defined] sdpa_alibi_fixed_cache: pgk_sdpa_fixed_cache's contract (Q [hq, q_len, d] over the first context_len rows of
+ * the caches [hkv, max_seq, d]; ctx_buf, a device int32, overrides h_context_len when non-NULL) with the bias
+ * -slopes[h] * (context_len - q_len + i - j).  q_len == 1: split-KV flash-decoding, `workspace` must hold
+ * pgk_sdpa_decode_workspace_bytes(hq, d, max_seq), no allocation, no sync.  q_len > 1: ctx_buf must be NULL; pgk_sdpa_alibi
+ * over the cache in place.  f16 / bf16, d 64 or 128, hq % hkv == 0, q_len <= context_len <= max_seq. */
+pgk_status pgk_sdpa_alibi_fixed_cache(const void* q, const void* k_cache, const void* v_cache, const void* slopes, void* out, int hq,
+                                      int hkv, int q_len, int max_seq, int d, float scale, int h_context_len, const int32_t* ctx_buf,
+                                      void* workspace, pgk_dtype dt, pgk_stream s);
 /* ops.cuh:294-300 sdpa_causal_fixed_cache / _ptr: Q[Hq,q_len,D] over the first context_len rows of
  * cache[Hc,max_seq,D].  ctx_buf (device int32) overrides h_context_len when non-NULL.  q_len == 1
  * uses split-KV flash-decoding (replaces native/ops/nn/flash_decoding.cuh:75-377, fp16-only there);

@@ -107,6 +107,10 @@ _PROTOS = {
     "pgk_llama4_qk_norm_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _I, _V, _I, _V],
     "pgk_sdpa_irope_fixed_cache": [_V, _V, _V, _V, _I, _I, _I, _I, _F, _F, _I, _V, _V, _I, _V],
     "pgk_sdpa_fixed_cache": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _V, _V, _I, _V],
+    "pgk_pope_inplace": [_V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V], "pgk_alibi_compute_bias": [_V, _V, _I, _I, _I, _V],
+    "pgk_alibi_add_bias": [_V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V],
+    "pgk_sdpa_alibi": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
+    "pgk_sdpa_alibi_fixed_cache": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _V, _V, _I, _V],
     "pgk_engine_create": [C.POINTER(ModelConfig), _V, _V, _V, C.POINTER(LayerWeights), c_void_pp],
     "pgk_engine_destroy": [_V], "pgk_engine_bytes": [_V, C.POINTER(_Z), C.POINTER(_Z)],
     "pgk_engine_prefill": [_V, _I, c_i32_p, _I, _I, _V, C.POINTER(_F), _V],

@@ -10,6 +10,8 @@
 // the end through LDS, and chunks are merged by a second tiny kernel (or by the consumer).
 #pragma once
 
+#include <type_traits>
+
 #include "pgk_device.hip.h"
 
 // diagnostic builds (-DPGK_PHASE_STAMPS): stamps inside the walk, parked like TLStamp::phase (engine_common.hip.h)
@@ -75,12 +77,16 @@ struct DecodeState {
     }
 };
 
+// Additive score term of decode_walk: B{}(g, pos) is added in fp32 to head g's score of cache row pos.  The default adds
+// nothing and compiles to the walk without a hook.
+struct DecodeNoBias {};
+
 // Walk positions [c0, c1) of one KV head's cache rows (row stride D elements).
 // qf[g][8]: this lane's slice of the G pre-scaled queries.  Wave `wid` of 4 takes every 4th
 // position-group.  LPR = D/8 lanes per row.
-template <class T, int D, int G, int NWV = 4>
+template <class T, int D, int G, int NWV = 4, class B = DecodeNoBias>
 __device__ __forceinline__ void decode_walk(const T* kbase, const T* vbase, int c0, int c1, const float (&qf)[G][8],
-                                            int lane, int wid, DecodeState<G>& st) {
+                                            int lane, int wid, DecodeState<G>& st, const B& bias = B{}) {
     constexpr int LPR = D / 8, PPW = 64 / LPR, U = 4, STRIDE = NWV * PPW;
     const int grp = lane / LPR, sub = lane % LPR;
     // U position-groups per trip: all 2*U 16-byte loads are issued before the first is consumed, so a
@@ -105,6 +111,7 @@ __device__ __forceinline__ void decode_walk(const T* kbase, const T* vbase, int 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) d = fmaf(qf[g][j], kf[u][j], d);
                 d = group_sum<LPR>(d);
+                if constexpr (!std::is_same<B, DecodeNoBias>::value) d += bias(g, p0 + u * STRIDE + grp);
                 s[g] = d;
             }
             if (valid[u]) st.update(s, vf[u]);  // lane-group uniform

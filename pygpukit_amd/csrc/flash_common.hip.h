@@ -48,13 +48,17 @@ __device__ __forceinline__ long long irope_position(const void* positions, int i
 
 // Optional last argument of flash_fwd_kernel (ops_flash.hip).  FlashPlain: sdpa_causal, mask offset kv_len - q_len, one
 // scale for every row.  FlashIrope: sdpa_irope (ops_llama4.hip), the row's temperature folded into the Q premultiply and
-// a free mask offset.
+// a free mask offset.  FlashAlibi: sdpa_alibi (ops_posenc.hip), mask as FlashPlain, the score of (row i, key j) of query head h
+// gets -slopes[h] * (kv_len - q_len + i - j): the MFMA accumulators of Q.K^T start at that bias instead of at zero.
 struct FlashPlain {};
 struct FlashIrope {
     const void* positions;   // [q_len] int64 or int32
     float attn_scale, floor_scale;
     int causal_offset;       // row i sees kv j <= i + causal_offset
     int pos_is_i64;
+};
+struct FlashAlibi {
+    const float* slopes;     // [Hq] fp32, one per QUERY head
 };
 
 // V^T image: [D][64 kv] 16-bit = 128-byte rows, 8-byte chunk c8 (0..15) of row d at d*128 + ((c8 ^ ((d>>1) & 15)) << 3):

@@ -19,6 +19,8 @@
 // Mask: kv_pos <= (kv_len - q_len) + q_pos  (reference: native/ops/nn/attention_kernels.cuh:32-148).
 // The same kernel is Llama-4's sdpa_irope (pgk_sdpa_irope, ops_llama4.hip) when its last argument is a FlashIrope: the
 // row's temperature joins the Q premultiply and the mask offset is an argument, kv_pos <= causal_offset + q_pos.
+// With a FlashAlibi it is sdpa_alibi (pgk_sdpa_alibi, ops_posenc.hip): the accumulators of S^T start at the ALiBi bias
+// -slope[head] * (mask_off + q_pos - kv_pos), in the exp2 domain, instead of at zero - no extra pass over the scores.
 
 #include "flash_common.hip.h"
 
@@ -28,11 +30,13 @@ namespace pgk {
 template <int D> __device__ __forceinline__ int fl_k_off(int r, int c) { return r * (2 * D) + ((c ^ (r & (D / 8 - 1))) << 4); }
 
 // X = FlashPlain: sdpa_causal.  X = FlashIrope: sdpa_irope - the two differences are `if constexpr (IROPE)` below.
+// X = FlashAlibi: sdpa_alibi - the head's slope and the start value of the score accumulators, `if constexpr (ALIBI)`.
 template <class T, int D, class X = FlashPlain>
 __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, const T* k, const T* vt, T* out, int hq, int hkv,
                                                               int q_len, int kv_len, int kv_pad, float scale_log2e, FlashStrides sd,
                                                               FlashSplit sp, X ex) {
     constexpr bool IROPE = std::is_same<X, FlashIrope>::value;
+    constexpr bool ALIBI = std::is_same<X, FlashAlibi>::value;
     constexpr int NC = D / 8;            // 16-byte chunks per K row
     constexpr int KS = D / 16;           // k-steps of Q.K^T
     constexpr int DT = D / 32;           // 32-row tiles of O^T
@@ -94,6 +98,11 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;    // running max (scaled, log2 domain) and this lane's half of the row sum
+    // ALiBi: slope * log2(e) of this head (wave-uniform).  The bias of (this lane's query, kv row kv0 + 4h + kvl) is
+    // slope2 * (kv0 + 4h + kvl - mask_off - q) <= 0 on every visible key: the integers stay below 2^24 (exact in fp32) and
+    // the origin is the same for every tile and KV run of a row, so m_run and the split records need no correction.
+    float slope2 = 0.f;
+    if constexpr (ALIBI) slope2 = ex.slopes[head] * 1.4426950408889634f;
 
     const int q_last = min(qt * FL_BQ + FL_BQ - 1, q_len - 1);
     const int kv_end = min(kv_len, causal_off + q_last + 1);
@@ -166,9 +175,19 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
         }
     };
     // S^T = K . Q^T of one tile: two 32-kv sub-tiles (rows = positions, column = this lane's query)
-    auto qk = [&](int buf, f32x16_fl& s0, f32x16_fl& s1) {
+    auto qk = [&](int buf, int kv0, f32x16_fl& s0, f32x16_fl& s1) {
+        if constexpr (ALIBI) {
+            // one FMA per register where the other policies move a zero: literal row offset, per-tile lane base
+            const float base = slope2 * (float)(kv0 + 4 * h - (causal_off + qw0 + ql));
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+            for (int r = 0; r < 16; ++r) {
+                s0[r] = fmaf(slope2, (float)((r & 3) + 8 * (r >> 2)), base);
+                s1[r] = fmaf(slope2, (float)(32 + (r & 3) + 8 * (r >> 2)), base);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+        }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const uint4 a0 = *reinterpret_cast<const uint4*>(Ks(buf) + fl_k_off<D>(ql, 2 * ks + h));
@@ -203,7 +222,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
         const int buf = t & 1, kv0 = t * FL_BKV;
         if (t + 1 < t1) { load_k(t + 1); load_v(t + 1); }
         const bool cur = live(t);
-        if (cur) qk(buf, sc0, sc1);
+        if (cur) qk(buf, kv0, sc0, sc1);
         if (cur) {
             // ---- mask, online softmax (this lane: query qw0 + ql, kv rows (r&3) + 8(r>>2) + 4h of each sub-tile) ----
             const bool need_mask = kv0 + FL_BKV - 1 > causal_off + qw0 || kv0 + FL_BKV > kv_len;   // wave-uniform
@@ -280,7 +299,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
     const int qrow = qw0 + ql;
-    if constexpr (std::is_same<T, bf16>::value && D == 128 && !IROPE) {
+    if constexpr (std::is_same<T, bf16>::value && D == 128 && std::is_same<X, FlashPlain>::value) {
         if (sp.q8 != nullptr && sp.nsplit == 1) {       // workgroup-uniform
             // the lane's 64 dims (the partner lane ^ 32 holds the other 64), rounded to bf16 as the plain store would
             float amax = 0.f;
@@ -399,6 +418,24 @@ pgk_status flash_prefill_irope(const void* q, const void* k, const void* v, cons
     if (d == 128) PGK_IROPE_CASE(f16, 128);
     PGK_IROPE_CASE(f16, 64);
 #undef PGK_IROPE_CASE
+}
+
+// entry used by pgk_sdpa_alibi / pgk_sdpa_alibi_fixed_cache (ops_posenc.hip), which have checked the arguments (scale > 0,
+// kv_len >= q_len); slopes: [hq] fp32 on the device
+pgk_status flash_prefill_alibi(const void* q, const void* k, const void* v, const float* slopes, void* out, int hq, int hkv, int q_len,
+                               int kv_len, int d, float scale, long long qh, long long qs, long long kh, long long ks, long long oh,
+                               long long os, int dt16, hipStream_t st) {
+    const FlashStrides sd{qh, qs, kh, ks, oh, os};
+    const FlashAlibi ex{slopes};
+#define PGK_ALIBI_CASE(T, DD) \
+    return flash_launch<T, DD, FlashAlibi>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st, nullptr, nullptr, ex)
+    if (dt16 == 0) {
+        if (d == 128) PGK_ALIBI_CASE(bf16, 128);
+        PGK_ALIBI_CASE(bf16, 64);
+    }
+    if (d == 128) PGK_ALIBI_CASE(f16, 128);
+    PGK_ALIBI_CASE(f16, 64);
+#undef PGK_ALIBI_CASE
 }
 
 // engine entry (fp8 x fp8 prefill, bf16, head_dim 128, q_len > 128): causal attention whose result leaves as the o_proj's fp8

@@ -1,4 +1,5 @@
 from pygpukit_amd.ops.nn.activation import gelu, relu2, sigmoid, silu, tanh
+from pygpukit_amd.ops.nn.alibi import sdpa_alibi, sdpa_alibi_fixed_cache, sdpa_alibi_fixed_cache_ptr, sdpa_alibi_strided
 from pygpukit_amd.ops.nn.attention import (fa3_fp8_available, get_sm_version, quantize_fp8_per_head, sdpa_causal,
                                           sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr, sdpa_causal_fp8,
                                           sdpa_causal_fp8_strided, sdpa_causal_strided)
@@ -7,11 +8,14 @@ from pygpukit_amd.ops.nn.llama4 import (irope_scale_q, l2norm, llama4_qk_norm_ca
                                         sdpa_irope, sdpa_irope_fixed_cache, sdpa_irope_fixed_cache_ptr, sdpa_irope_strided)
 from pygpukit_amd.ops.nn.linear import bias_add_inplace, slice_rows_range_ptr, split_qkv_batch
 from pygpukit_amd.ops.nn.norm import layernorm, rmsnorm
-from pygpukit_amd.ops.nn.rope import rope_inplace, rope_inplace_f32table
+from pygpukit_amd.ops.nn.rope import (alibi_add_bias, alibi_compute_bias, alibi_init_slopes, pope_init_encoding, pope_inplace,
+                                      rope_init_linear, rope_init_ntk_aware, rope_init_yarn, rope_inplace, rope_inplace_f32table)
 
 __all__ = ["gelu", "silu", "sigmoid", "tanh", "relu2", "sdpa_causal", "sdpa_causal_fixed_cache",
            "sdpa_causal_fixed_cache_ptr", "sdpa_causal_strided", "sdpa_causal_fp8", "sdpa_causal_fp8_strided", "fa3_fp8_available",
            "get_sm_version", "quantize_fp8_per_head", "rmsnorm_residual", "swiglu", "geglu", "glu_packed",
            "bias_add_inplace", "split_qkv_batch", "slice_rows_range_ptr", "layernorm", "rmsnorm", "rope_inplace",
            "rope_inplace_f32table", "l2norm", "irope_scale_q", "sdpa_irope", "sdpa_irope_strided", "llama4_qk_norm_cache_write",
-           "llama4_qk_norm_cache_write_ptr", "sdpa_irope_fixed_cache", "sdpa_irope_fixed_cache_ptr"]
+           "llama4_qk_norm_cache_write_ptr", "sdpa_irope_fixed_cache", "sdpa_irope_fixed_cache_ptr", "rope_init_ntk_aware",
+           "rope_init_yarn", "rope_init_linear", "pope_init_encoding", "pope_inplace", "alibi_init_slopes", "alibi_compute_bias",
+           "alibi_add_bias", "sdpa_alibi", "sdpa_alibi_strided", "sdpa_alibi_fixed_cache", "sdpa_alibi_fixed_cache_ptr"]
