@@ -1,5 +1,5 @@
 // Split-KV decode attention core (flash-decoding) for gfx950, shared by the op-level
-// sdpa_causal_fixed_cache (ops_attention.hip) and the fused decode step (engine.hip).
+// sdpa_causal_fixed_cache (ops_attention.hip) and the fused decode step (engine_attn.hip.h).
 //
 // One workgroup = 4 waves owns one KV head and one contiguous chunk of cached positions and
 // serves all G = Hq/Hkv query heads of that KV head from a single pass over K and V (the

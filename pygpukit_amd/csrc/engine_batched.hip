@@ -1,5 +1,5 @@
 // Batched decode projections on MFMA (3..64 sequences per launch): kernels in engine_batched.hip.h, run-time dispatch here.
-// Its own translation unit so that the ~150 template instances compile beside engine.hip instead of inside it.
+// Its own translation unit so that the ~150 template instances compile beside engine.hip instead of inside it (engine_prefill.hip: the same for the prefill).
 
 #include <cstdlib>
 #include <type_traits>

@@ -1,6 +1,6 @@
 // Batched decode projections on MFMA (3 <= M <= 64 sequences per launch), included by engine_batched.hip.
 //
-// The GEMV kernels of engine.hip score every weight chunk against M activation rows with VALU dot products: 32 packed
+// The GEMV kernels of engine_gemv.hip.h score every weight chunk against M activation rows with VALU dot products: 32 packed
 // dot instructions per 16-byte weight chunk at M = 8, and the kernel turns instruction-bound (gate_up 9.3 us, lm_head
 // 86 us at M = 8 against 5.7 / 50 us at M = 1).  Here the M rows are the (zero-padded) A operand of
 // v_mfma_f32_16x16x32_bf16 and 16 weight rows are its B operand, loaded straight from HBM in fragment shape
@@ -9,7 +9,7 @@
 //   workgroup = 4 waves = 16 output rows (SWIGLU: 16 gate rows and their 16 up rows); the waves split K four ways
 //   (every lane's weight loads - K/128 of them - are issued before the prologue touches the activations), partial
 //   16x16 tiles are summed through LDS; prologue = RMSNorm (or plain copy) of the M rows into an LDS image laid out
-//   [k/8][MP] x 16 B so that an A-fragment read is 64 consecutive 16-byte slots; epilogues as in engine.hip
+//   [k/8][MP] x 16 B so that an A-fragment read is 64 consecutive 16-byte slots; epilogues as in engine_gemv.hip.h
 //   (store / residual add / SiLU(g)*u / logits + per-workgroup argmax partials, lowest index on ties).
 // fp8 weights: 8 codes per lane per step, widened to bf16 with the block scale in registers (as ops_wsgemm.hip).
 
@@ -241,7 +241,7 @@ template <class WT, int PRO, int EPI, int S, int RPG>
 __global__ __launch_bounds__(256) void batched_reg_kernel(unsigned long long* tl, const void* w_, const bf16* wp_, const float* x_, const bf16* gamma_,
                                                           int N_, int K_, int M, int nblk_logits, FusedArgs a) {
     // the first 14 dwords of the arguments - everything the load-issue phase needs - arrive preloaded in SGPRs (see fused_gemv_kernel,
-    // engine.hip): w_ / wp_ = FusedArgs::w / wp, x_ = the fp32 input rows (h for the norm prologue, xin otherwise), gamma_, N_, K_
+    // engine_gemv.hip.h): w_ / wp_ = FusedArgs::w / wp, x_ = the fp32 input rows (h for the norm prologue, xin otherwise), gamma_, N_, K_
     const TLStamp tls(tl);
     constexpr bool FP8 = std::is_same<WT, fp8e4m3>::value;
     constexpr int NT = (EPI == EPI_SWIGLU) ? 2 : 1;

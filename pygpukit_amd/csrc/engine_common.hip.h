@@ -1,4 +1,4 @@
-// Argument block and prologue / epilogue codes shared by the fused decode kernels of engine.hip (GEMV, M <= 8) and
+// Argument block and prologue / epilogue codes shared by the fused decode kernels of engine_gemv.hip.h (GEMV, M <= 8) and
 // engine_batched.hip (MFMA, 3..64 sequences per launch).
 #pragma once
 
@@ -13,7 +13,7 @@
 namespace pgk {
 
 // --------------------------------------------------------------------------------------------
-// Measurement hooks shared by every decode-step kernel (engine.hip, engine_batched.hip).
+// Measurement hooks shared by every decode-step kernel (engine_gemv.hip.h, engine_attn.hip.h, engine_batched.hip; g_probe: engine.hip).
 //
 // (1) Per-launch device time: with a Probe installed and `timing` set, a launch goes through hipExtLaunchKernelGGL with
 //     a start and a stop event - the dispatch's own begin / end timestamps, the interval rocprofv3 --kernel-trace reports

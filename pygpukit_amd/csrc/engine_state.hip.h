@@ -1,0 +1,141 @@
+// The native engine's host state and the small pure helpers every engine translation unit shares.
+#pragma once
+
+#include <algorithm>
+#include <cstdlib>
+#include <type_traits>
+#include <vector>
+
+#include "engine_common.hip.h"
+
+namespace pgk {
+
+constexpr int SHORT_CTX = 512;   // contexts up to here take the whole-context attention kernels (direct batch attention); one sequence: SHORT_CTX_B1
+constexpr int SHORT_CTX_B1 = 384; // a single sequence's fused attention + o_proj kernel walks the context in chunks of 192 rows (AM_CHUNK) in EVERY one of its
+                                  // 256 workgroups: two chunks still beat the split-KV sequence (context 300: 0.616 vs 0.625 ms per step), three do not (400: 0.678 vs 0.627)
+
+struct Engine {
+    pgk_model_config_t cfg;
+    const bf16 *embed, *lm_head, *final_norm;
+    std::vector<pgk_layer_weights_t> layers;
+    int nsplit = 1, lm_blocks = 1, lm_cap = 1, log_cap = 4096;
+    bool batched_mfma = true;   // chunks of 3 and 5..16 sequences use engine_batched.hip.h (PGK_BATCHED_MFMA=0: GEMV kernels only, =2: from 3 up)
+    int batched_min = 5, batched_max = 64;   // PGK_BATCHED_MAX=16: chunks of at most 16 sequences (one weight pass per chunk), the A/B switch of the tiled kernels
+    int cu_count = 256;
+    bool short_path = true;     // contexts <= SHORT_CTX take the whole-context attention kernels (PGK_FUSED_ATTN=0: the split-KV sequence at every context)
+    int pos_hi = -1;            // host-side upper bound of the largest position the next step sees (-1: unknown); selects the sequence, see step_is_short
+    // in-graph stochastic sampling (pgk_engine_set_sampling): temperature <= 0 keeps greedy argmax
+    float sample_temperature = 0.f, sample_top_p = 1.f;
+    int sample_top_k = 0, u_cap = 0, u_alloc_rows = 0;   // u_cap: rows in use (ring length); u_alloc_rows: rows allocated
+    float* u_ring = nullptr;       // [u_cap][max_batch] uniforms, row = step counter % u_cap
+    void* sample_scratch = nullptr;   // top-k candidate keys (ops_sampling.hip), sized for max_batch rows
+    size_t sample_scratch_cap = 0;
+    int32_t* sampled = nullptr;    // [max_batch]
+    bool fused_attn = false;   // one sequence at short context: attn + o_proj in one kernel (bf16 W_o, shapes that tile)
+    bool attn_mfma = false;    // ... with Q.K^T and P.V on the matrix pipe from LDS-staged K/V (head_dim 128; PGK_ATTN_MFMA=0: the dot2 kernels); also the whole-context
+                               // batch attention while its workgroups (96 KB of LDS: one per CU) fit one round - batch x Hkv <= CUs (beyond: attn_decode_kernel, batch 64 1.258 vs 1.316 ms)
+    bool merged_oproj = false; // long contexts / fp8 W_o, one or two sequences: split-KV merge + o_proj in one kernel (PGK_MERGED_OPROJ=0: merge kernel + GEMV)
+    int moproj_rows = 32;
+    int oproj_rows = 32;       // W_o rows per workgroup on the fused path
+    // device state
+    bf16 *kcache = nullptr, *vcache = nullptr;
+    float *rope_cos = nullptr, *rope_sin = nullptr, *cur_cos = nullptr, *cur_sin = nullptr;
+    int32_t *tokens = nullptr, *positions = nullptr, *token_log = nullptr, *step_counter = nullptr;
+    bf16 *act16 = nullptr, *attnv16 = nullptr;   // batched MFMA path: bf16 hand-off of SwiGLU output and attention output
+    bf16* x16 = nullptr;                         // 17..64 sequences: the next RMSNorm's input rows in bf16 (layer 0: normalised by norm_rows_bf16; then un-normalised, written by o_proj / down)
+    float* ss_part = nullptr;                    // ... and its statistic: per-workgroup sums of squares [64][1024]
+    float *h = nullptr, *h2 = nullptr, *qkv = nullptr, *part = nullptr, *opart = nullptr, *attnv = nullptr, *act = nullptr, *logits = nullptr,
+          *amax_val = nullptr;
+    int* amax_idx = nullptr;
+    unsigned long long* clk_log = nullptr;
+    size_t kv_bytes = 0, ws_bytes = 0;
+    // fragment-major copies of the layer weights for prompts of <= 128 tokens (ops_pkgemm.hip); PGK_PACKED_PREFILL=0: none
+    struct PackedLayer { bf16 *qkv = nullptr, *o = nullptr, *gate_up = nullptr, *down = nullptr; };
+    std::vector<PackedLayer> packed;
+    bool packed_ok = false;     // the skinny-GEMM kernels of ops_pkgemm.hip can use the copy (their shape limits)
+    bool packed_have = false;   // the copy exists (w8a16 engines: also for shapes beyond those kernels - the long-prompt GEMMs read it)
+    size_t packed_bytes = 0;
+    bool packed_resid = false;      // o_proj / down_proj without K split, carrying the next RMSNorm (pkgemm_resid_nt); PGK_PACKED_RESID=0: split-K slabs + norm launches
+    float* pk_ss = nullptr;         // its sum-of-squares table [128][PK_SS_LD]
+    bf16* packed_lm = nullptr;      // fragment-major lm_head for the batched (3..64 sequences) lm_head kernels; PGK_PACKED_LMHEAD=0: none
+    float* dec_slabs = nullptr;     // 17..64 sequences on the packed kernels: split-K slabs of o_proj / down_proj [splits][M][H] (PGK_PACKED_DECODE=0: engine_batched kernels)
+    bool packed_decode = false;
+    // NVF4 engines (weight_format 3): ONE layer's linears dequantised to row-major bf16 [qkv | o | gate_up | down], refilled
+    // by the prefill in front of every layer's projections (never a copy of all layers)
+    bf16* nv_deq = nullptr;
+    // prefill workspace (grown on demand, outside capture)
+    void* pf = nullptr;
+    size_t pf_bytes = 0;
+    int32_t* pf_tokens = nullptr;
+    int pf_tokens_cap = 0;
+    // captured steps: tier 0 = the short-context sequence (span 0); the others = the split-KV sequence with its slices cut for
+    // contexts up to `span` positions (1024, 2048, ... and the cache length).  pgk_engine_replay picks per step (pick_tier).
+    struct Tier { int span = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int launches = 0; };
+    std::vector<Tier> tiers;
+    int graph_batch = 0;
+    int step_span = 0;          // the split-KV slicing of the step being enqueued (launch_attn); 0: the whole cache
+    int launches_per_step = 0;
+    std::vector<void*> allocs;
+
+    size_t kv_layer_elems() const { return (size_t)cfg.max_batch * cfg.num_kv_heads * cfg.max_seq_len * cfg.head_dim; }
+    int qkv_dim() const { return (cfg.num_heads + 2 * cfg.num_kv_heads) * cfg.head_dim; }
+};
+
+// a PGK_* switch that is on unless the environment sets it to 0
+inline bool env_on(const char* name) {
+    const char* v = getenv(name);
+    return !(v && atoi(v) == 0);
+}
+
+inline pgk_status dev_alloc(Engine* e, void** p, size_t bytes, size_t* acct) {
+    if (pgk_status r = pgk_malloc(p, bytes)) return r;
+    e->allocs.push_back(*p);
+    if (acct) *acct += bytes;
+    return PGK_OK;
+}
+
+// Which launch sequence the NEXT step takes: the short-context one while the host-side bound on the step's largest
+// position (set by pgk_engine_set_state, advanced by every step this library enqueues) stays below SHORT_CTX.  The bound
+// is a speed hint only - both sequences are correct at any context - so a caller that rewrites the device-resident
+// positions behind the library's back loses speed, never correctness; an unknown bound selects the long sequence.
+inline int short_limit(int batch) { return batch == 1 ? SHORT_CTX_B1 : SHORT_CTX; }
+inline bool step_is_short(const Engine* e, int batch) { return e->short_path && e->pos_hi >= 0 && e->pos_hi + 1 <= short_limit(batch); }
+
+// The split-KV slicing a step at the host-side position bound needs: the smallest of 1024, 2048, ... that covers the context, capped at
+// the cache length (an unknown bound: the cache length).
+inline int span_for(const Engine* e) {
+    const int cap = e->cfg.max_seq_len;
+    if (e->pos_hi < 0) return cap;
+    int span = 1024;
+    while (span < e->pos_hi + 1 && span < cap) span *= 2;
+    return span < cap ? span : cap;
+}
+
+// The captured step the next replay takes: the short-context sequence while the position bound allows it (and it was captured),
+// otherwise the split-KV tier whose slices cover the context; both kinds are correct at any context they cover.
+inline size_t pick_tier(const Engine* e) {
+    const bool has_short = !e->tiers.empty() && e->tiers[0].span == 0;
+    if (has_short && (e->tiers.size() == 1 || step_is_short(e, e->graph_batch))) return 0;
+    const int want = span_for(e);
+    for (size_t i = has_short ? 1 : 0; i < e->tiers.size(); ++i)
+        if (e->tiers[i].span >= want) return i;
+    return e->tiers.size() - 1;
+}
+
+// One decode chunk being enqueued: sequences [b0, b0 + M) of the step.  Every helper that enqueues adds to *launches at
+// the point of its launch: `counted(n, launch(...))` (n == nullptr: the prefill, which keeps no count).
+struct StepCtx { Engine* e; int b0, M; hipStream_t st; int* launches; bool short_ctx; };
+inline pgk_status counted(int* launches, pgk_status r) {
+    if (launches) ++*launches;
+    return r;
+}
+
+// Host entries the prefill and the decode step's packed path (one row per SEQUENCE) share; defined in engine_prefill.hip.
+// h[r] += the *pending split-K slabs of the projection in front of this norm (then *pending = 0), x[r] = bf16(rmsnorm(h[r]) * gamma)
+pgk_status rmsnorm_slabs(float* h, const bf16* gamma, bf16* x, int rows, int H, float eps, const float* slabs, int* pending, uint8_t* q8,
+                         float* q8s, hipStream_t st, int* launches);
+// packed path with carried norms, after attention: o_proj, gate_up, down_proj of `layer`
+pgk_status packed_mlp_carried(Engine* e, int layer, int rows, const bf16* attn16, bf16* act16, float* h, bf16* x16, int* ss_n, hipStream_t st,
+                              int* launches);
+
+}  // namespace pgk

@@ -1,5 +1,5 @@
 // Weight-streaming GEMV core for gfx950, shared by the op-level GEMV (ops_gemv.hip) and
-// the fused decode kernels (engine.hip).
+// the fused decode kernels (engine_gemv.hip.h).
 //
 //   y[m][n] = sum_k x[m][k] * W[n][k]        W is [N,K] row-major (PyTorch [out,in]), M small.
 //
