@@ -625,6 +625,30 @@ pgk_status pgk_grouped_gemm_sorted(const void* a, const int32_t* a_map, const vo
                                    int splits, const int32_t* expert_offsets, const int32_t* tiles, int T, int k, int E, int N,
                                    int K, pgk_stream s);
 
+/* ------------------------------------------------------------------------ LSTM ------ */
+/* LSTM forward over a whole sequence, one or two directions (ops_lstm.hip; reference: native/ops/nn/recurrent/lstm.inl).
+ *   g = W_ih . x_t + b_ih + b_hh + W_hh . h_{t-1}  (gate order i, f, g, o);  c_t = sigmoid(f) c_{t-1} + sigmoid(i) tanh(g_g);
+ *   h_t = sigmoid(o) tanh(c_t).
+ * x [B,S,I]; per direction W_ih [4H,I], W_hh [4H,H], b_ih / b_hh [4H], h0 / c0 [B,H] or NULL for zeros.  bwd == NULL: one
+ * direction, walked t = S-1..0 when reverse != 0, out [B,S,H], h_n / c_n [B,H].  bwd != NULL (reverse must be 0): the
+ * backward direction runs in the same launches, out [B,S,2H] with forward in [..., :H] and backward in [..., H:] written
+ * in place (leading dimension ndir * H, no concatenation pass), h_n / c_n [2,B,H].  out[:, t] is written at the position
+ * processed, so h_n is out[:, S-1] walking forwards and out[:, 0] walking backwards.
+ * dt: PGK_F32 (any I, H >= 1) or PGK_F16 / PGK_BF16 (I % 8 == 0, H % 8 == 0), shared by every tensor.  Gates, h and c are fp32
+ * for the whole sequence in every dtype: only what is returned is rounded, once.
+ * x, G (B*S*4H) and each weight must stay below 2^31 elements.
+ * Workspaces (device, 16-byte aligned, fp32): ws_gates [ndir * B * S * 4H], ws_state [3 * ndir * B * H].  The library
+ * allocates nothing, never synchronises the host and enqueues everything on `s`: 2 launches when pgk_lstm_plan says
+ * resident (1), S + 2 when it says stepped (0).  PGK_LSTM_RESIDENT=0 (read per call) forces the stepped path. */
+typedef struct {
+    const void *w_ih, *w_hh, *b_ih, *b_hh, *h0, *c0;
+} pgk_lstm_dir;
+pgk_status pgk_lstm(const void* x, const pgk_lstm_dir* fwd, const pgk_lstm_dir* bwd, void* out, void* h_n, void* c_n, float* ws_gates,
+                    float* ws_state, int B, int S, int I, int H, int reverse, pgk_dtype dt, pgk_stream s);
+/* Host only, needs no device: 1 when a call of this size runs the resident recurrence (one workgroup per direction and
+ * chunk of batch rows keeps W_hh in registers for all S steps), 0 when it runs one launch per timestep. */
+int pgk_lstm_plan(int batch, int hidden, pgk_dtype dt);
+
 /* ------------------------------------------------------------------------ RCCL ------ */
 /* New functionality (the reference is single-GPU, docs/scheduler.md:358): data-parallel batch
  * decode over one 8xMI355X node.  One process per GPU; RCCL over xGMI only for the one-time weight

@@ -16,7 +16,7 @@ from pygpukit_amd.core.device import (DeviceCapabilities, DeviceInfo, FallbackDe
                                       get_device_info, is_cuda_available)
 from pygpukit_amd.core.stream import StreamManager, default_stream  # noqa: F401,E402
 from pygpukit_amd.ops.basic import (abs, add, argmax, bias_add_inplace, clamp, cos, div, exp, gelu, layernorm,  # noqa: F401,E402,A004
-                                    linear_bias_gelu, log, matmul, max, mean, min, mul, neg, relu, rsqrt, sigmoid, sin, softmax,
+                                    linear_bias_gelu, log, lstm_bidirectional, lstm_forward, matmul, max, mean, min, mul, neg, relu, rsqrt, sigmoid, sin, softmax,
                                     sqrt, sub, sum, sum_axis, tanh, transpose, where)
 from pygpukit_amd.jit import (JITKernel, NvrtcError, NvrtcErrorCode, get_nvrtc_path, get_nvrtc_version, is_nvrtc_available,  # noqa: F401,E402
                               jit, warmup)

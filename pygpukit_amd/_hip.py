@@ -46,6 +46,10 @@ class LayerWeights(C.Structure):
                                           "mlp_norm", "w_gate_up", "s_gate_up", "w_down", "s_down")]
 
 
+class LstmDir(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "h0", "c0")]
+
+
 # name -> (argtypes); every function returns pgk_status (int) unless listed in _NON_STATUS
 _V, _I, _F, _Z, _D, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_double, C.c_int64
 _PROTOS = {
@@ -111,6 +115,7 @@ _PROTOS = {
     "pgk_alibi_add_bias": [_V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V],
     "pgk_sdpa_alibi": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
     "pgk_sdpa_alibi_fixed_cache": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _V, _V, _I, _V],
+    "pgk_lstm": [_V, C.POINTER(LstmDir), C.POINTER(LstmDir), _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _V],
     "pgk_engine_create": [C.POINTER(ModelConfig), _V, _V, _V, C.POINTER(LayerWeights), c_void_pp],
     "pgk_engine_destroy": [_V], "pgk_engine_bytes": [_V, C.POINTER(_Z), C.POINTER(_Z)],
     "pgk_engine_prefill": [_V, _I, c_i32_p, _I, _I, _V, C.POINTER(_F), _V],
@@ -141,6 +146,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_grouped_gemm_sorted_splits": ([_I, _I, _I, _I, _I], C.c_int),
                "pgk_gemv_nvf4_workspace_bytes": ([_I, _I], C.c_size_t),
                "pgk_gemm_nvf4_workspace_bytes": ([_I, _I, _I], C.c_size_t),
+               "pgk_lstm_plan": ([_I, _I, _I], C.c_int),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}

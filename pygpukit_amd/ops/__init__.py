@@ -18,7 +18,7 @@ from pygpukit_amd.ops.matmul import (batched_matmul, gemm_w8a16_init_lut, gemv_b
 from pygpukit_amd.ops.moe import (moe_compute_permutation, moe_expand_expert_offsets, moe_gather, moe_scatter, moe_softmax_topk,
                                   moe_topk_softmax, moe_topk_with_indices)
 from pygpukit_amd.ops.nn import (fa3_fp8_available, get_sm_version, quantize_fp8_per_head, sdpa_causal_fp8, sdpa_causal_fp8_strided,
-                                bias_add_inplace, geglu, gelu, glu_packed, layernorm, relu2, rmsnorm, rmsnorm_residual, rope_inplace,
+                                bias_add_inplace, geglu, gelu, glu_packed, layernorm, lstm_bidirectional, lstm_forward, relu2, rmsnorm, rmsnorm_residual, rope_inplace,
                                 rope_inplace_f32table, sdpa_causal, sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr,
                                 sdpa_causal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh)
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis

@@ -7,7 +7,7 @@ from pygpukit_amd.ops.matmul import (batched_matmul, gemm_w8a16_init_lut, gemv_b
                                     gemv_fp8_bf16_batched, linear_bias_gelu, matmul, matmul_nt, transpose, w8a16_gemm,
                                     w8a16_gemm_nk, w8a16_gemm_sm120)
 from pygpukit_amd.ops.matmul.fp8 import *  # noqa: F401,F403
-from pygpukit_amd.ops.nn import (bias_add_inplace, geglu, gelu, glu_packed, layernorm, relu2, rmsnorm, rmsnorm_residual, rope_inplace,
+from pygpukit_amd.ops.nn import (bias_add_inplace, geglu, gelu, glu_packed, layernorm, lstm_bidirectional, lstm_forward, relu2, rmsnorm, rmsnorm_residual, rope_inplace,
                                 rope_inplace_f32table, sdpa_causal, sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr,
                                 sdpa_causal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh)
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis
