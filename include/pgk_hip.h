@@ -384,6 +384,17 @@ pgk_status pgk_sdpa_causal(const void* q, const void* k, const void* v, void* ou
                            int kv_len, int d, float scale, int64_t q_stride_h, int64_t q_stride_s,
                            int64_t kv_stride_h, int64_t kv_stride_s, int64_t o_stride_h, int64_t o_stride_s,
                            pgk_dtype dt, pgk_stream s);
+/* [build-defined: the reference's encoders run batched_matmul -> softmax -> batched_matmul]  sdpa_noncausal:
+ * out[h][i] = softmax_j(q[h][i] . k[h / rep][j] * scale, over ALL j < kv_len) . v[h / rep] - no mask, and no relation
+ * between q_len and kv_len (cross-attention: few queries, many keys).  Arguments as pgk_sdpa_causal.  f16 / bf16 with
+ * d 64 or 128, 16-byte aligned q / k / v, 8-byte aligned out, q / kv strides multiples of 8 and out strides multiples of 4
+ * elements run the MFMA flash kernel (FlashFull policy, every q_len; V^T and split workspaces from the pool); anything
+ * else - float32 included - and PYGPUKIT_FLASH_ATTENTION=0 run the one-workgroup-per-row fallback (kv_len <= 15360,
+ * q_len <= 65535, PGK_ERR_UNSUPPORTED beyond). */
+pgk_status pgk_sdpa_noncausal(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len,
+                              int kv_len, int d, float scale, int64_t q_stride_h, int64_t q_stride_s,
+                              int64_t kv_stride_h, int64_t kv_stride_s, int64_t o_stride_h, int64_t o_stride_s,
+                              pgk_dtype dt, pgk_stream s);
 /* sdpa_causal_fp8 (src/pygpukit/ops/nn/attention.py:238-347; flash_attention_3_fp8_sm120.cuh): the same op with the
  * first product in fp8.  Q (per query head) and K (per kv head) are quantised to e4m3 with one power-of-two scale
  * per head (pgk_quantize_fp8_per_head), s = scale * 2^(eq+ek) * sum_d q8 * k8 in fp32, softmax in fp32, P.V with
@@ -648,6 +659,27 @@ pgk_status pgk_lstm(const void* x, const pgk_lstm_dir* fwd, const pgk_lstm_dir* 
 /* Host only, needs no device: 1 when a call of this size runs the resident recurrence (one workgroup per direction and
  * chunk of batch rows keeps W_hh in registers for all S steps), 0 when it runs one launch per timestep. */
 int pgk_lstm_plan(int batch, int hidden, pgk_dtype dt);
+
+/* ---------------------------------------------------------------------- conv1d ------ */
+/* conv1d (ops_conv.hip; reference: src/pygpukit/ops/conv.py, native/ops/conv/conv1d_kernels.cuh):
+ *   out[b][m][n] = bias[m] + sum_{c < C_in, t < K} weight[m][c][t] * x[b][c][n * stride + t - padding]   (zeros outside [0, L))
+ * x [B,C_in,L], weight [C_out,C_in,K], bias [C_out] or NULL, L_out = (L + 2 * padding - K) / stride + 1 >= 1; any sizes.
+ * [build-defined] epilogue, on the fp32 accumulator, in this order: + bias; act (0 none, 1 tanh GELU - the gelu op's device
+ * function); layout [B,C_out,L_out] or, with channels_last, [B,L_out,C_out]; + add[L_out][C_out] (same dtype, may be NULL,
+ * needs channels_last); one rounding to dt.
+ * bf16 / f16 run an implicit GEMM on the 32x32x16 MFMA when pgk_conv1d_plan says 1; it reads the weight as the image
+ * [K][C_out padded to 64][C_in padded to 32] that pgk_conv1d_pack_weight writes: packed_weight (16-byte aligned, of
+ * pgk_conv1d_packed_elems elements) or, when NULL, packed per call into stream-ordered pool workspace.  float32, and 16-bit
+ * calls with plan 0 or a misaligned packed_weight, run the tiled FMA kernel on `weight` itself.  One launch (+ the pack
+ * pre-pass), never synchronises the host, everything on `s`.  B <= 65535, L + 2 * padding < 2^31. */
+pgk_status pgk_conv1d(const void* x, const void* weight, const void* packed_weight, const void* bias, const void* add, void* out,
+                      int B, int C_in, int C_out, int L, int K, int stride, int padding, int act, int channels_last, pgk_dtype dt,
+                      pgk_stream s);
+/* Host only, needs no device: 1 = MFMA kernel (16-bit dtype, (63 * stride + K + 64 * K) * 80 bytes of LDS <= 64 KiB,
+ * PGK_CONV_MFMA != "0", read per call), 0 = FMA kernel, -1 = invalid shape or dtype. */
+int pgk_conv1d_plan(int C_in, int C_out, int L, int K, int stride, int padding, pgk_dtype dt);
+size_t pgk_conv1d_packed_elems(int C_in, int C_out, int K);
+pgk_status pgk_conv1d_pack_weight(const void* weight, void* packed, int C_in, int C_out, int K, pgk_dtype dt, pgk_stream s);
 
 /* ------------------------------------------------------------------------ RCCL ------ */
 /* New functionality (the reference is single-GPU, docs/scheduler.md:358): data-parallel batch

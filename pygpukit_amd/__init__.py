@@ -20,4 +20,5 @@ from pygpukit_amd.ops.basic import (abs, add, argmax, bias_add_inplace, clamp, c
                                     sqrt, sub, sum, sum_axis, tanh, transpose, where)
 from pygpukit_amd.jit import (JITKernel, NvrtcError, NvrtcErrorCode, get_nvrtc_path, get_nvrtc_version, is_nvrtc_available,  # noqa: F401,E402
                               jit, warmup)
-from pygpukit_amd.ops.nn.attention import fa3_fp8_available, get_sm_version, sdpa_causal_fp8  # noqa: F401,E402
+from pygpukit_amd.ops.nn.attention import (fa3_fp8_available, get_sm_version, sdpa_causal_fp8, sdpa_noncausal,  # noqa: F401,E402
+                                          sdpa_noncausal_strided)

@@ -1,0 +1,8 @@
+"""Whisper encoder with the reference's API (src/pygpukit/asr/whisper): WhisperConfig, WhisperWeights, WhisperEncoderLayer,
+WhisperEncoder, create_encoder."""
+
+from pygpukit_amd.asr.whisper.config import WHISPER_CONFIGS, WhisperConfig
+from pygpukit_amd.asr.whisper.encoder import WhisperEncoder, WhisperEncoderLayer, create_encoder
+from pygpukit_amd.asr.whisper.loader import WhisperWeights
+
+__all__ = ["WhisperConfig", "WHISPER_CONFIGS", "WhisperWeights", "WhisperEncoder", "WhisperEncoderLayer", "create_encoder"]

@@ -50,7 +50,9 @@ __device__ __forceinline__ long long irope_position(const void* positions, int i
 // scale for every row.  FlashIrope: sdpa_irope (ops_llama4.hip), the row's temperature folded into the Q premultiply and
 // a free mask offset.  FlashAlibi: sdpa_alibi (ops_posenc.hip), mask as FlashPlain, the score of (row i, key j) of query head h
 // gets -slopes[h] * (kv_len - q_len + i - j): the MFMA accumulators of Q.K^T start at that bias instead of at zero.
+// FlashFull: sdpa_noncausal (ops_attention.hip), every key visible to every query row, kv_len and q_len unrelated.
 struct FlashPlain {};
+struct FlashFull {};        // sdpa_noncausal: no mask but the end of the keys (mask offset kv_len)
 struct FlashIrope {
     const void* positions;   // [q_len] int64 or int32
     float attn_scale, floor_scale;

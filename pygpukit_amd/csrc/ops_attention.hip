@@ -315,7 +315,8 @@ __global__ __launch_bounds__(64 * NW) void attn_short_kernel(const bf16* q, cons
 }
 
 // fp32 / odd head_dim fallback: one workgroup per (head, query row), scores kept in LDS.
-template <class T>
+// CAUSAL = false is sdpa_noncausal's fallback: every row attends all kv_len keys.
+template <class T, bool CAUSAL = true>
 __global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k, const T* v, T* out, int hq, int hkv,
                                                          int q_len, int kv_len, int d, float scale, AttnStrides sd) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k,
     __shared__ float red[16];
     const int head = blockIdx.x, qi = blockIdx.y, kvh = head / (hq / hkv);
     const T* qr = q + (size_t)head * sd.qh + (size_t)qi * sd.qs;
-    const int n_att = min(kv_len, (kv_len - q_len) + qi + 1);
+    const int n_att = CAUSAL ? min(kv_len, (kv_len - q_len) + qi + 1) : kv_len;
     float mx = -INFINITY;
     for (int p = threadIdx.x; p < n_att; p += blockDim.x) {
         const T* kr = k + (size_t)kvh * sd.kh + (size_t)p * sd.ks;
@@ -454,6 +455,33 @@ static pgk_status sdpa_dispatch(const void* q, const void* k, const void* v, voi
     return PGK_OK;
 }
 
+pgk_status flash_prefill_full(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
+                              float scale, long long qh, long long qs, long long kh, long long ks, long long oh, long long os, int dt16,
+                              hipStream_t st);
+
+// sdpa_noncausal: the second-generation flash kernel with the FlashFull policy at EVERY q_len (the first-generation and
+// one-tile kernels stay causal-only); float32, other head dims, misaligned buffers and PYGPUKIT_FLASH_ATTENTION=0 take
+// the non-causal form of the one-workgroup-per-row fallback.
+template <class T>
+static pgk_status sdpa_full_dispatch(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len,
+                                     int d, float scale, const AttnStrides& sd, hipStream_t st) {
+    if constexpr (!std::is_same<T, float>::value) {
+        const bool gen2_ok = (d == 64 || d == 128) && aligned16(q) && aligned16(k) && aligned16(v) && sd.qs % 8 == 0 && sd.ks % 8 == 0 &&
+                             sd.qh % 8 == 0 && sd.kh % 8 == 0 && !flash_attention_off() && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 &&
+                             sd.os % 4 == 0 && sd.oh % 4 == 0;
+        if (gen2_ok)
+            return flash_prefill_full(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd.qh, sd.qs, sd.kh, sd.ks, sd.oh, sd.os,
+                                      std::is_same<T, f16>::value ? 1 : 0, st);
+    }
+    const size_t lds = (size_t)kv_len * 4;
+    if (lds > 60 * 1024) return set_error(PGK_ERR_UNSUPPORTED, "sdpa: fallback kernel supports kv_len <= 15360 (got %d)", kv_len);
+    if (q_len > 65535) return set_error(PGK_ERR_UNSUPPORTED, "sdpa_noncausal: fallback kernel supports q_len <= 65535 (got %d)", q_len);
+    dim3 grid(hq, q_len);
+    sdpa_naive_kernel<T, false><<<grid, 256, lds, st>>>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, d, scale, sd);
+    PGK_CHECK_HIP(hipGetLastError());
+    return PGK_OK;
+}
+
 }  // namespace pgk
 
 using namespace pgk;
@@ -471,6 +499,21 @@ pgk_status pgk_sdpa_causal(const void* q, const void* k, const void* v, void* ou
     const AttnStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
     hipStream_t st = resolve_stream(s);
     PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_causal", return (sdpa_dispatch<T>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, st)));
+    return PGK_OK;
+}
+
+pgk_status pgk_sdpa_noncausal(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
+                              float scale, int64_t q_stride_h, int64_t q_stride_s, int64_t kv_stride_h, int64_t kv_stride_s,
+                              int64_t o_stride_h, int64_t o_stride_s, pgk_dtype dt, pgk_stream s) {
+    PGK_REQUIRE(q && k && v && out, "pgk_sdpa_noncausal: null pointer");
+    PGK_REQUIRE(hq > 0 && hkv > 0 && hq % hkv == 0, "pgk_sdpa_noncausal: n_heads mismatch (Hq=%d, Hkv=%d)", hq, hkv);
+    PGK_REQUIRE(q_len > 0 && kv_len > 0 && d > 0, "pgk_sdpa_noncausal: bad shape q_len=%d kv_len=%d D=%d", q_len, kv_len, d);
+    PGK_REQUIRE(q_stride_h >= 0 && q_stride_s >= 0 && kv_stride_h >= 0 && kv_stride_s >= 0 && o_stride_h >= 0 && o_stride_s >= 0,
+                "pgk_sdpa_noncausal: negative stride");
+    if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
+    const AttnStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
+    hipStream_t st = resolve_stream(s);
+    PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_noncausal", return (sdpa_full_dispatch<T>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, st)));
     return PGK_OK;
 }
 

@@ -24,11 +24,10 @@ __device__ __forceinline__ float binop(float a, float b, int op) {
     }
 }
 
-// gelu: tanh form with the reference's constants (native/ops/nn/activation_kernels.cuh:110-171)
 __device__ __forceinline__ float act_fn(float x, int act) {
     switch (act) {
         case 0: return x / (1.0f + expf(-x));                                              // silu
-        case 1: return x * 0.5f * (1.0f + tanhf(0.7978845608f * (x + 0.044715f * x * x * x)));  // gelu
+        case 1: return gelu_tanh(x);                                                        // gelu (pgk_device.hip.h)
         case 2: return 1.0f / (1.0f + expf(-x));                                           // sigmoid
         case 3: return tanhf(x);
         case 4: { float r = fmaxf(x, 0.f); return r * r; }                                    // relu2

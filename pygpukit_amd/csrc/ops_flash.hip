@@ -21,6 +21,8 @@
 // row's temperature joins the Q premultiply and the mask offset is an argument, kv_pos <= causal_offset + q_pos.
 // With a FlashAlibi it is sdpa_alibi (pgk_sdpa_alibi, ops_posenc.hip): the accumulators of S^T start at the ALiBi bias
 // -slope[head] * (mask_off + q_pos - kv_pos), in the exp2 domain, instead of at zero - no extra pass over the scores.
+// With a FlashFull it is sdpa_noncausal (pgk_sdpa_noncausal, ops_attention.hip): the mask offset is kv_len, so no key is
+// ever above a diagonal; q_len may be smaller or larger than kv_len and any q_len >= 1 takes this kernel.
 
 #include "flash_common.hip.h"
 
@@ -37,6 +39,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
                                                               FlashSplit sp, X ex) {
     constexpr bool IROPE = std::is_same<X, FlashIrope>::value;
     constexpr bool ALIBI = std::is_same<X, FlashAlibi>::value;
+    constexpr bool FULL = std::is_same<X, FlashFull>::value;
     constexpr int NC = D / 8;            // 16-byte chunks per K row
     constexpr int KS = D / 16;           // k-steps of Q.K^T
     constexpr int DT = D / 32;           // 32-row tiles of O^T
@@ -65,6 +68,9 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
     const int qw0 = qt * FL_BQ + wid * 32;          // first query row of this wave
     int mask_off = kv_len - q_len;
     if constexpr (IROPE) mask_off = ex.causal_offset;
+    // no diagonal: with the offset at kv_len, kv_end, live() and lim admit every key of every row and only the ragged last
+    // tile takes the mask branch (for the keys past kv_len)
+    if constexpr (FULL) mask_off = kv_len;
     const int causal_off = mask_off;
     const T* qh = q + (size_t)head * sd.qh;
     const T* kh = k + (size_t)kvh * sd.kh;
@@ -436,6 +442,23 @@ pgk_status flash_prefill_alibi(const void* q, const void* k, const void* v, cons
     if (d == 128) PGK_ALIBI_CASE(f16, 128);
     PGK_ALIBI_CASE(f16, 64);
 #undef PGK_ALIBI_CASE
+}
+
+// entry used by pgk_sdpa_noncausal (ops_attention.hip), which has checked the arguments.  Every KV run of every query tile is
+// live, so the split heuristic sees all kv_len keys.
+pgk_status flash_prefill_full(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
+                              float scale, long long qh, long long qs, long long kh, long long ks, long long oh, long long os, int dt16,
+                              hipStream_t st) {
+    const FlashStrides sd{qh, qs, kh, ks, oh, os};
+#define PGK_FULL_CASE(T, DD) \
+    return flash_launch<T, DD, FlashFull>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st, nullptr, nullptr, FlashFull{}, kv_len)
+    if (dt16 == 0) {
+        if (d == 128) PGK_FULL_CASE(bf16, 128);
+        PGK_FULL_CASE(bf16, 64);
+    }
+    if (d == 128) PGK_FULL_CASE(f16, 128);
+    PGK_FULL_CASE(f16, 64);
+#undef PGK_FULL_CASE
 }
 
 // engine entry (fp8 x fp8 prefill, bf16, head_dim 128, q_len > 128): causal attention whose result leaves as the o_proj's fp8

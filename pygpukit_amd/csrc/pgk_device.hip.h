@@ -39,6 +39,10 @@ template <> __device__ __forceinline__ float from_f<float>(float f) { return f; 
 template <> __device__ __forceinline__ f16 from_f<f16>(float f) { return f16{static_cast<_Float16>(f)}; }
 template <> __device__ __forceinline__ bf16 from_f<bf16>(float f) { return bf16{f_to_bf16_bits(f)}; }
 
+// tanh GELU with the reference's constants (native/ops/nn/activation_kernels.cuh:110-171): the gelu op and every fused
+// epilogue (conv1d) call this one function, so a fused result equals the op applied to the same fp32 value bit for bit
+__device__ __forceinline__ float gelu_tanh(float x) { return x * 0.5f * (1.0f + tanhf(0.7978845608f * (x + 0.044715f * x * x * x))); }
+
 // ---- 16-byte vectors ----------------------------------------------------------------------
 // Vec<T>::N elements of T in one 16-byte access: 4 x fp32 or 8 x 16-bit.
 template <class T> struct Vec {

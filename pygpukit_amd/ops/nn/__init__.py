@@ -2,7 +2,8 @@ from pygpukit_amd.ops.nn.activation import gelu, relu2, sigmoid, silu, tanh
 from pygpukit_amd.ops.nn.alibi import sdpa_alibi, sdpa_alibi_fixed_cache, sdpa_alibi_fixed_cache_ptr, sdpa_alibi_strided
 from pygpukit_amd.ops.nn.attention import (fa3_fp8_available, get_sm_version, quantize_fp8_per_head, sdpa_causal,
                                           sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr, sdpa_causal_fp8,
-                                          sdpa_causal_fp8_strided, sdpa_causal_strided)
+                                          sdpa_causal_fp8_strided, sdpa_causal_strided, sdpa_noncausal,
+                                          sdpa_noncausal_strided)
 from pygpukit_amd.ops.nn.fused import geglu, glu_packed, rmsnorm_residual, swiglu
 from pygpukit_amd.ops.nn.llama4 import (irope_scale_q, l2norm, llama4_qk_norm_cache_write, llama4_qk_norm_cache_write_ptr,
                                         sdpa_irope, sdpa_irope_fixed_cache, sdpa_irope_fixed_cache_ptr, sdpa_irope_strided)
@@ -20,4 +21,4 @@ __all__ = ["gelu", "silu", "sigmoid", "tanh", "relu2", "sdpa_causal", "sdpa_caus
            "llama4_qk_norm_cache_write_ptr", "sdpa_irope_fixed_cache", "sdpa_irope_fixed_cache_ptr", "rope_init_ntk_aware",
            "rope_init_yarn", "rope_init_linear", "pope_init_encoding", "pope_inplace", "alibi_init_slopes", "alibi_compute_bias",
            "alibi_add_bias", "sdpa_alibi", "sdpa_alibi_strided", "sdpa_alibi_fixed_cache", "sdpa_alibi_fixed_cache_ptr",
-           "lstm_forward", "lstm_bidirectional", "lstm_plan"]
+           "lstm_forward", "lstm_bidirectional", "lstm_plan", "sdpa_noncausal", "sdpa_noncausal_strided"]

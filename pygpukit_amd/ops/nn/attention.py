@@ -47,6 +47,33 @@ def sdpa_causal_strided(q: GPUArray, k: GPUArray, v: GPUArray, out: GPUArray, hq
          kv_strides[0], kv_strides[1], o_strides[0], o_strides[1], q.dtype.code, None)
 
 
+def sdpa_noncausal(Q: GPUArray, K: GPUArray, V: GPUArray, scale: float = 0.0, *, out: GPUArray | None = None) -> GPUArray:
+    """[build-defined] softmax(Q K^T * scale) V with every key visible to every query: Q [Hq, q_len, D], K / V [Hkv, kv_len, D],
+    any q_len and kv_len >= 1 (encoders, cross-attention); scale <= 0 -> 1/sqrt(head_dim).  bfloat16 / float16 with head_dim 64 or
+    128 run the MFMA flash kernel at every q_len; float32, other head dims and PYGPUKIT_FLASH_ATTENTION=0 the fallback."""
+    hq, hkv, q_len, kv_len, d = _check_qkv(Q, K, V, "sdpa_noncausal")
+    if min(q_len, kv_len, d) < 1:
+        raise ValueError(f"sdpa_noncausal: empty dimension, Q {Q.shape} K {K.shape}")
+    o = check_out(out, (hq, q_len, d), Q.dtype, "sdpa_noncausal")
+    call("pgk_sdpa_noncausal", Q._p, K._p, V._p, o._p, hq, hkv, q_len, kv_len, d, float(scale), q_len * d, d, kv_len * d, d,
+         q_len * d, d, Q.dtype.code, None)
+    return o
+
+
+def sdpa_noncausal_strided(q: GPUArray, k: GPUArray, v: GPUArray, out: GPUArray, hq: int, hkv: int, q_len: int, kv_len: int,
+                           d: int, q_strides, kv_strides, o_strides, scale: float = 0.0) -> None:
+    """sdpa_noncausal on [S,H,D]-layout (or any head/row-strided) buffers: strides are (head, row) in elements, so the
+    [S, 3*H*D] output of a fused QKV projection is read in place."""
+    if hq < 1 or hkv < 1 or hq % hkv:
+        raise ValueError("sdpa_noncausal_strided: n_heads mismatch")
+    if min(q_len, kv_len, d) < 1:
+        raise ValueError(f"sdpa_noncausal_strided: needs q_len, kv_len, head_dim >= 1, got {q_len}, {kv_len}, {d}")
+    if any(int(x) < 0 for x in (*q_strides, *kv_strides, *o_strides)):
+        raise ValueError("sdpa_noncausal_strided: strides must be non-negative")
+    call("pgk_sdpa_noncausal", q._p, k._p, v._p, out._p, hq, hkv, q_len, kv_len, d, float(scale), q_strides[0], q_strides[1],
+         kv_strides[0], kv_strides[1], o_strides[0], o_strides[1], q.dtype.code, None)
+
+
 def get_sm_version() -> int:
     """The reference returns the CUDA SM version (120 for SM120).  Here the number is the gfx target of the current
     device - the decimal digits after "gfx" in its architecture name: 950 on MI355X (gfx950)."""
