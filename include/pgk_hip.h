@@ -681,6 +681,33 @@ int pgk_conv1d_plan(int C_in, int C_out, int L, int K, int stride, int padding, 
 size_t pgk_conv1d_packed_elems(int C_in, int C_out, int K);
 pgk_status pgk_conv1d_pack_weight(const void* weight, void* packed, int C_in, int C_out, int K, pgk_dtype dt, pgk_stream s);
 
+/* [build-defined] ln_linear: the linear layer of a LayerNorm transformer's one-token step in one launch (ops_lnlinear.hip).
+ *   out[m, n] = act( LN(x[m, :]; gamma, beta, eps) . w[n, :] + bias[n] ) + residual[m, n]
+ * w is [n, k] (PyTorch layout), m = 1..8, every operand of dtype dt (f32 / f16 / bf16).  gamma == NULL: no norm (beta must then be
+ * NULL too); bias and residual may be NULL; act 0 = none, 1 = the gelu op's tanh GELU.  residual may alias out; x may not
+ * (PGK_ERR_INVALID).  LayerNorm uses the population variance, as pgk_layernorm.  Statistics, the normalised row, accumulation and
+ * the epilogue are fp32 with ONE rounding at the store: in the 16-bit dtypes the normalised activations are never rounded to 16
+ * bits when the m * k fp32 image fits in 64 KB of LDS; no-norm calls beyond that hold the rows in dt as pgk_gemv does; k % 8 != 0,
+ * operands off 16-byte alignment and norm calls beyond the budget run a generic kernel (one wave per output).  No allocation, no
+ * host synchronisation, capturable. */
+pgk_status pgk_ln_linear(const void* x, const void* gamma, const void* beta, const void* w, const void* bias, const void* residual,
+                         void* out, int m, int k, int n, float eps, int act, pgk_dtype dt, pgk_stream s);
+/* Host only, needs no device: the kernel a pgk_ln_linear call takes.  0 = generic, 1 = fast path on an fp32 image, 2 = fast path on
+ * a dt image (no norm, fp32 image over 64 KB), -1 = invalid shape or dtype.  `aligned`: x, w (and gamma, beta) are 16-byte aligned.
+ * PGK_LN_LINEAR_GENERIC=1 (read per call) forces 0.  k is a runtime argument of every kernel: there is no k specialisation. */
+int pgk_ln_linear_plan(int m, int k, int n, pgk_dtype dt, int norm, int aligned);
+/* The same kernel at m = 1, n = 3 * heads * head_dim on the fused q | k | v weight, with a scatter epilogue: rows [0, d) go to
+ * q_out[d], rows [d, 2d) to k_cache[h][pos][:] and rows [2d, 3d) to v_cache[h][pos][:] (d = heads * head_dim, caches
+ * [heads, max_seq, head_dim]).  pos = pos_buf[0] when pos_buf != NULL, clamped to the cache on the device; else h_pos, which must
+ * lie in [0, max_seq).  The stored values are bit-identical to pgk_ln_linear followed by two pgk_kv_cache_write calls. */
+pgk_status pgk_ln_linear_qkv_cache(const void* x, const void* gamma, const void* beta, const void* w_qkv, const void* bias_qkv,
+                                   void* q_out, void* k_cache, void* v_cache, int k, int heads, int head_dim, int max_seq, float eps,
+                                   int h_pos, const int32_t* pos_buf, pgk_dtype dt, pgk_stream s);
+/* out[hidden] = tok_table[state[0]][:] + pos_table[state[1]][:]: one fp32 add, one rounding.  state is a device int32[2]; both
+ * indices are clamped on the device to [0, vocab) / [0, max_pos). */
+pgk_status pgk_embed_token_position(const void* tok_table, const void* pos_table, void* out, int hidden, int vocab, int max_pos,
+                                    const int32_t* state, pgk_dtype dt, pgk_stream s);
+
 /* ------------------------------------------------------------------------ RCCL ------ */
 /* New functionality (the reference is single-GPU, docs/scheduler.md:358): data-parallel batch
  * decode over one 8xMI355X node.  One process per GPU; RCCL over xGMI only for the one-time weight

@@ -107,6 +107,9 @@ _PROTOS = {
     "pgk_sdpa_noncausal": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
     "pgk_conv1d": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V],
     "pgk_conv1d_pack_weight": [_V, _V, _I, _I, _I, _I, _V],
+    "pgk_ln_linear": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _F, _I, _I, _V],
+    "pgk_ln_linear_qkv_cache": [_V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _F, _I, _V, _I, _V],
+    "pgk_embed_token_position": [_V, _V, _V, _I, _I, _I, _V, _I, _V],
     "pgk_sdpa_causal_fp8": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
     "pgk_quantize_fp8_per_head": [_V, _V, _V, _I, _I, _I, _I64, _I64, _I, _V], "pgk_device_arch": [C.POINTER(_I)],
     "pgk_l2norm": [_V, _V, _I, _I, _F, _I, _V], "pgk_irope_scale_q": [_V, _V, _V, _I, _I, _I, _F, _F, _I, _I, _V],
@@ -151,6 +154,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_gemm_nvf4_workspace_bytes": ([_I, _I, _I], C.c_size_t),
                "pgk_lstm_plan": ([_I, _I, _I], C.c_int),
                "pgk_conv1d_plan": ([_I, _I, _I, _I, _I, _I, _I], C.c_int), "pgk_conv1d_packed_elems": ([_I, _I, _I], C.c_size_t),
+               "pgk_ln_linear_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}

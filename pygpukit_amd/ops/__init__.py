@@ -21,7 +21,8 @@ from pygpukit_amd.ops.moe import (moe_compute_permutation, moe_expand_expert_off
 from pygpukit_amd.ops.nn import (fa3_fp8_available, get_sm_version, quantize_fp8_per_head, sdpa_causal_fp8, sdpa_causal_fp8_strided,
                                 bias_add_inplace, geglu, gelu, glu_packed, layernorm, lstm_bidirectional, lstm_forward, relu2, rmsnorm, rmsnorm_residual, rope_inplace,
                                 rope_inplace_f32table, sdpa_causal, sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr,
-                                sdpa_causal_strided, sdpa_noncausal, sdpa_noncausal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh)
+                                sdpa_causal_strided, sdpa_noncausal, sdpa_noncausal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh,
+                                embed_token_position_ptr, ln_linear, ln_linear_plan, ln_linear_qkv_cache_ptr)
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis
 from pygpukit_amd.ops.unary import abs, cos, exp, log, neg, relu, rsqrt, sin, sqrt
 from pygpukit_amd.ops.paged import (allocate_kv_cache, argmax_sample, check_eos, compute_cumsum, copy_to_paged_cache, gather_embeddings,

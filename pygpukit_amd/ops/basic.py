@@ -9,7 +9,8 @@ from pygpukit_amd.ops.matmul import (batched_matmul, gemm_w8a16_init_lut, gemv_b
 from pygpukit_amd.ops.matmul.fp8 import *  # noqa: F401,F403
 from pygpukit_amd.ops.nn import (bias_add_inplace, geglu, gelu, glu_packed, layernorm, lstm_bidirectional, lstm_forward, relu2, rmsnorm, rmsnorm_residual, rope_inplace,
                                 rope_inplace_f32table, sdpa_causal, sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr,
-                                sdpa_causal_strided, sdpa_noncausal, sdpa_noncausal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh)
+                                sdpa_causal_strided, sdpa_noncausal, sdpa_noncausal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh,
+                                embed_token_position_ptr, ln_linear, ln_linear_plan, ln_linear_qkv_cache_ptr)
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis
 from pygpukit_amd.ops.unary import abs, cos, exp, log, neg, relu, rsqrt, sin, sqrt
 from pygpukit_amd.ops.sampling import (sample_greedy, sample_multinomial, sample_token_gpu, sample_topk, sample_topk_to_buf_ptr,
