@@ -708,6 +708,37 @@ pgk_status pgk_ln_linear_qkv_cache(const void* x, const void* gamma, const void*
 pgk_status pgk_embed_token_position(const void* tok_table, const void* pos_table, void* out, int hidden, int vocab, int max_pos,
                                     const int32_t* state, pgk_dtype dt, pgk_stream s);
 
+/* ------------------------------------------------------------------------ audio ------ */
+/* ops.audio (pygpukit_amd/csrc/ops_audio.hip).  Everything is float32 up to the final cast.
+ * pgk_audio_log_mel: samples [batch][n] -> log-mel in ONE launch: reflect centre padding by index arithmetic (center != 0, pad =
+ * n_fft / 2), framing, window [n_fft], the DFT as an f32 MFMA GEMM against dft_table, re^2 + im^2, the filterbank mel_fb
+ * [n_mels][n_fft / 2 + 1] over each row's span fb_span[2 m] .. fb_span[2 m + 1] (inclusive, first > last for an empty row), the
+ * logarithm (log_mode 0: log10(max(m, eps)) with log_floor = log10(eps) rounded once by the caller; 1: ln(m + eps); 2: none), (x + offset) *
+ * scale, the cast to out_dt.  dft_table is [2][n_fft][nbp] floats, nbp = n_fft / 2 + 1 rounded up to 32, zeros in the padding:
+ * cos(2 pi k bin / n_fft) at [0][k][bin] and -sin at [1][k][bin].  out is [batch][n_mels][n_frames], or [batch][n_frames][n_mels]
+ * when frames_last; n_frames may be less than the signal holds (drop_last_frame).  n_fft even in [16, 2048], 1 <= hop <= n_fft,
+ * n_mels in [1, 256].  use_range: x = max(x, max over the whole call - range) before the affine; the kernel then stores float32,
+ * folds the maximum into one device word and a second kernel finishes (one stream-ordered workspace allocation). */
+pgk_status pgk_audio_log_mel(const float* samples, const float* window, const float* dft_table, const float* mel_fb, const int32_t* fb_span,
+                             void* out, int batch, long long n, int n_fft, int hop, int center, int n_mels, int n_frames, int log_mode, float eps,
+                             float log_floor, float offset, float scale, int use_range, float range, int frames_last, pgk_dtype out_dt,
+                             pgk_stream s);
+/* Host only: 1 = the workgroup's sample span sits in LDS, 0 = samples are read from global memory (the span, the window and the
+ * power tile exceed the LDS budget, or PGK_AUDIO_LDS=0), -1 = invalid.  stage 0 = log-mel, 1 = stft. */
+int pgk_audio_log_mel_plan(int n_fft, int hop, int stage);
+/* The same kernel stopped after the DFT: out [n_frames][n_fft / 2 + 1][2] float32, re and im interleaved. */
+pgk_status pgk_audio_stft(const float* samples, const float* window, const float* dft_table, float* out, long long n, int n_fft, int hop,
+                          int center, pgk_stream s);
+/* n outputs, one launch.  op 0: int16 -> x / 32768; 1: interleaved L R pairs -> (l + r) * 0.5; 2: (re, im) pairs -> re^2 + im^2;
+ * 3: its square root; 4: ln(x + eps); 5: 10 log10(x + eps). */
+pgk_status pgk_audio_map(const void* in, float* out, size_t n, int op, float eps, pgk_stream s);
+/* In place, one launch (one workgroup).  mode 0: x / max|x| when max|x| > 1e-8; mode 1: x * target_rms / rms when rms > 1e-8. */
+pgk_status pgk_audio_normalize(float* x, size_t n, int mode, double target_rms, pgk_stream s);
+/* n_out = n * dst / src.  ratio >= 2 (src = ratio * dst): out[i] = sum_t taps[t] * x[i * ratio - n_taps / 2 + t], zeros outside the
+ * signal.  ratio 0: linear interpolation at i * src / dst, position and fraction computed in 64-bit integers. */
+pgk_status pgk_audio_resample(const float* x, float* out, const float* taps, long long n, long long n_out, int ratio, int n_taps, int src, int dst,
+                              pgk_stream s);
+
 /* ------------------------------------------------------------------------ RCCL ------ */
 /* New functionality (the reference is single-GPU, docs/scheduler.md:358): data-parallel batch
  * decode over one 8xMI355X node.  One process per GPU; RCCL over xGMI only for the one-time weight

@@ -110,6 +110,10 @@ _PROTOS = {
     "pgk_ln_linear": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _F, _I, _I, _V],
     "pgk_ln_linear_qkv_cache": [_V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _F, _I, _V, _I, _V],
     "pgk_embed_token_position": [_V, _V, _V, _I, _I, _I, _V, _I, _V],
+    "pgk_audio_log_mel": [_V, _V, _V, _V, _V, _V, _I, C.c_longlong, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _I, _F, _I, _I, _V],
+    "pgk_audio_stft": [_V, _V, _V, _V, C.c_longlong, _I, _I, _I, _V], "pgk_audio_map": [_V, _V, _Z, _I, _F, _V],
+    "pgk_audio_normalize": [_V, _Z, _I, _D, _V],
+    "pgk_audio_resample": [_V, _V, _V, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _V],
     "pgk_sdpa_causal_fp8": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
     "pgk_quantize_fp8_per_head": [_V, _V, _V, _I, _I, _I, _I64, _I64, _I, _V], "pgk_device_arch": [C.POINTER(_I)],
     "pgk_l2norm": [_V, _V, _I, _I, _F, _I, _V], "pgk_irope_scale_q": [_V, _V, _V, _I, _I, _I, _F, _F, _I, _I, _V],
@@ -155,6 +159,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_lstm_plan": ([_I, _I, _I], C.c_int),
                "pgk_conv1d_plan": ([_I, _I, _I, _I, _I, _I, _I], C.c_int), "pgk_conv1d_packed_elems": ([_I, _I, _I], C.c_size_t),
                "pgk_ln_linear_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
+               "pgk_audio_log_mel_plan": ([_I, _I, _I], C.c_int),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}

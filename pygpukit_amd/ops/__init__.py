@@ -33,5 +33,6 @@ from pygpukit_amd.ops.sampling import (sample_greedy, sample_multinomial, sample
 from pygpukit_amd.ops.tensor import (cast_bf16_to_f32, cast_f16_to_f32, cast_f32_to_bf16, cast_f32_to_f16, concat_axis0,
                                     repeat_interleave_axis1, reshape_copy, transpose_3d_012, transpose_3d_021, transpose_4d_0132,
                                     transpose_4d_0213)
+from pygpukit_amd.ops import audio
 
 __all__ = [n for n in dir() if not n.startswith("_")]
