@@ -321,6 +321,13 @@ pgk_status pgk_w8a16_gemm_nk(const void* a, const uint8_t* w_nk, const void* sca
  * w_scale [ceil(N/128), K/128] bf16 (the LinearFP8 layout, linear.py:149-160); C bf16 [M,N].  K % 128 == 0. */
 pgk_status pgk_gemm_fp8_nt(const uint8_t* a_fp8, const float* a_scale, const uint8_t* w_fp8_nk, const void* w_scale,
                            void* c, int m, int n, int k, pgk_stream s);
+/* [build-defined] The kernel that a call of the dense GEMM family takes, decided on the host (needs no device):
+ * op = "nt" (pgk_gemm_nt), "nn" (pgk_gemm_nn), "w8a16_nk", "w8a16_kn", "gemv_fp8" (pgk_gemv_fp8_bf16) or "fp8_nt"
+ * (pgk_gemm_fp8_nt); aligned = every operand on a 16-byte boundary.  Reads PGK_GEMM256 / PGK_GEMM256S per call, as the
+ * dispatchers do, and is built from the decision functions they switch on (csrc/gemm_plan.h).  Returns a leaf name
+ * ("GEMM dispatch leaves") in a thread-local buffer that the next call on the thread overwrites, or NULL
+ * with pgk_last_error set for an op, dtype or shape that the entry point rejects. */
+const char* pgk_gemm_plan(const char* op, int m, int n, int k, pgk_dtype dt, int aligned);
 /* gemm_fp8_fp8_sm120 / gemm_fp8_fp8_blockwise_sm120 (src/pygpukit/ops/matmul/fp8.py:220-343, bindings
  * native/bindings/gemm/fp8xfp8_fp8.cpp): fp8 in, fp8 out,
  *   D[m][n] = E4M3( sum_kb scale_a[mb,kb] * scale_b[nb,kb] * sum_{k in kb} E4M3(a[m][k]) * E4M3(b[k][n]) ),

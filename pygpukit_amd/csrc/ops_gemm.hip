@@ -12,8 +12,11 @@
 // exists on this target and nothing is linked in their place.
 
 #include "gemm_epilogues.hip.h"
+#include "gemm_plan.h"
 #include "gemv_core.hip.h"
 #include "pgk_internal.h"
+
+#include <string>
 
 namespace pgk {
 
@@ -38,7 +41,6 @@ bool want_gemm256(int M, int N) {
     if (force == 1) return true;
     return (long long)ceil_div(M, 256) * ceil_div(N, 256) >= 192;
 }
-static bool use_gemm256(int M, int N, int K) { return K % 64 == 0 && want_gemm256(M, N); }
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
@@ -346,18 +348,12 @@ static pgk_status launch_mfma(const T* A, const void* B, const bf16* bscale, con
     return PGK_OK;
 }
 
-// Tile choice: smallest BM covering M (<=128); BN as large as keeps >= ~256 workgroups in flight.
+// Tile choice: mfma_pick_tile (gemm_plan.h).
 template <class T, int MODE, int EPI = 0>
 static pgk_status dispatch_mfma(const T* A, const void* B, const bf16* bscale, const T* bias, void* C, int M, int N, int K,
                                 hipStream_t st) {
-    int bm = M <= 32 ? 32 : (M <= 64 ? 64 : 128);
-    long long mblocks = (M + bm - 1) / bm;
-    int bn = 128;
-    while (bn > 32 && mblocks * ((N + bn - 1) / bn) < 256) bn >>= 1;
-    // 128 x 64 tiles that only just cover the chip (one 4-wave workgroup per CU, nothing to overlap its barriers with)
-    // lose to twice as many 64 x 64 tiles: M=2048, N=1024, K=2048/3072 measured 23.9 / 33.9 us against 28.3 / 39.9
-    if (bm == 128 && bn == 64 && mblocks * ((N + 63) / 64) < 512) { bm = 64; mblocks = (M + 63) / 64; }
-    if (MODE == B_KN_FP8 && bn < 64) bn = 64;  // keep whole 16-code chunks per thread
+    const MfmaTile tile = mfma_pick_tile(M, N, MODE == B_KN_FP8);      // gemm_plan.h
+    const int bm = tile.bm, bn = tile.bn;
 #define PGK_TILE(BM_, BN_) if (bm == BM_ && bn == BN_) return launch_mfma<T, BM_, BN_, MODE, EPI>(A, B, bscale, bias, C, M, N, K, st);
     PGK_TILE(128, 128) PGK_TILE(128, 64) PGK_TILE(128, 32)
     PGK_TILE(64, 128) PGK_TILE(64, 64) PGK_TILE(64, 32)
@@ -417,7 +413,7 @@ pgk_status engine_gemm_nt(const bf16* A, const void* W, const bf16* wscale, bool
         if (use_gemm256(M, N, K)) return gemm256_bf16_nt(A, (const bf16*)W, nullptr, C, accum_f32, M, N, K, st, true);
         return gemm128s_bf16_nt(A, (const bf16*)W, nullptr, C, accum_f32 ? 1 : 0, 1, M, N, K, st, nullptr, true);
     }
-    if (fp8 && use_gemm256(M, N, K) && K % 128 == 0 && N % 128 == 0) {
+    if (fp8 && w8a16_large_pick(M, N, K) == W8_DEQUANT_GEMM256) {
         // large w8a16 products: dequantise the weight once into a bf16 scratch (a ~10 % extra pass over memory) and run
         // the LDS-DMA bf16 kernel, instead of dequantising in the staging path of the 128-tile kernel (0.58 vs ~1 PFLOP/s)
         void* wb = nullptr;
@@ -482,27 +478,24 @@ pgk_status pgk_gemm_nt(const void* a, const void* w, const void* bias, void* c, 
     PGK_REQUIRE(m >= 0 && n > 0 && k > 0, "pgk_gemm_nt: bad shape M=%d N=%d K=%d", m, n, k);
     if (!m) return PGK_OK;
     hipStream_t st = resolve_stream(s);
-    const bool al = aligned16(a) && aligned16(w) && (k % 8 == 0);
-    if (dt == PGK_F32 || !al) {
-        if (m <= 8) {
+    switch (gemm_nt_pick(m, n, k, dt, aligned16(a) && aligned16(w))) {      // gemm_plan.h
+        case NT_GEMV:
             PGK_DISPATCH_FLOAT(dt, "pgk_gemm_nt", return (launch_gemv<T>((const T*)a, (const T*)w, (const T*)bias, (T*)c, m, k, n, st)));
+            return PGK_OK;
+        case NT_SIMPLE: {
+            dim3 grid(ceil_div(n, 64), ceil_div(m, 64));
+            PGK_DISPATCH_FLOAT(dt, "pgk_gemm_nt", (gemm_simple_kernel<T, true><<<grid, 256, 0, st>>>((const T*)a, (const T*)w, (const T*)bias, (T*)c, m, n, k)));
+            PGK_LAUNCH_CHECK();
+            return PGK_OK;
         }
-        dim3 grid(ceil_div(n, 64), ceil_div(m, 64));
-        PGK_DISPATCH_FLOAT(dt, "pgk_gemm_nt", (gemm_simple_kernel<T, true><<<grid, 256, 0, st>>>((const T*)a, (const T*)w, (const T*)bias, (T*)c, m, n, k)));
-        PGK_LAUNCH_CHECK();
-        return PGK_OK;
+        case NT_WSGEMM: return wsgemm_nt((const bf16*)a, k, w, nullptr, false, c, (const bf16*)bias, 0, 1, m, n, k, st);
+        case NT_GEMM256: return gemm256_bf16_nt((const bf16*)a, (const bf16*)w, (const bf16*)bias, c, false, m, n, k, st);
+        case NT_GEMM128S: return gemm128s_bf16_nt((const bf16*)a, (const bf16*)w, (const bf16*)bias, c, 0, 1, m, n, k, st);
+        case NT_MFMA: break;
     }
-    if (m <= 8 && (size_t)m * k * 2 <= 64 * 1024) {  // weight-streaming GEMV path
-        if (dt == PGK_BF16) return launch_gemv<bf16>((const bf16*)a, (const bf16*)w, (const bf16*)bias, (bf16*)c, m, k, n, st);
-        return launch_gemv<f16>((const f16*)a, (const f16*)w, (const f16*)bias, (f16*)c, m, k, n, st);
-    }
-    if (dt == PGK_BF16 && m <= 128)   // weight-bound regime: stream W once through the skinny MFMA kernel
-        return wsgemm_nt((const bf16*)a, k, w, nullptr, false, c, (const bf16*)bias, 0, 1, m, n, k, st);
-    if (dt == PGK_BF16 && use_gemm256(m, n, k))
-        return gemm256_bf16_nt((const bf16*)a, (const bf16*)w, (const bf16*)bias, c, false, m, n, k, st);
-    if (dt == PGK_BF16 && gemm128s_ok(m, n, k)) return gemm128s_bf16_nt((const bf16*)a, (const bf16*)w, (const bf16*)bias, c, 0, 1, m, n, k, st);
     if (dt == PGK_BF16) return dispatch_mfma<bf16, B_NT>((const bf16*)a, w, nullptr, (const bf16*)bias, (bf16*)c, m, n, k, st);
-    return dispatch_mfma<f16, B_NT>((const f16*)a, w, nullptr, (const f16*)bias, (f16*)c, m, n, k, st);
+    if (dt == PGK_F16) return dispatch_mfma<f16, B_NT>((const f16*)a, w, nullptr, (const f16*)bias, (f16*)c, m, n, k, st);
+    return set_error(PGK_ERR_INVALID, "pgk_gemm_nt: unsupported dtype %d", (int)dt);
 }
 
 pgk_status pgk_gemm_nn(const void* a, const void* b, void* c, int m, int n, int k, pgk_dtype dt, pgk_stream s) {
@@ -510,15 +503,15 @@ pgk_status pgk_gemm_nn(const void* a, const void* b, void* c, int m, int n, int 
     PGK_REQUIRE(m >= 0 && n > 0 && k > 0, "pgk_gemm_nn: bad shape M=%d N=%d K=%d", m, n, k);
     if (!m) return PGK_OK;
     hipStream_t st = resolve_stream(s);
-    const bool al = aligned16(a) && aligned16(b) && (k % 8 == 0) && (n % 8 == 0);
-    if (dt == PGK_F32 || !al) {
+    if (gemm_nn_pick(n, k, dt, aligned16(a) && aligned16(b)) == NN_SIMPLE) {      // gemm_plan.h
         dim3 grid(ceil_div(n, 64), ceil_div(m, 64));
         PGK_DISPATCH_FLOAT(dt, "pgk_gemm_nn", (gemm_simple_kernel<T, false><<<grid, 256, 0, st>>>((const T*)a, (const T*)b, nullptr, (T*)c, m, n, k)));
         PGK_LAUNCH_CHECK();
         return PGK_OK;
     }
     if (dt == PGK_BF16) return dispatch_mfma<bf16, B_NN>((const bf16*)a, b, nullptr, nullptr, (bf16*)c, m, n, k, st);
-    return dispatch_mfma<f16, B_NN>((const f16*)a, b, nullptr, nullptr, (f16*)c, m, n, k, st);
+    if (dt == PGK_F16) return dispatch_mfma<f16, B_NN>((const f16*)a, b, nullptr, nullptr, (f16*)c, m, n, k, st);
+    return set_error(PGK_ERR_INVALID, "pgk_gemm_nn: unsupported dtype %d", (int)dt);
 }
 
 pgk_status pgk_w8a16_gemm_nk(const void* a, const uint8_t* w_nk, const void* scale, void* c, int m, int n, int k,
@@ -528,7 +521,8 @@ pgk_status pgk_w8a16_gemm_nk(const void* a, const uint8_t* w_nk, const void* sca
     PGK_REQUIRE(k % 128 == 0 && n % 128 == 0, "pgk_w8a16_gemm_nk: K=%d, N=%d must be multiples of the 128x128 scale block", k, n);
     PGK_REQUIRE(aligned16(a) && aligned16(w_nk), "pgk_w8a16_gemm_nk: operands must be 16-byte aligned");
     if (!m) return PGK_OK;
-    if (m <= 128) return wsgemm_nt((const bf16*)a, k, w_nk, (const bf16*)scale, true, c, nullptr, 0, 1, m, n, k, resolve_stream(s));
+    if (w8a16_nk_pick(m, n, k) == W8_WSGEMM)      // gemm_plan.h; engine_gemm_nt takes W8_DEQUANT_GEMM256 / W8_MFMA by the same function
+        return wsgemm_nt((const bf16*)a, k, w_nk, (const bf16*)scale, true, c, nullptr, 0, 1, m, n, k, resolve_stream(s));
     return engine_gemm_nt((const bf16*)a, w_nk, (const bf16*)scale, true, c, false, m, n, k, resolve_stream(s), false);
 }
 
@@ -540,6 +534,79 @@ pgk_status pgk_w8a16_gemm_kn(const void* a, const uint8_t* b_kn, const void* sca
     PGK_REQUIRE(aligned16(a) && aligned16(b_kn), "pgk_w8a16_gemm_kn: operands must be 16-byte aligned");
     if (!m) return PGK_OK;
     return dispatch_mfma<bf16, B_KN_FP8>((const bf16*)a, b_kn, (const bf16*)scale, nullptr, (bf16*)c, m, n, k, resolve_stream(s));
+}
+
+// The kernel a call of this shape takes, as text (tests assert it; see DESIGN.md "GEMM dispatch leaves").  Built from the
+// decision functions of gemm_plan.h that the entry points above and their launchers switch on; needs no device.
+// NULL (and pgk_last_error) for an op name, dtype or shape that the entry point itself rejects.
+const char* pgk_gemm_plan(const char* op, int m, int n, int k, pgk_dtype dt, int aligned) {
+    static thread_local char buf[96];
+    const auto fail = [](const char* why, const char* op_, int m_, int n_, int k_, int dt_) -> const char* {
+        set_error(PGK_ERR_INVALID, "pgk_gemm_plan: %s (op=%s M=%d N=%d K=%d dtype=%d)", why, op_ ? op_ : "NULL", m_, n_, k_, dt_);
+        return nullptr;
+    };
+    if (!op) return fail("null op", op, m, n, k, (int)dt);
+    if (m < 1 || n < 1 || k < 1) return fail("bad shape", op, m, n, k, (int)dt);
+    const std::string o(op);
+    const bool al = aligned != 0;
+    const auto gemm256 = [&](const char* prefix) -> const char* {
+        static const char* const names[] = {"gemm256s", "gemm256s_n192", "gemm256_lockstep"};
+        snprintf(buf, sizeof buf, "%s%s", prefix, names[gemm256_pick(m, n, false, false)]);
+        return buf;
+    };
+    const auto mfma = [&](const char* mode, bool kn) -> const char* {
+        const MfmaTile t = mfma_pick_tile(m, n, kn);
+        snprintf(buf, sizeof buf, "mfma_%dx%d_%s", t.bm, t.bn, mode);
+        return buf;
+    };
+    const auto wsgemm = [&](bool fp8) -> const char* {
+        snprintf(buf, sizeof buf, "wsgemm_mt%d%s", wsgemm_pick_mt(m), fp8 ? "_fp8" : "");
+        return buf;
+    };
+    if (o == "nt" || o == "nn") {
+        if (!is_float_dtype(dt)) return fail("dtype must be float32, float16 or bfloat16", op, m, n, k, (int)dt);
+        if (o == "nn") {
+            if (gemm_nn_pick(n, k, dt, al) == NN_SIMPLE) return "simple_nn";
+            return mfma("B_NN", false);
+        }
+        switch (gemm_nt_pick(m, n, k, dt, al)) {
+            case NT_GEMV:
+                if (gemv_pick(m, k, dtype_size(dt), al) == GEMV_GENERIC) return "gemv_generic";
+                snprintf(buf, sizeof buf, "gemv_fast_m%d", m);
+                return buf;
+            case NT_SIMPLE: return "simple_nt";
+            case NT_WSGEMM: return wsgemm(false);
+            case NT_GEMM256: return gemm256("");
+            case NT_GEMM128S: return "gemm128s";
+            case NT_MFMA: return mfma("B_NT", false);
+        }
+        return fail("no kernel", op, m, n, k, (int)dt);
+    }
+    // the fp8 entry points: bf16 activations / output, 16-byte aligned operands and whole 128 x 128 scale blocks by contract
+    if (dt != PGK_BF16) return fail("the fp8 entry points are bfloat16", op, m, n, k, (int)dt);
+    if (!al) return fail("the fp8 entry points need 16-byte aligned operands", op, m, n, k, (int)dt);
+    if (o == "fp8_nt") {
+        if (k % 128) return fail("K must be a multiple of 128", op, m, n, k, (int)dt);
+        return gemm_fp8_pick(m, n) == FP8_TILE256 ? "fp8_256" : "fp8_128";
+    }
+    if (k % 128 || n % 128) return fail("K and N must be multiples of the 128 x 128 scale block", op, m, n, k, (int)dt);
+    if (o == "w8a16_nk") {
+        switch (w8a16_nk_pick(m, n, k)) {
+            case W8_WSGEMM: return wsgemm(true);
+            case W8_DEQUANT_GEMM256: return gemm256("dequant+");
+            case W8_MFMA: return mfma("B_NT_FP8", false);
+        }
+    }
+    if (o == "w8a16_kn") return mfma("B_KN_FP8", true);
+    if (o == "gemv_fp8") {
+        if ((size_t)gemv_fp8_pass_rows(m, 0) * k * 2 > 64 * 1024) return fail("K too large for the rows of one pass", op, m, n, k, (int)dt);
+        const int full = m / 8, rest = m % 8;       // passes of gemv_fp8_pass_rows: `full` of 8 rows, then the rest
+        if (m <= 8) snprintf(buf, sizeof buf, "gemv_fp8_m%d", m);
+        else if (rest) snprintf(buf, sizeof buf, "gemv_fp8_m8x%d+m%d", full, rest);
+        else snprintf(buf, sizeof buf, "gemv_fp8_m8x%d", full);
+        return buf;
+    }
+    return fail("op must be one of nt, nn, w8a16_nk, w8a16_kn, gemv_fp8, fp8_nt", op, m, n, k, (int)dt);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 // The reference calls CUTLASS / cuBLASLt here (native/ops/matmul/matmul.cu:142-235); nothing of theirs is used.
 
 #include "gemm_epilogues.hip.h"
+#include "gemm_plan.h"
 #include "gemv_core.hip.h"
 #include "pgk_internal.h"
 
@@ -942,19 +943,17 @@ pgk_status gemm256_bf16_nt(const bf16* A, const bf16* W, const bf16* bias, void*
         attr_done = true;
     }
     const int ntm = ceil_div(M, G2_BM), ntn = ceil_div(N, G2_BN);
-    const char* e = getenv("PGK_GEMM256S");          // 0: two full stages, waves in lockstep; default: staggered phases
-    if (packed || !e || atoi(e) != 0) {
+    static_assert(G2_BM == 256 && G2_BN == 256, "gemm256_pick counts 256 x 256 tiles");
+    const Gemm256Kernel kern = gemm256_pick(M, N, accum_f32, packed);      // gemm_plan.h (reads PGK_GEMM256S)
+    if (kern != G256_LOCKSTEP) {
         static bool attr_s = false;
         if (!attr_s) {
             PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
             PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
             attr_s = true;
         }
-        // 192-column tiles when they fill the rounds of the chip better (cost = rounds x work per tile)
         const int ntn3 = N / 192;
-        const bool narrow = !accum_f32 && N % 192 == 0 &&
-                            0.75 * ceil_div(ntm * ntn3, 256) < (double)ceil_div(ntm * ntn, 256) - 0.01;
-        if (narrow) {
+        if (kern == G256_STAGGERED_N192) {      // 192-column tiles
             static bool attr_n = false;
             if (!attr_n) {
                 PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));

@@ -1,6 +1,7 @@
 // Op-level GEMV entry points (M = 1..8 activation rows against an [N,K] weight).
 // See gemv_core.hip.h for the kernel design.
 
+#include "gemm_plan.h"
 #include "gemv_core.hip.h"
 #include "pgk_internal.h"
 
@@ -112,9 +113,9 @@ static int gemv_grid(int N) {
 // Launch helper used by pgk_gemv and by the M<=8 path of pgk_gemm_nt.
 template <class T>
 pgk_status launch_gemv(const T* x, const T* w, const T* bias, T* out, int M, int K, int N, hipStream_t st) {
-    constexpr int NV = Vec<T>::N;
+    static_assert(Vec<T>::N * sizeof(T) == 16, "gemv_pick assumes 16-byte vectors");
     const size_t lds = (size_t)M * K * sizeof(T);
-    const bool fast = (K % NV == 0) && aligned16(x) && aligned16(w) && lds <= 64 * 1024 && M <= 8;
+    const bool fast = gemv_pick(M, K, sizeof(T), aligned16(x) && aligned16(w)) == GEMV_FAST;      // gemm_plan.h
     const int grid = gemv_grid(N);
     if (!fast) {
         gemv_generic_kernel<T><<<grid, GEMV_BLOCK, 0, st>>>(x, w, bias, out, M, K, N);
@@ -158,7 +159,7 @@ pgk_status pgk_gemv_fp8_bf16(const void* a, const uint8_t* b_nk, const void* sca
     const int grid = gemv_grid(n);
     // M rows in passes of <= 8 (weights are re-read per pass; M > 8 belongs to pgk_w8a16_gemm_kn / MFMA)
     for (int m0 = 0; m0 < m; m0 += 8) {
-        const int mm = (m - m0) < 8 ? (m - m0) : 8;
+        const int mm = gemv_fp8_pass_rows(m, m0);      // gemm_plan.h
         const bf16* x = (const bf16*)a + (size_t)m0 * k;
         bf16* o = (bf16*)c + (size_t)m0 * n;
         const size_t lds = (size_t)mm * k * 2;

@@ -14,6 +14,7 @@
 // The reference has nothing of this shape (M < 16 goes to cuBLASLt, M >= 16 to 128x128 CUTLASS tiles,
 // native/ops/matmul/matmul.cu:142-235).
 
+#include "gemm_plan.h"
 #include "gemv_core.hip.h"
 #include "pgk_internal.h"
 
@@ -209,7 +210,7 @@ pgk_status wsgemm_nt(const bf16* a, int lda, const void* w, const bf16* wscale, 
     g.k_per_split = kps;
     const int real_splits = ceil_div(K, kps);
     PGK_REQUIRE(real_splits == splits, "wsgemm: %d splits do not tile K=%d (use %d)", splits, K, real_splits);
-    const int mt = ceil_div(M, 16);
+    const int mt = wsgemm_pick_mt(M);      // gemm_plan.h: 1, 2, 4 or 8 tiles of 16 rows
     dim3 grid(ceil_div(N, 64), splits);
 #define PGK_WS_LAUNCH(MTV, F8, MD)                                                                               \
     {                                                                                                            \
@@ -222,7 +223,7 @@ pgk_status wsgemm_nt(const bf16* a, int lda, const void* w, const bf16* wscale, 
         wsgemm_kernel<MTV, F8, MD><<<grid, WS_THREADS, lds, st>>>(g);                                            \
     }
 #define PGK_WS(MTV)                                                                                              \
-    if (mt <= MTV) {                                                                                             \
+    if (mt == MTV) {                                                                                             \
         const size_t lds = (size_t)MTV * 16 * WS_KT * 2;                                                         \
         if (fp8) {                                                                                               \
             if (mode == 0) PGK_WS_LAUNCH(MTV, true, 0) else if (mode == 1) PGK_WS_LAUNCH(MTV, true, 1) else PGK_WS_LAUNCH(MTV, true, 2) \

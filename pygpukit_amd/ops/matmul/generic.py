@@ -40,6 +40,28 @@ def matmul_nt(a: GPUArray, w: GPUArray, bias: GPUArray | None = None, *, out: GP
     return c
 
 
+GEMM_PLAN_OPS = ("nt", "nn", "w8a16_nk", "w8a16_kn", "gemv_fp8", "fp8_nt")
+
+
+def gemm_plan(op: str, m: int, n: int, k: int, dtype, aligned: bool = True) -> str:
+    """[build-defined] The kernel a dense GEMM call of this shape takes, decided on the host (needs no device).  `op` names the
+    entry point: "nt" (matmul_nt), "nn" (matmul), "w8a16_nk", "w8a16_kn" (w8a16_gemm), "gemv_fp8" (gemv_fp8_bf16[_batched]) or
+    "fp8_nt" (gemm_fp8_fp8_blockwise_nt); `aligned=False`: an operand off 16-byte alignment.  PGK_GEMM256 / PGK_GEMM256S are
+    read per call, as the dispatchers read them.  The leaves are listed in DESIGN.md ("GEMM dispatch leaves"): gemv_fast_m1..8,
+    gemv_generic, simple_nt / simple_nn, wsgemm_mt{1,2,4,8}[_fp8], gemm256s / gemm256s_n192 / gemm256_lockstep (with a
+    "dequant+" prefix for large w8a16_nk products), gemm128s, mfma_{bm}x{bn}_{B_NT,B_NN,B_NT_FP8,B_KN_FP8}, gemv_fp8_m1..8 and
+    gemv_fp8_m8x{passes}[+m{rest}] beyond 8 rows, fp8_128 / fp8_256."""
+    from pygpukit_amd import _hip
+    from pygpukit_amd.core.dtypes import as_dtype
+
+    lib = _hip.load()
+    plan = lib.pgk_gemm_plan(str(op).encode(), int(m), int(n), int(k), as_dtype(dtype).code, int(bool(aligned)))
+    if plan is None:
+        msg = lib.pgk_last_error()
+        raise ValueError(msg.decode(errors="replace") if msg else f"gemm_plan: invalid call op={op} m={m} n={n} k={k} dtype={dtype}")
+    return plan.decode()
+
+
 def transpose(a: GPUArray) -> GPUArray:
     """2-D transpose (generic.py:122-162); any element size (also used on uint8 fp8 weights)."""
     if a.ndim != 2:

@@ -5,8 +5,6 @@ fp8 <= 5e-2; copies and index ops bit-exact."""
 
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import pytest
 
@@ -18,6 +16,7 @@ pytestmark = pytest.mark.gpu
 pk = pytest.importorskip("pygpukit_amd")
 from pygpukit_amd import ops  # noqa: E402
 from pygpukit_amd.core import bfloat16, float16, float32, from_numpy  # noqa: E402
+from pygpukit_amd.ops.matmul import gemm_plan  # noqa: E402
 
 g1 = load_golden("g1_ops.npz")
 DT = {"float32": float32, "float16": float16, "bfloat16": bfloat16}
@@ -549,11 +548,15 @@ def test_gemm_fp8_blockwise(shape):
     assert rel_err(c, a @ w.T) < 5e-2
 
 
-@pytest.mark.parametrize("shape", [(256, 256, 128), (300, 520, 384), (1000, 260, 1024)])
+@pytest.mark.parametrize("shape", [(256, 256, 128), (300, 520, 384), (1000, 260, 1024), (512, 512, 256), (512, 768, 384)])
 def test_gemm256_fp8_matches_oracle_and_128_tile_kernel(shape, monkeypatch):
     """fp8 x fp8 on the 256-tile LDS-DMA structure (operand tiles AND scales arrive by DMA) vs the oracle and vs the
-    128-tile kernel, on ragged M / N (N = 260, 520: a last 128-column scale block that is only partly there)."""
+    128-tile kernel.  The 256-tile kernel takes whole tiles only (M % 256 == 0 and N % 256 == 0): on those shapes the two
+    forced legs run different kernels, which gemm_plan confirms.  The ragged shapes (N = 260, 520: a last 128-column scale
+    block that is only partly there) fall back to the 128-tile kernel even when forced, so both legs run that kernel and
+    the comparison between them only shows that the fallback is taken and gives the same words twice."""
     M, N, K = shape
+    whole = M % 256 == 0 and N % 256 == 0
     rng = np.random.default_rng(33)
     a = (rng.standard_normal((M, K)) * rng.uniform(0.1, 4.0, (M, 1))).astype(np.float32)
     w = (rng.standard_normal((N, K)) * 0.02 * rng.uniform(0.5, 2.0, (N, 1))).astype(np.float32)
@@ -566,8 +569,10 @@ def test_gemm256_fp8_matches_oracle_and_128_tile_kernel(shape, monkeypatch):
     ref = O.gemm_fp8_blockwise(a8, sa, w8, sw)
     args = [from_numpy(a8), from_numpy(w8), from_numpy(sa), from_numpy(sw)]
     monkeypatch.setenv("PGK_GEMM256", "1")
+    assert gemm_plan("fp8_nt", M, N, K, "bfloat16") == ("fp8_256" if whole else "fp8_128")
     c256 = host(ops.gemm_fp8_fp8_blockwise_nt(*args))
     monkeypatch.setenv("PGK_GEMM256", "0")
+    assert gemm_plan("fp8_nt", M, N, K, "bfloat16") == "fp8_128"
     c128 = host(ops.gemm_fp8_fp8_blockwise_nt(*args))
     assert rel_err(c256, ref) < 3e-3 and rel_err(c128, ref) < 3e-3
     assert rel_err(c256, c128) < 3e-3
@@ -613,27 +618,30 @@ def test_config5_shape_gemms_fp8a8_and_w8a16_vs_oracle(shape, monkeypatch):
         assert rel_err(c[rows], exact) < 5e-2, (tile, rel_err(c[rows], exact))
 
 
-def test_gemm_fp8_exact_integers_and_asymmetric_operand():
+def test_gemm_fp8_exact_integers_and_asymmetric_operand(monkeypatch):
     """Small-integer operands with unit scales are exact in e4m3 and in fp32: the result must be bit-exact, which
-    pins the A/B lane->k pairing and the C row/col map (an asymmetric W catches a transposed store)."""
+    pins the A/B lane->k pairing and the C row/col map (an asymmetric W catches a transposed store).  48 x 160 is no whole
+    number of 256-tiles, so it runs the 128-tile kernel on both legs (forcing the 256-tile one falls back); 256 x 512 runs
+    the 128-tile kernel, then the 256-tile LDS-DMA kernel, as gemm_plan confirms.  Block scales that differ between blocks
+    are in tests/test_gemm_exact_gpu.py."""
     rng = np.random.default_rng(24)
-    M, N, K = 48, 160, 256
     table = O.fp8_e4m3_table()
     ints = {float(v): c for c, v in enumerate(table[:0x7F]) if v == np.floor(v) and v <= 8}
-    ai = rng.integers(-4, 5, (M, K)).astype(np.float32)
-    wi = rng.integers(-4, 5, (N, K)).astype(np.float32)
-    wi[:, 0] = np.arange(N) % 5       # asymmetric
     enc = lambda x: (np.vectorize(lambda v: ints[abs(float(v))])(x).astype(np.uint8) | np.where(x < 0, 0x80, 0).astype(np.uint8))
-    a8, w8 = enc(ai), enc(wi)
-    sa = np.ones((M, K // 128), np.float32)
-    sw = np.full((2, K // 128), 0x3F80, np.uint16)
-    for force in ("0", "1"):      # 128-tile kernel, then the 256-tile LDS-DMA kernel
-        os.environ["PGK_GEMM256"] = force
-        try:
+    for M, N, K in ((48, 160, 256), (256, 512, 256)):
+        ai = rng.integers(-4, 5, (M, K)).astype(np.float32)
+        wi = rng.integers(-4, 5, (N, K)).astype(np.float32)
+        wi[:, 0] = np.arange(N) % 5       # asymmetric
+        a8, w8 = enc(ai), enc(wi)
+        sa = np.ones((M, K // 128), np.float32)
+        sw = np.full(((N + 127) // 128, K // 128), 0x3F80, np.uint16)
+        plans = []
+        for force in ("0", "1"):      # 128-tile kernel, then (whole 256-tiles only) the 256-tile LDS-DMA kernel
+            monkeypatch.setenv("PGK_GEMM256", force)
+            plans.append(gemm_plan("fp8_nt", M, N, K, "bfloat16"))
             c = host(ops.gemm_fp8_fp8_blockwise_nt(from_numpy(a8), from_numpy(w8), from_numpy(sa), from_numpy(sw)))
-        finally:
-            del os.environ["PGK_GEMM256"]
-        np.testing.assert_array_equal(c, O.bf16_round(ai @ wi.T))
+            np.testing.assert_array_equal(c, O.bf16_round(ai @ wi.T))
+        assert plans == (["fp8_128", "fp8_256"] if M % 256 == 0 and N % 256 == 0 else ["fp8_128", "fp8_128"])
 
 
 def test_matmul_fp8_auto_quantise():
