@@ -162,6 +162,15 @@ pgk_status pgk_glu_packed(const void* gate_up, void* out, int rows, int inter, i
 /* ops.cuh:426-436 cast_f32_to_bf16 / f32_to_f16 / bf16_to_f32 / f16_to_f32 (RNE) */
 pgk_status pgk_cast(const void* src, pgk_dtype src_dt, void* dst, pgk_dtype dst_dt, size_t n, pgk_stream s);
 
+/* Host-only queries of the base op dispatch (csrc/base_plan.h; DESIGN.md "Base op dispatch leaves"): the kernel branch a call
+ * takes and the number of blocks it launches, from the functions the launchers themselves call.  op: "binary", "activation",
+ * "glu", "cast", "clamp", "where", "reduce" (n_or_rows = elements, features ignored), "glu_packed" (rows, inter), "bias_add",
+ * "rmsnorm", "rmsnorm_residual", "layernorm" (rows, features), "rope" (seq * (Hq + Hk), D).  aligned: every pointer the
+ * launcher tests is on a 16-byte boundary.  Leaves: ew_vec / ew_scalar, row_vec / row_scalar, norm_wave / norm_block,
+ * cast_x4, rope_pairs, ew_stride, reduce_tree (the first level of pgk_reduce).  NULL / -1 and pgk_last_error for a call the entry point rejects.  No device is touched. */
+const char* pgk_base_op_plan(const char* op, size_t rows, int features, pgk_dtype dt, int aligned);
+int pgk_base_op_grid(const char* op, size_t n_or_rows, int features, pgk_dtype dt, int aligned);
+
 /* ------------------------------------------------------------------------ norms ----- */
 /* ops.cuh:152-155 rmsnorm(input[rows,features], gamma[features]) -> out (may alias input) */
 pgk_status pgk_rmsnorm(const void* x, const void* gamma, void* out, int rows, int features, float eps,

@@ -160,6 +160,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_conv1d_plan": ([_I, _I, _I, _I, _I, _I, _I], C.c_int), "pgk_conv1d_packed_elems": ([_I, _I, _I], C.c_size_t),
                "pgk_ln_linear_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
                "pgk_gemm_plan": ([C.c_char_p, _I, _I, _I, _I, _I], C.c_char_p),
+               "pgk_base_op_plan": ([C.c_char_p, _Z, _I, _I, _I], C.c_char_p), "pgk_base_op_grid": ([C.c_char_p, _Z, _I, _I, _I], C.c_int),
                "pgk_audio_log_mel_plan": ([_I, _I, _I], C.c_int),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),

@@ -2,18 +2,13 @@
 // All HBM-bound: 16-byte accesses per lane, grid capped at 2048 blocks and grid-strided
 // (cdna_hip_programming.md Guideline 11/13).  fp32 math, one rounding on store.
 
+#include <string>
+
+#include "base_plan.h"
 #include "pgk_device.hip.h"
 #include "pgk_internal.h"
 
 namespace pgk {
-
-constexpr int EW_BLOCK = 256;
-
-static inline int ew_grid(size_t work_items) {
-    size_t g = (work_items + EW_BLOCK - 1) / EW_BLOCK;
-    if (g < 1) g = 1;
-    return (int)(g > 2048 ? 2048 : g);
-}
 
 __device__ __forceinline__ float binop(float a, float b, int op) {
     switch (op) {
@@ -200,9 +195,10 @@ pgk_status pgk_binary(const void* a, const void* b, void* c, size_t n, int op, p
     PGK_REQUIRE(op >= 0 && op <= 3, "pgk_binary: bad op %d", op);
     if (!n) return PGK_OK;
     hipStream_t st = resolve_stream(s);
-    const bool vec = aligned16(a) && aligned16(b) && aligned16(c);
+    const bool al = aligned16(a) && aligned16(b) && aligned16(c);
+    const bool vec = ew_flat_pick(al) == EW_VEC;      // base_plan.h
     PGK_DISPATCH_FLOAT(dt, "pgk_binary", {
-        const int grid = ew_grid(vec ? n / Vec<T>::N + 1 : n);
+        const int grid = ew_flat_grid(n, sizeof(T), al);
         if (vec) binary_kernel<T, true><<<grid, EW_BLOCK, 0, st>>>((const T*)a, (const T*)b, (T*)c, n, op);
         else binary_kernel<T, false><<<grid, EW_BLOCK, 0, st>>>((const T*)a, (const T*)b, (T*)c, n, op);
     });
@@ -220,9 +216,9 @@ pgk_status pgk_bias_add_inplace(void* out, const void* bias, int rows, int featu
     if (!rows) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     PGK_DISPATCH_FLOAT(dt, "pgk_bias_add_inplace", {
-        const bool vec = aligned16(out) && aligned16(bias) && (features % Vec<T>::N == 0);
-        const size_t n = (size_t)rows * features;
-        const int grid = ew_grid(vec ? n / Vec<T>::N : n);
+        const bool al = aligned16(out) && aligned16(bias);
+        const bool vec = ew_row_pick(features, sizeof(T), al) == ROW_VEC;      // base_plan.h
+        const int grid = ew_row_grid((size_t)rows, features, sizeof(T), al);
         if (vec) bias_add_kernel<T, true><<<grid, EW_BLOCK, 0, st>>>((T*)out, (const T*)bias, rows, features);
         else bias_add_kernel<T, false><<<grid, EW_BLOCK, 0, st>>>((T*)out, (const T*)bias, rows, features);
     });
@@ -235,9 +231,10 @@ pgk_status pgk_activation(const void* x, void* y, size_t n, int act, pgk_dtype d
     PGK_REQUIRE(act >= 0 && act <= 13, "pgk_activation: bad activation %d", act);
     if (!n) return PGK_OK;
     hipStream_t st = resolve_stream(s);
-    const bool vec = aligned16(x) && aligned16(y);
+    const bool al = aligned16(x) && aligned16(y);
+    const bool vec = ew_flat_pick(al) == EW_VEC;      // base_plan.h
     PGK_DISPATCH_FLOAT(dt, "pgk_activation", {
-        const int grid = ew_grid(vec ? n / Vec<T>::N + 1 : n);
+        const int grid = ew_flat_grid(n, sizeof(T), al);
         if (vec) act_kernel<T, true><<<grid, EW_BLOCK, 0, st>>>((const T*)x, (T*)y, n, act);
         else act_kernel<T, false><<<grid, EW_BLOCK, 0, st>>>((const T*)x, (T*)y, n, act);
     });
@@ -250,9 +247,10 @@ pgk_status pgk_glu(const void* gate, const void* up, void* out, size_t n, int ac
     PGK_REQUIRE(act == 0 || act == 1, "pgk_glu: bad activation %d", act);
     if (!n) return PGK_OK;
     hipStream_t st = resolve_stream(s);
-    const bool vec = aligned16(gate) && aligned16(up) && aligned16(out);
+    const bool al = aligned16(gate) && aligned16(up) && aligned16(out);
+    const bool vec = ew_flat_pick(al) == EW_VEC;      // base_plan.h
     PGK_DISPATCH_FLOAT(dt, "pgk_glu", {
-        const int grid = ew_grid(vec ? n / Vec<T>::N + 1 : n);
+        const int grid = ew_flat_grid(n, sizeof(T), al);
         if (vec) glu_kernel<T, true><<<grid, EW_BLOCK, 0, st>>>((const T*)gate, (const T*)up, (T*)out, n, act);
         else glu_kernel<T, false><<<grid, EW_BLOCK, 0, st>>>((const T*)gate, (const T*)up, (T*)out, n, act);
     });
@@ -267,9 +265,9 @@ pgk_status pgk_glu_packed(const void* gate_up, void* out, int rows, int inter, i
     if (!rows) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     PGK_DISPATCH_FLOAT(dt, "pgk_glu_packed", {
-        const bool vec = aligned16(gate_up) && aligned16(out) && (inter % Vec<T>::N == 0);
-        const size_t n = (size_t)rows * inter;
-        const int grid = ew_grid(vec ? n / Vec<T>::N : n);
+        const bool al = aligned16(gate_up) && aligned16(out);
+        const bool vec = ew_row_pick(inter, sizeof(T), al) == ROW_VEC;      // base_plan.h
+        const int grid = ew_row_grid((size_t)rows, inter, sizeof(T), al);
         if (vec) glu_packed_kernel<T, true><<<grid, EW_BLOCK, 0, st>>>((const T*)gate_up, (T*)out, rows, inter, act);
         else glu_packed_kernel<T, false><<<grid, EW_BLOCK, 0, st>>>((const T*)gate_up, (T*)out, rows, inter, act);
     });
@@ -283,7 +281,7 @@ pgk_status pgk_cast(const void* src, pgk_dtype sdt, void* dst, pgk_dtype ddt, si
     if (!n) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     if (sdt == ddt) return pgk_memcpy_d2d(dst, src, n * dtype_size(sdt), s);
-    const int grid = ew_grid(n / 4 + 1);
+    const int grid = cast_grid(n);      // base_plan.h
 #define PGK_CAST_CASE(SD, DD, ST, DT)                                                                      \
     if (sdt == SD && ddt == DD) {                                                                          \
         cast_kernel<ST, DT><<<grid, EW_BLOCK, 0, st>>>((const ST*)src, (DT*)dst, n);                       \
@@ -298,6 +296,56 @@ pgk_status pgk_cast(const void* src, pgk_dtype sdt, void* dst, pgk_dtype ddt, si
     PGK_CAST_CASE(PGK_F16, PGK_BF16, f16, bf16)
 #undef PGK_CAST_CASE
     return set_error(PGK_ERR_INVALID, "pgk_cast: unsupported pair");
+}
+
+// The kernel branch a base op takes and the number of blocks it launches, as the launchers of this file, ops_norm_rope.hip
+// and ops_reduce.hip decide them (tests assert both; see DESIGN.md "Base op dispatch leaves").  Built from the functions of
+// base_plan.h that those launchers call; needs no device.  `n_or_rows`: elements for binary / activation / glu / cast / clamp /
+// where / reduce (features is ignored), rows for glu_packed (features = inter) / bias_add / the norms, seq * (Hq + Hk) for rope
+// (features = D).  NULL / -1 (and pgk_last_error) for an op name, dtype or shape that the entry point itself rejects.
+static int base_op_query(const char* who, const char* op, size_t n, int features, pgk_dtype dt, int aligned, const char** leaf) {
+    const auto fail = [&](const char* why) {
+        set_error(PGK_ERR_INVALID, "%s: %s (op=%s n=%zu features=%d dtype=%d)", who, why, op ? op : "NULL", n, features, (int)dt);
+        return -1;
+    };
+    if (!op) return fail("null op");
+    if (!is_float_dtype(dt)) return fail("dtype must be float32, float16 or bfloat16");
+    if (n < 1) return fail("bad shape");
+    const std::string o(op);
+    const size_t item = dtype_size(dt);
+    const bool al = aligned != 0;
+    if (o == "binary" || o == "activation" || o == "glu") {
+        *leaf = ew_flat_pick(al) == EW_VEC ? "ew_vec" : "ew_scalar";
+        return ew_flat_grid(n, item, al);
+    }
+    if (o == "cast") { *leaf = "cast_x4"; return cast_grid(n); }
+    if (o == "clamp" || o == "where") { *leaf = "ew_stride"; return rd_grid(n); }
+    if (o == "reduce") { *leaf = "reduce_tree"; return rd_grid(n); }      // first level of pgk_reduce; the second is one block
+    if (features < 1 || n > 0x7fffffffu) return fail("bad shape");
+    if (o == "glu_packed" || o == "bias_add") {
+        *leaf = ew_row_pick(features, item, al) == ROW_VEC ? "row_vec" : "row_scalar";
+        return ew_row_grid(n, features, item, al);
+    }
+    if (o == "rmsnorm" || o == "rmsnorm_residual" || o == "layernorm") {
+        *leaf = norm_pick(features, item, al) == NORM_WAVE ? "norm_wave" : "norm_block";
+        return norm_grid((int)n, features, item, al);
+    }
+    if (o == "rope") {
+        if (features % 2) return fail("D must be even");
+        *leaf = "rope_pairs";
+        return rope_grid(n * (size_t)(features / 2));
+    }
+    return fail("op must be one of binary, activation, glu, glu_packed, bias_add, cast, rmsnorm, rmsnorm_residual, layernorm, rope, clamp, where, reduce");
+}
+
+const char* pgk_base_op_plan(const char* op, size_t rows, int features, pgk_dtype dt, int aligned) {
+    const char* leaf = nullptr;
+    return base_op_query("pgk_base_op_plan", op, rows, features, dt, aligned, &leaf) < 0 ? nullptr : leaf;
+}
+
+int pgk_base_op_grid(const char* op, size_t n_or_rows, int features, pgk_dtype dt, int aligned) {
+    const char* leaf = nullptr;
+    return base_op_query("pgk_base_op_grid", op, n_or_rows, features, dt, aligned, &leaf);
 }
 
 }  // extern "C"

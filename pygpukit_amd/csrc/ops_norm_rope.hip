@@ -3,13 +3,11 @@
 // else one 256-thread block per row; fp32 math, one rounding on store
 // (reference: native/ops/nn/norm_kernels.cuh:32-584, 32-lane shuffles there, 64 here).
 
+#include "base_plan.h"
 #include "pgk_device.hip.h"
 #include "pgk_internal.h"
 
 namespace pgk {
-
-constexpr int NORM_WAVES = 4;  // rows per block in the wave-per-row kernels
-constexpr int NORM_MAXV = 8;   // 16-byte vectors per lane held in registers
 
 // mode: 0 rmsnorm, 1 rmsnorm(x + residual), 2 layernorm
 template <class T, int MODE>
@@ -123,15 +121,14 @@ __global__ __launch_bounds__(256) void norm_block_kernel(const T* x, const T* re
 template <class T, int MODE>
 static pgk_status launch_norm(const void* x, const void* res, const void* gamma, const void* beta, void* out,
                               int rows, int features, float eps, hipStream_t st) {
-    constexpr int N = Vec<T>::N;
-    const bool vec = (features % N == 0) && features <= 64 * N * NORM_MAXV && aligned16(x) && aligned16(out) &&
-                     aligned16(gamma) && (MODE != 1 || aligned16(res)) && (MODE != 2 || aligned16(beta)) &&
-                     ((size_t)features * sizeof(T)) % 16 == 0;
-    if (vec) {
-        norm_wave_kernel<T, MODE><<<ceil_div(rows, NORM_WAVES), NORM_WAVES * 64, 0, st>>>(
+    const bool al = aligned16(x) && aligned16(out) && aligned16(gamma) && (MODE != 1 || aligned16(res)) &&
+                    (MODE != 2 || aligned16(beta));
+    const int grid = norm_grid(rows, features, sizeof(T), al);      // base_plan.h
+    if (norm_pick(features, sizeof(T), al) == NORM_WAVE) {
+        norm_wave_kernel<T, MODE><<<grid, NORM_WAVES * 64, 0, st>>>(
             (const T*)x, (const T*)res, (const T*)gamma, (const T*)beta, (T*)out, rows, features, eps);
     } else {
-        norm_block_kernel<T, MODE><<<rows, 256, 0, st>>>((const T*)x, (const T*)res, (const T*)gamma,
+        norm_block_kernel<T, MODE><<<grid, 256, 0, st>>>((const T*)x, (const T*)res, (const T*)gamma,
                                                          (const T*)beta, (T*)out, rows, features, eps);
     }
     PGK_LAUNCH_CHECK();
@@ -205,8 +202,7 @@ pgk_status pgk_rope_inplace(void* q, void* k, const void* cos, const void* sin, 
                 seq, hq, hk, d);
     if (!seq) return PGK_OK;
     hipStream_t st = resolve_stream(s);
-    const size_t total = (size_t)seq * (hq + hk) * (d / 2);
-    const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
+    const int grid = rope_grid((size_t)seq * (hq + hk) * (d / 2));      // base_plan.h
     PGK_DISPATCH_FLOAT(dt, "pgk_rope_inplace", {
         if (f32_table) rope_kernel<T, float><<<grid, 256, 0, st>>>((T*)q, (T*)k, (const float*)cos, (const float*)sin, seq, hq, hk, d);
         else rope_kernel<T, T><<<grid, 256, 0, st>>>((T*)q, (T*)k, (const T*)cos, (const T*)sin, seq, hq, hk, d);

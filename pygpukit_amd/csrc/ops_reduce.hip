@@ -4,13 +4,11 @@
 // Every reduction is a fixed two-level tree (per-workgroup partials in fp32, then one workgroup over the partials),
 // so a result does not depend on scheduling: same bits on every run.
 
+#include "base_plan.h"
 #include "pgk_device.hip.h"
 #include "pgk_internal.h"
 
 namespace pgk {
-
-constexpr int RD_BLOCK = 256;
-constexpr int RD_MAX_BLOCKS = 1024;
 
 // op: 0 sum, 1 mean (sum here, scaled at the end), 2 max, 3 min
 __device__ __forceinline__ float rd_identity(int op) { return op == 2 ? -INFINITY : (op == 3 ? INFINITY : 0.f); }
@@ -94,11 +92,6 @@ __global__ void where_kernel(const uint8_t* cond, const T* a, const T* b, T* y, 
 __global__ void widen_i32_i64_kernel(const int32_t* in, int64_t* out, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += stride) out[i] = in[i];
-}
-
-static inline int rd_grid(size_t n) {
-    const size_t g = (n + RD_BLOCK - 1) / RD_BLOCK;
-    return (int)(g < 1 ? 1 : (g > RD_MAX_BLOCKS ? RD_MAX_BLOCKS : g));
 }
 
 }  // namespace pgk
