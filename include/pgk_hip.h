@@ -755,6 +755,31 @@ pgk_status pgk_audio_normalize(float* x, size_t n, int mode, double target_rms, 
 pgk_status pgk_audio_resample(const float* x, float* out, const float* taps, long long n, long long n_out, int ratio, int n_taps, int src, int dst,
                               pgk_stream s);
 
+/* ------------------------------------------------------------------- diffusion ------ */
+/* ops_diffusion.hip: the row kernels of a diffusion transformer (DiT) block.  x, residual, sum_out, y are [batch, tokens,
+ * features] in dt; for every token row r of batch element b
+ *     mode 0:  s = residual ? residual[r] + g_b * x[r] : x[r];   sum_out[r] = round(s);
+ *              y[r] = round((norm ? LN(s) : s) * (1 + scale_b) + shift_b)
+ *     mode 1:  y[r] = round(residual[r] + g_b * (LN(x[r]) * (1 + scale_b) + shift_b))     (the reference's adaln_zero)
+ * LN(s) = (s - mean) / sqrt(var + eps): population variance, no gamma / beta, on the unrounded fp32 s.  Each of gate / scale /
+ * shift is tab[features] + vec[b * stride .. + features] in vec_dt (dt or PGK_F32); either part may be NULL (both NULL: g = 1,
+ * scale = 0, shift = 0), stride 0 gives a batch-independent vector.  residual, sum_out and y may each be NULL in mode 0 (at
+ * least one of sum_out / y is required; a gate needs a residual); mode 1 needs residual and y and always normalises.  sum_out
+ * may alias residual and y may alias x.  A wave per row with the row in registers when features is a whole number of 16-byte
+ * vectors within 64 * 8 of them and every pointer and vector row is 16-byte aligned, else a 256-thread block per row. */
+pgk_status pgk_adaln_fused(const void* x, const void* residual, void* sum_out, void* y, const void* gate_tab, const void* gate_vec,
+                           int64_t gate_stride, const void* scale_tab, const void* scale_vec, int64_t scale_stride,
+                           const void* shift_tab, const void* shift_vec, int64_t shift_stride, int batch, int tokens, int features,
+                           float eps, int norm, int mode, pgk_dtype dt, pgk_dtype vec_dt, pgk_stream s);
+/* Host only: "adaln_wave" or "adaln_block" from the function the launcher calls; NULL and pgk_last_error when invalid.  aligned:
+ * every pointer the launcher tests (rows, tables, vectors and their strides) is on a 16-byte boundary. */
+const char* pgk_adaln_plan(int features, pgk_dtype dt, int aligned);
+/* in [B, C, H, W] -> out [B * (H/p) * (W/p), C * p * p]: rows in row-major (h, w) patch order, columns (c, ph, pw).  A pure move
+ * of 2- or 4-byte elements; H or W no multiple of p is PGK_ERR_INVALID. */
+pgk_status pgk_patchify(const void* in, void* out, int B, int C, int H, int W, int p, pgk_dtype dt, pgk_stream s);
+/* in [B * (H/p) * (W/p), p * p * Co] with columns (ph, pw, c) -> out [B, Co, H, W]. */
+pgk_status pgk_unpatchify(const void* in, void* out, int B, int Co, int H, int W, int p, pgk_dtype dt, pgk_stream s);
+
 /* ------------------------------------------------------------------------ RCCL ------ */
 /* New functionality (the reference is single-GPU, docs/scheduler.md:358): data-parallel batch
  * decode over one 8xMI355X node.  One process per GPU; RCCL over xGMI only for the one-time weight

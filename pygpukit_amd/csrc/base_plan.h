@@ -60,6 +60,13 @@ inline int norm_grid(int rows, int features, size_t item, bool ptrs_aligned) {
     return norm_pick(features, item, ptrs_aligned) == NORM_WAVE ? ceil_div(rows, NORM_WAVES) : rows;
 }
 
+// ---- pgk_adaln_fused (ops_diffusion.hip): the same two kernels, rows of [batch, tokens, features] ------------------------------
+// ptrs_aligned: x, residual, sum_out, y, every table and vector that is given, and every vector's batch stride in bytes
+inline NormKernel adaln_pick(int features, size_t item, bool ptrs_aligned) { return norm_pick(features, item, ptrs_aligned); }
+inline const char* adaln_leaf(int features, size_t item, bool ptrs_aligned) {
+    return adaln_pick(features, item, ptrs_aligned) == NORM_WAVE ? "adaln_wave" : "adaln_block";
+}
+
 // ---- pgk_rope_inplace: a thread per (x[d], x[d + D/2]) pair, 256 per block ------------------------------------------------------
 inline int rope_grid(size_t pairs) { return (int)((pairs + 255) / 256 > 2048 ? 2048 : (pairs + 255) / 256); }
 
