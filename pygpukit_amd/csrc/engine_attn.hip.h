@@ -689,16 +689,44 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
             xf[0] = u.x; xf[1] = u.y; xf[2] = u.z; xf[3] = u.w; xf[4] = v.x; xf[5] = v.y; xf[6] = v.z; xf[7] = v.w;
         }
         float* outp = a.opart + ((size_t)b * a.hkv + kvh) * a.H;
-        for (int p = 0; p < npass; ++p) {
-            const int row = r0 + p * RPP + rip;
-            uint4 w = (p < PRE) ? pre[p < PRE ? p : 0] : load_nt16(wbase + (size_t)row * ldw);
-            float wf[8];
-            WTraits<bf16>::decode(w, wf);
-            float acc = 0.f;
+        // The pass counts the engine's row slicing produces (at most PRE preloaded passes per workgroup) as compile-time
+        // constants: fully unrolled, pre[] read with static indices (registers, no indexing through memory), and the NP
+        // independent cross-lane sums next to each other for the scheduler to interleave.  Per pass the same eight FMAs
+        // and the same reduction as the runtime loop below, which stays for any other slicing.
+        auto wo_fixed = [&](auto np_c) {
+            constexpr int NP = decltype(np_c)::value;
+            static_assert(NP <= PRE, "every pass of a fixed count is preloaded");
+            float acc[NP];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc = fmaf(wf[j], xf[j], acc);
-            acc = group_sum<LPW>(acc);
-            if (lr == 0) outp[row] = acc;
+            for (int p = 0; p < NP; ++p) {
+                float wf[8];
+                WTraits<bf16>::decode(pre[p], wf);
+                acc[p] = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[p] = fmaf(wf[j], xf[j], acc[p]);
+            }
+#pragma unroll
+            for (int p = 0; p < NP; ++p) acc[p] = group_sum<LPW>(acc[p]);
+            if (lr == 0) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) outp[r0 + p * RPP + rip] = acc[p];
+            }
+        };
+        if (npass == 4) wo_fixed(std::integral_constant<int, 4>{});
+        else if (npass == 2) wo_fixed(std::integral_constant<int, 2>{});
+        else if (npass == 1) wo_fixed(std::integral_constant<int, 1>{});
+        else {
+            for (int p = 0; p < npass; ++p) {
+                const int row = r0 + p * RPP + rip;
+                uint4 w = (p < PRE) ? pre[p < PRE ? p : 0] : load_nt16(wbase + (size_t)row * ldw);
+                float wf[8];
+                WTraits<bf16>::decode(w, wf);
+                float acc = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc = fmaf(wf[j], xf[j], acc);
+                acc = group_sum<LPW>(acc);
+                if (lr == 0) outp[row] = acc;
+            }
         }
     } else {
         const size_t ob = ((size_t)b * a.hq + (size_t)kvh * G) * D;

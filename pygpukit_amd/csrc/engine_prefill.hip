@@ -40,6 +40,16 @@ __global__ void embed_rows_kernel(const bf16* embed, const int32_t* tokens, floa
     for (int i = threadIdx.x; i < H; i += blockDim.x) h[(size_t)s * H + i] = to_f(row[i]);
 }
 
+// Up to EMBED_ARG_TOKENS token ids travel by value in the kernel arguments (512 bytes): no host-to-device copy of the ids,
+// no synchronise for the caller's (possibly pageable) buffer and no launch into a stream that just went idle.
+constexpr int EMBED_ARG_TOKENS = 128;
+struct EmbedTokenArgs { int32_t id[EMBED_ARG_TOKENS]; };
+__global__ void embed_rows_arg_kernel(const bf16* embed, float* h, int H, EmbedTokenArgs tokens) {
+    const int s = blockIdx.x;
+    const bf16* row = embed + (size_t)tokens.id[s] * H;
+    for (int i = threadIdx.x; i < H; i += blockDim.x) h[(size_t)s * H + i] = to_f(row[i]);
+}
+
 // h32[s] += sum of the split-K slabs of the projection that precedes this norm (if any), written back;
 // x_bf16[s] = rmsnorm(h32[s]) * gamma.  One 256-thread workgroup per row, 4 elements per thread per trip;
 // the slab loads are unconditional (clamped slab index, masked add) so they share one memory round trip.
@@ -347,15 +357,18 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
         if (pgk_status r = pgk_malloc(&e->pf, need)) return r;
         e->pf_bytes = need;
     }
-    if (n > e->pf_tokens_cap) {
+    const bool ids_by_value = n <= EMBED_ARG_TOKENS;   // the embedding kernel is the ids' only reader: short prompts pass them as arguments
+    if (!ids_by_value && n > e->pf_tokens_cap) {
         if (e->pf_tokens) { PGK_CHECK_HIP(hipStreamSynchronize(st)); pgk_free(e->pf_tokens); }
         if (pgk_status r = pgk_malloc((void**)&e->pf_tokens, (size_t)n * 4)) return r;
         e->pf_tokens_cap = n;
     }
     for (int i = 0; i < n; ++i)
         PGK_REQUIRE(h_tokens[i] >= 0 && h_tokens[i] < c.vocab_size, "pgk_engine_prefill: token %d out of range", h_tokens[i]);
-    PGK_CHECK_HIP(hipMemcpyAsync(e->pf_tokens, h_tokens, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    PGK_CHECK_HIP(hipStreamSynchronize(st));  // h_tokens may be pageable: make the copy complete before returning control
+    if (!ids_by_value) {
+        PGK_CHECK_HIP(hipMemcpyAsync(e->pf_tokens, h_tokens, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        PGK_CHECK_HIP(hipStreamSynchronize(st));  // h_tokens may be pageable: make the copy complete before returning control
+    }
     const bool fp8 = c.weight_format == 1 || c.weight_format == 2;
     const bool fp8act = c.weight_format == 2 && n > 128;   // fp8 x fp8 MFMA projections, activations quantised on the fly
     layout(e->pf);
@@ -393,7 +406,13 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
     auto norm = [&](const bf16* gamma, bool to_fp8 = false) -> pgk_status {
         return rmsnorm_slabs(h32, gamma, x, n, H, c.norm_eps, slabs, &pending, to_fp8 ? q8 : nullptr, to_fp8 ? q8s : nullptr, st, nullptr);
     };
-    embed_rows_kernel<<<n, 256, 0, st>>>(e->embed, e->pf_tokens, h32, H);
+    if (ids_by_value) {
+        EmbedTokenArgs ids{};
+        for (int i = 0; i < n; ++i) ids.id[i] = h_tokens[i];
+        embed_rows_arg_kernel<<<n, 256, 0, st>>>(e->embed, h32, H, ids);
+    } else {
+        embed_rows_kernel<<<n, 256, 0, st>>>(e->embed, e->pf_tokens, h32, H);
+    }
     PGK_LAUNCH_CHECK();
     const int kv_len = start_pos + n;
     int ss_n = 0;    // partial sums per row in pk_ss (carried norms)
