@@ -49,8 +49,11 @@ constexpr int SMP_WHOLE_K = 256;   // candidates the whole-vocabulary nucleus pa
 
 using u64 = unsigned long long;
 
-__device__ __forceinline__ uint32_t smp_key(float z) {   // larger z -> larger key; -0 < +0 is harmless
-    const uint32_t b = __float_as_uint(z);
+// larger z -> larger key.  -0.0 takes the key of +0.0: the two are one value, so a tie between them goes to the lowest
+// index like any other (a padded vocabulary row with zero lm_head weights yields zeros of both signs).
+__device__ __forceinline__ uint32_t smp_key(float z) {
+    uint32_t b = __float_as_uint(z);
+    if (b == 0x80000000u) b = 0u;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float smp_unkey(uint32_t k) { return (k & 0x80000000u) ? __uint_as_float(k & 0x7fffffffu) : __uint_as_float(~k); }
