@@ -1,5 +1,6 @@
-// Split-KV decode attention core (flash-decoding) for gfx950, shared by the op-level
-// sdpa_causal_fixed_cache (ops_attention.hip) and the fused decode step (engine_attn.hip.h).
+// Split-KV decode attention core (flash-decoding) for gfx950, shared by the op-level fixed-cache entries
+// (decode_phase1_kernel / launch_split_decode at the end of this file: ops_attention.hip, ops_llama4.hip,
+// ops_posenc.hip), paged attention's combine (ops_paged.hip) and the fused decode step (engine_attn.hip.h).
 //
 // One workgroup = 4 waves owns one KV head and one contiguous chunk of cached positions and
 // serves all G = Hq/Hkv query heads of that KV head from a single pass over K and V (the
@@ -12,6 +13,7 @@
 
 #include <type_traits>
 
+#include "attn_plan.h"
 #include "pgk_device.hip.h"
 
 // diagnostic builds (-DPGK_PHASE_STAMPS): stamps inside the walk, parked like TLStamp::phase (engine_common.hip.h)
@@ -80,6 +82,14 @@ struct DecodeState {
 // Additive score term of decode_walk: B{}(g, pos) is added in fp32 to head g's score of cache row pos.  The default adds
 // nothing and compiles to the walk without a hook.
 struct DecodeNoBias {};
+
+// ALiBi: -slope[head] * (ctx - 1 - pos) added in fp32 to the score of cache row pos before the online softmax
+template <int G>
+struct AlibiDecodeBias {
+    float slope[G];
+    int last;                                       // the query's position: context_len - 1
+    __device__ __forceinline__ float operator()(int g, int pos) const { return -slope[g] * (float)(last - pos); }
+};
 
 // Walk positions [c0, c1) of one KV head's cache rows (row stride D elements).
 // qf[g][8]: this lane's slice of the G pre-scaled queries.  Wave `wid` of 4 takes every 4th
@@ -334,6 +344,7 @@ __device__ __forceinline__ float decode_combine(const float* recs, int nsplit, i
 }
 
 // Phase 2 of the op-level split-KV decode: one block per query head merges the head's `nsplit` chunk records.
+// pgk_paged_attention_v1 launches it with a block per (sequence, head): blockIdx.x = seq * heads + head.
 template <class T, int D>
 __global__ void decode_phase2_kernel(const float* ws, T* out, int nsplit) {
     const int h = blockIdx.x;
@@ -347,6 +358,96 @@ __device__ __host__ __forceinline__ int decode_chunk_len(int ctx, int nsplit, in
     int c = (ctx + nsplit - 1) / nsplit;
     c = (c + gran - 1) / gran * gran;  // whole position-group steps (4 waves x 64 / (D/8) rows: 32 at D = 64, 16 at D = 128)
     return c < gran ? gran : c;
+}
+
+// ---- op-level split-KV decode of ONE query row over a fixed cache [Hkv][max_seq][D] ----------------------------------------------
+// Last argument of decode_phase1_kernel, as FlashPlain / FlashIrope / FlashAlibi are flash_fwd_kernel's.  The context length
+// (DecodeIrope: the query's position) comes from the host or, under a captured graph, from ctx_buf[0] / pos_buf[0].
+//   DecodePlain  pgk_sdpa_fixed_cache        (ops_attention.hip): rows 0 .. ctx - 1, q * scale
+//   DecodeIrope  pgk_sdpa_irope_fixed_cache  (ops_llama4.hip): rows 0 .. pos (clamped to the cache), and t(pos) * scale multiplies
+//                                            the fp32 q values - Q * t is never rounded to 16 bits
+//   DecodeAlibi  pgk_sdpa_alibi_fixed_cache  (ops_posenc.hip): as DecodePlain, plus AlibiDecodeBias on every score
+struct DecodePlain { int host_ctx; const int32_t* ctx_buf; float scale; };
+struct DecodeIrope { int host_pos; const int32_t* pos_buf; float scale, attn_scale, floor_scale; };
+struct DecodeAlibi { int host_ctx; const int32_t* ctx_buf; float scale; const float* slopes; };   // slopes: [Hq] fp32
+
+// Phase 1: workgroup (chunk, group of G consecutive query heads of one kv head: G divides Hq / Hkv) -> G partial records.
+template <class T, int D, int G, class X>
+__global__ __launch_bounds__(256) void decode_phase1_kernel(const T* q, const T* kc, const T* vc, float* ws, int hq, int hkv,
+                                                            int max_seq, int nsplit, X ex) {
+    constexpr bool IROPE = std::is_same<X, DecodeIrope>::value, ALIBI = std::is_same<X, DecodeAlibi>::value;
+    constexpr int LPR = D / 8, PPW = 64 / LPR, RS = D + 2;
+    __shared__ float lds[4 * PPW * G * RS];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int ctx;
+    float qmul = ex.scale;
+    if constexpr (IROPE) {
+        const int pos = max(ex.pos_buf ? ex.pos_buf[0] : ex.host_pos, 0);
+        ctx = min(pos, max_seq - 1) + 1;
+        qmul = irope_temperature(pos, ex.attn_scale, ex.floor_scale) * ex.scale;
+    } else {
+        ctx = min(ex.ctx_buf ? ex.ctx_buf[0] : ex.host_ctx, max_seq);
+        if constexpr (ALIBI) ctx = max(ctx, 0);
+    }
+    const int h0 = blockIdx.y * G;
+    const int kv_head = h0 / (hq / hkv);
+    const int chunk = decode_chunk_len(ctx, nsplit);
+    const int c0 = min(blockIdx.x * chunk, ctx), c1 = min(c0 + chunk, ctx);
+    float qf[G][8];
+    const int sub = lane % LPR;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        KVLoad<T>::load8(q + (size_t)(h0 + g) * D + sub * 8, qf[g]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[g][j] *= qmul;
+    }
+    DecodeState<G> st;
+    st.init();
+    const T* kbase = kc + (size_t)kv_head * max_seq * D;
+    const T* vbase = vc + (size_t)kv_head * max_seq * D;
+    if constexpr (ALIBI) {
+        AlibiDecodeBias<G> bias;
+        bias.last = ctx - 1;
+#pragma unroll
+        for (int g = 0; g < G; ++g) bias.slope[g] = ex.slopes[h0 + g];
+        decode_walk<T, D, G>(kbase, vbase, c0, c1, qf, lane, wid, st, bias);
+    } else {
+        decode_walk<T, D, G>(kbase, vbase, c0, c1, qf, lane, wid, st);
+    }
+    decode_block_merge<D, G>(st, lds, ws + ((size_t)h0 * nsplit + blockIdx.x) * RS, (size_t)nsplit * RS, lane, wid);
+}
+
+// Phase 1 over decode_nsplit(max_seq) chunks, then phase 2.  ws: pgk_sdpa_decode_workspace_bytes(hq, D, max_seq)
+template <class T, int D, class X>
+static pgk_status launch_split_decode(const void* q, const void* kc, const void* vc, void* out, void* ws, int hq, int hkv, int max_seq,
+                                      const X& ex, hipStream_t st) {
+    constexpr bool FIVE = !std::is_same<X, DecodePlain>::value;
+    const int nsplit = decode_nsplit(max_seq), G = decode_heads_per_group(hq, hkv, nsplit, FIVE);
+    auto phase1 = [&](auto g) {
+        decode_phase1_kernel<T, D, decltype(g)::value, X><<<dim3(nsplit, hq / G), 256, 0, st>>>((const T*)q, (const T*)kc, (const T*)vc,
+                                                                                             (float*)ws, hq, hkv, max_seq, nsplit, ex);
+    };
+    switch (G) {
+        case 1: phase1(std::integral_constant<int, 1>{}); break;
+        case 2: phase1(std::integral_constant<int, 2>{}); break;
+        case 4: phase1(std::integral_constant<int, 4>{}); break;
+        case 5: if constexpr (FIVE) phase1(std::integral_constant<int, 5>{}); break;
+    }
+    decode_phase2_kernel<T, D><<<hq, D, 0, st>>>((const float*)ws, (T*)out, nsplit);
+    PGK_LAUNCH_CHECK();
+    return PGK_OK;
+}
+
+// the 16-bit-only entries: the caller has checked dt in {bf16, f16} and d in {64, 128}
+template <class X>
+static pgk_status launch_split_decode16(pgk_dtype dt, int d, const void* q, const void* kc, const void* vc, void* out, void* ws, int hq,
+                                        int hkv, int max_seq, const X& ex, hipStream_t st) {
+    if (dt == PGK_BF16) {
+        if (d == 128) return launch_split_decode<bf16, 128>(q, kc, vc, out, ws, hq, hkv, max_seq, ex, st);
+        return launch_split_decode<bf16, 64>(q, kc, vc, out, ws, hq, hkv, max_seq, ex, st);
+    }
+    if (d == 128) return launch_split_decode<f16, 128>(q, kc, vc, out, ws, hq, hkv, max_seq, ex, st);
+    return launch_split_decode<f16, 64>(q, kc, vc, out, ws, hq, hkv, max_seq, ex, st);
 }
 
 }  // namespace pgk

@@ -466,12 +466,7 @@ pgk_status pgk_engine_create(const pgk_model_config_t* cfg, const void* embed, c
     e->final_norm = (const bf16*)final_norm;
     e->layers.assign(layers, layers + c.num_layers);
     int nsplit = (c.max_seq_len + 63) / 64;   // ~64 cached positions per workgroup: one KV batch per wave
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            e->cu_count = prop.multiProcessorCount;
-    }
+    e->cu_count = device_cu_count();
     e->nsplit = nsplit < 1 ? 1 : (nsplit > 64 ? 64 : nsplit);
     e->lm_blocks = 1024;
     // fused attention + o_proj: short contexts, bf16 W_o, and a row slicing that tiles the workgroup

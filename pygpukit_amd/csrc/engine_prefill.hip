@@ -1,6 +1,7 @@
 // Prefill of the native engine (bf16 activations, fp32 residual stream), its own translation unit like engine_batched.hip;
 // the decode step's packed path shares two host entries with it (rmsnorm_slabs, packed_mlp_carried: engine_state.hip.h).
 
+#include "attn_plan.h"
 #include "engine_gemv.hip.h"
 #include "engine_state.hip.h"
 #include "gemm_epilogues.hip.h"
@@ -17,9 +18,6 @@ pgk_status engine_gemm_nt_slabs(const bf16* A, const void* W, float* slabs, int 
 pgk_status gemm_fp8_nt(const uint8_t* a, const float* sa, const uint8_t* w, const bf16* sw, void* c, bool accum_f32, int M,
                        int N, int K, hipStream_t st);
 pgk_status quantize_fp8_rows_bf16(const bf16* x, uint8_t* out, float* scale, int M, int K, hipStream_t st);
-bool sdpa_flash_enabled();                                     // ops_attention.hip: PYGPUKIT_FLASH_ATTENTION
-pgk_status flash_prefill_q8(const void* q, const void* k, const void* v, uint8_t* q8, float* q8s, int hq, int hkv, int q_len, int kv_len,
-                            float scale, long long qh, long long qs, long long kh, long long ks, hipStream_t st);   // ops_flash.hip
 bool engine_gemm_qkv_heads_ok(int M, int N, int K);            // ops_gemm.hip: QKV projection with per-head norm + RoPE + cache write as its epilogue
 pgk_status engine_gemm_qkv_heads_nt(const bf16* A, const bf16* W, bf16* qkv, int M, int N, int K, const QkvHeadArgs& hd, hipStream_t st, bool packed = false);
 bool engine_gemm_swiglu_ok(int M, int I, int K, bool fp8);     // ops_gemm.hip: gate / up projection with the SwiGLU epilogue

@@ -4,8 +4,8 @@
 
 #include <type_traits>
 
+#include "attn_plan.h"
 #include "pgk_device.hip.h"
-#include "pgk_internal.h"
 
 namespace pgk {
 
@@ -24,26 +24,6 @@ template <class T> __device__ __forceinline__ uint32_t pack16x2(float lo, float 
 template <> __device__ __forceinline__ uint32_t pack16x2<bf16>(float lo, float hi) { return pack_bf16x2(lo, hi); }
 template <> __device__ __forceinline__ uint32_t pack16x2<f16>(float lo, float hi) {
     return (uint32_t)__builtin_bit_cast(uint16_t, static_cast<_Float16>(lo)) | ((uint32_t)__builtin_bit_cast(uint16_t, static_cast<_Float16>(hi)) << 16);
-}
-
-struct FlashStrides { long long qh, qs, kh, ks, oh, os; };
-
-constexpr int FL_BQ = 128, FL_BKV = 64, FL_THREADS = 256;
-
-// Llama-4 iRoPE temperature of a query position (reference: native/ops/nn/llama4_kernels.cuh:228):
-//   t = log1pf(floorf((float)(pos + 1) / floor_scale)) * attn_scale + 1, every step rounded to fp32 in that order.
-// log1pf is taken as the CORRECTLY ROUNDED value (evaluated in double, rounded once) and the multiply-add is not
-// contracted into an FMA, so a host restatement that rounds after every step reproduces t bit for bit whatever
-// libm it runs on.  One evaluation per query row, outside every loop.
-__device__ __forceinline__ float irope_temperature(long long pos, float attn_scale, float floor_scale) {
-#pragma clang fp contract(off)
-    const float steps = floorf((float)(pos + 1) / floor_scale);
-    const float lg = (float)log1p((double)steps);
-    const float scaled = lg * attn_scale;
-    return scaled + 1.0f;
-}
-__device__ __forceinline__ long long irope_position(const void* positions, int i, int pos_is_i64) {
-    return pos_is_i64 ? (long long)static_cast<const int64_t*>(positions)[i] : (long long)static_cast<const int32_t*>(positions)[i];
 }
 
 // Optional last argument of flash_fwd_kernel (ops_flash.hip).  FlashPlain: sdpa_causal, mask offset kv_len - q_len, one
@@ -83,17 +63,6 @@ struct FlashSplit {
     uint8_t* q8;
     float* q8s;
 };
-
-// KV runs per query tile: enough workgroups for two per CU (the kernels' occupancy), never more runs than the
-// shortest useful run of two KV tiles allows for the heaviest query tile
-inline int flash_nsplit(int nqt, int hq, int kv_len) {
-    int nsplit = 1, dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    const long long wgs = (long long)nqt * hq;
-    while (nsplit < 4 && wgs * nsplit < 2LL * cus && ceil_div(kv_len, FL_BKV) >= 4 * (nsplit * 2)) nsplit *= 2;
-    return nsplit;
-}
 
 // out[q][head][:] = sum_s w_s o_s / sum_s w_s,  w_s = l_s 2^(m_s - max m): one thread per 8 output elements
 template <class T, int D>

@@ -32,8 +32,6 @@ template <class T> __device__ __forceinline__ uint16_t to_bits16(float f);
 template <> __device__ __forceinline__ uint16_t to_bits16<bf16>(float f) { return f_to_bf16_bits(f); }
 template <> __device__ __forceinline__ uint16_t to_bits16<f16>(float f) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f)); }
 
-struct AttnStrides { long long qh, qs, kh, ks, oh, os; };
-
 constexpr int FA_BQ = 64, FA_BKV = 64;
 
 // [rows][64 x 16-bit] tile, 128-byte rows, 16-byte chunk kc XOR-swizzled by the row
@@ -46,7 +44,7 @@ template <int D> __device__ __forceinline__ int tD_off(int row, int kc) {
 
 template <class T, int D>
 __global__ __launch_bounds__(256) void flash_prefill_kernel(const T* q, const T* k, const T* v, T* out, int hq, int hkv,
-                                                            int q_len, int kv_len, float scale, AttnStrides sd) {
+                                                            int q_len, int kv_len, float scale, FlashStrides sd) {
     constexpr int NC = D / 8;          // 16-byte chunks per K row
     constexpr int KS = D / 32;         // k-steps for Q.K^T
     constexpr int DT = D / 16;         // output column tiles
@@ -194,7 +192,7 @@ __device__ __forceinline__ int sa_voff(int row, int ch) { return row * 256 + ((c
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void attn_short_kernel(const bf16* q, const bf16* k, const bf16* v, bf16* out, int hq, int hkv,
-                                                             int q_len, int kv_len, float scale, AttnStrides sd) {
+                                                             int q_len, int kv_len, float scale, FlashStrides sd) {
     constexpr int D = 128, NT = 8;
     __shared__ __attribute__((aligned(16))) char k_lds[128 * 256];
     __shared__ __attribute__((aligned(16))) char v_lds[128 * 256];
@@ -318,7 +316,7 @@ __global__ __launch_bounds__(64 * NW) void attn_short_kernel(const bf16* q, cons
 // CAUSAL = false is sdpa_noncausal's fallback: every row attends all kv_len keys.
 template <class T, bool CAUSAL = true>
 __global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k, const T* v, T* out, int hq, int hkv,
-                                                         int q_len, int kv_len, int d, float scale, AttnStrides sd) {
+                                                         int q_len, int kv_len, int d, float scale, FlashStrides sd) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sc = reinterpret_cast<float*>(smem);  // [kv_len]
     __shared__ float red[16];
@@ -356,53 +354,14 @@ __global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k,
     }
 }
 
-// ---- flash-decoding (q_len == 1) ---------------------------------------------------------------
-template <class T, int D, int G>
-__global__ __launch_bounds__(256) void decode_phase1_kernel(const T* q, const T* kc, const T* vc, float* ws, int hq,
-                                                            int hc, int max_seq, float scale, int host_ctx,
-                                                            const int32_t* ctx_buf, int nsplit) {
-    constexpr int LPR = D / 8, PPW = 64 / LPR, RS = D + 2;
-    __shared__ float lds[4 * PPW * G * RS];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int ctx = min(ctx_buf ? ctx_buf[0] : host_ctx, max_seq);
-    const int hgroup = blockIdx.y;                  // group of G consecutive query heads
-    const int h0 = hgroup * G;
-    const int cache_head = h0 / (hq / hc);          // all G heads share it (G divides Hq/Hc, or Hc == Hq and G == 1)
-    const int chunk = decode_chunk_len(ctx, nsplit);
-    const int c0 = min(blockIdx.x * chunk, ctx), c1 = min(c0 + chunk, ctx);
-    float qf[G][8];
-    const int sub = lane % LPR;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        KVLoad<T>::load8(q + (size_t)(h0 + g) * D + sub * 8, qf[g]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[g][j] *= scale;
-    }
-    DecodeState<G> st;
-    st.init();
-    decode_walk<T, D, G>(kc + (size_t)cache_head * max_seq * D, vc + (size_t)cache_head * max_seq * D, c0, c1, qf, lane,
-                         wid, st);
-    decode_block_merge<D, G>(st, lds, ws + ((size_t)h0 * nsplit + blockIdx.x) * RS, (size_t)nsplit * RS, lane, wid);
-}
-
-int decode_nsplit(int max_seq) {        // also the split count of pgk_sdpa_irope_fixed_cache (ops_llama4.hip)
-    int n = (max_seq + 255) / 256;  // ~256 positions per chunk at full context
-    if (n < 1) n = 1;
-    return n > 64 ? 64 : n;
-}
-
 template <class T, int D>
 static pgk_status launch_prefill(const T* q, const T* k, const T* v, T* out, int hq, int hkv, int q_len, int kv_len,
-                                 float scale, const AttnStrides& sd, hipStream_t st) {
+                                 float scale, const FlashStrides& sd, hipStream_t st) {
     dim3 grid(ceil_div(q_len, FA_BQ), hq);
     flash_prefill_kernel<T, D><<<grid, 256, 0, st>>>(q, k, v, out, hq, hkv, q_len, kv_len, scale, sd);
     PGK_CHECK_HIP(hipGetLastError());
     return PGK_OK;
 }
-
-pgk_status flash_prefill(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
-                         float scale, long long qh, long long qs, long long kh, long long ks, long long oh, long long os,
-                         int dt16, hipStream_t st);
 
 // The reference's A/B switches, same names and values (native/ops/nn/attention/sdpa_causal.inl:380-447), read per call:
 //   PYGPUKIT_FLASH_ATTENTION  "0"/"false": never the tiled MFMA flash kernels (one-workgroup-per-row fallback, kv_len <= 15360);
@@ -421,63 +380,41 @@ static bool flash_decoding_off() {
 
 bool sdpa_flash_enabled() { return !flash_attention_off(); }   // for the engine's direct use of ops_flash.hip
 
-template <class T>
+// pgk_sdpa_causal (CAUSAL) and pgk_sdpa_noncausal on the kernel attn_plan.h picks.  Non-causal is the second-generation flash
+// kernel with the FlashFull policy at EVERY q_len (the first-generation and one-tile kernels stay causal-only); float32, other
+// head dims, misaligned buffers and PYGPUKIT_FLASH_ATTENTION=0 take the one-workgroup-per-row fallback in either form.
+template <class T, bool CAUSAL>
 static pgk_status sdpa_dispatch(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len,
-                                int kv_len, int d, float scale, const AttnStrides& sd, hipStream_t st) {
-    const bool mfma_ok = !std::is_same<T, float>::value && (d == 64 || d == 128) && aligned16(q) && aligned16(k) &&
-                         aligned16(v) && sd.qs % 8 == 0 && sd.ks % 8 == 0 && sd.qh % 8 == 0 && sd.kh % 8 == 0 && !flash_attention_off();
-    if constexpr (!std::is_same<T, float>::value) {
-        // second generation: 128-row query tiles, transposed-score orientation (ops_flash.hip); the first-generation
-        // kernel keeps the short prompts, where its 64-row tiles give twice the workgroups
-        const bool gen2_ok = mfma_ok && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 && sd.os % 4 == 0 && sd.oh % 4 == 0;
-        if (gen2_ok && q_len > 128)
-            return flash_prefill(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd.qh, sd.qs, sd.kh, sd.ks, sd.oh, sd.os,
-                                 std::is_same<T, f16>::value ? 1 : 0, st);
-        if constexpr (std::is_same<T, bf16>::value) {
-            // the whole context in one tile (attn_short_kernel)
-            if (gen2_ok && d == 128 && kv_len <= 128) {
+                                int kv_len, int d, float scale, const FlashStrides& sd, hipStream_t st) {
+    constexpr bool HALF = !std::is_same<T, float>::value, BF16 = std::is_same<T, bf16>::value;
+    const bool in16 = aligned16(q) && aligned16(k) && aligned16(v), out8 = (reinterpret_cast<uintptr_t>(out) & 7u) == 0;
+    const SdpaKernel pick = CAUSAL ? sdpa_causal_pick(HALF, BF16, d, q_len, kv_len, in16, out8, sd, !flash_attention_off())
+                                   : sdpa_full_pick(HALF, d, in16, out8, sd, !flash_attention_off());
+    if constexpr (HALF) {
+        const int dt16 = std::is_same<T, f16>::value ? 1 : 0;
+        if (pick == SDPA_FLASH2)
+            return CAUSAL ? flash_prefill(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, dt16, st)
+                          : flash_prefill_full(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, dt16, st);
+    }
+    if constexpr (HALF && CAUSAL) {
+        if constexpr (BF16) {
+            if (pick == SDPA_ONE_TILE) {
                 attn_short_kernel<2><<<dim3(ceil_div(q_len, 32), hq), 128, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, hq, hkv,
                                                                                   q_len, kv_len, scale, sd);
                 PGK_CHECK_HIP(hipGetLastError());
                 return PGK_OK;
             }
         }
-        if (mfma_ok) {
+        if (pick == SDPA_FLASH1) {
             if (d == 128) return launch_prefill<T, 128>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st);
             return launch_prefill<T, 64>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st);
         }
     }
     const size_t lds = (size_t)kv_len * 4;
     if (lds > 60 * 1024) return set_error(PGK_ERR_UNSUPPORTED, "sdpa: fallback kernel supports kv_len <= 15360 (got %d)", kv_len);
+    if (!CAUSAL && q_len > 65535) return set_error(PGK_ERR_UNSUPPORTED, "sdpa_noncausal: fallback kernel supports q_len <= 65535 (got %d)", q_len);
     dim3 grid(hq, q_len);
-    sdpa_naive_kernel<T><<<grid, 256, lds, st>>>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, d, scale, sd);
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
-}
-
-pgk_status flash_prefill_full(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
-                              float scale, long long qh, long long qs, long long kh, long long ks, long long oh, long long os, int dt16,
-                              hipStream_t st);
-
-// sdpa_noncausal: the second-generation flash kernel with the FlashFull policy at EVERY q_len (the first-generation and
-// one-tile kernels stay causal-only); float32, other head dims, misaligned buffers and PYGPUKIT_FLASH_ATTENTION=0 take
-// the non-causal form of the one-workgroup-per-row fallback.
-template <class T>
-static pgk_status sdpa_full_dispatch(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len,
-                                     int d, float scale, const AttnStrides& sd, hipStream_t st) {
-    if constexpr (!std::is_same<T, float>::value) {
-        const bool gen2_ok = (d == 64 || d == 128) && aligned16(q) && aligned16(k) && aligned16(v) && sd.qs % 8 == 0 && sd.ks % 8 == 0 &&
-                             sd.qh % 8 == 0 && sd.kh % 8 == 0 && !flash_attention_off() && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 &&
-                             sd.os % 4 == 0 && sd.oh % 4 == 0;
-        if (gen2_ok)
-            return flash_prefill_full(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd.qh, sd.qs, sd.kh, sd.ks, sd.oh, sd.os,
-                                      std::is_same<T, f16>::value ? 1 : 0, st);
-    }
-    const size_t lds = (size_t)kv_len * 4;
-    if (lds > 60 * 1024) return set_error(PGK_ERR_UNSUPPORTED, "sdpa: fallback kernel supports kv_len <= 15360 (got %d)", kv_len);
-    if (q_len > 65535) return set_error(PGK_ERR_UNSUPPORTED, "sdpa_noncausal: fallback kernel supports q_len <= 65535 (got %d)", q_len);
-    dim3 grid(hq, q_len);
-    sdpa_naive_kernel<T, false><<<grid, 256, lds, st>>>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, d, scale, sd);
+    sdpa_naive_kernel<T, CAUSAL><<<grid, 256, lds, st>>>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, d, scale, sd);
     PGK_CHECK_HIP(hipGetLastError());
     return PGK_OK;
 }
@@ -496,9 +433,9 @@ pgk_status pgk_sdpa_causal(const void* q, const void* k, const void* v, void* ou
     PGK_REQUIRE(q_len > 0 && kv_len > 0 && d > 0, "pgk_sdpa_causal: bad shape q_len=%d kv_len=%d D=%d", q_len, kv_len, d);
     PGK_REQUIRE(kv_len >= q_len, "pgk_sdpa_causal: kv_len %d < q_len %d", kv_len, q_len);
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
-    const AttnStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
+    const FlashStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
     hipStream_t st = resolve_stream(s);
-    PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_causal", return (sdpa_dispatch<T>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, st)));
+    PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_causal", return (sdpa_dispatch<T, true>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, st)));
     return PGK_OK;
 }
 
@@ -511,9 +448,9 @@ pgk_status pgk_sdpa_noncausal(const void* q, const void* k, const void* v, void*
     PGK_REQUIRE(q_stride_h >= 0 && q_stride_s >= 0 && kv_stride_h >= 0 && kv_stride_s >= 0 && o_stride_h >= 0 && o_stride_s >= 0,
                 "pgk_sdpa_noncausal: negative stride");
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
-    const AttnStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
+    const FlashStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
     hipStream_t st = resolve_stream(s);
-    PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_noncausal", return (sdpa_full_dispatch<T>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, st)));
+    PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_noncausal", return (sdpa_dispatch<T, false>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, st)));
     return PGK_OK;
 }
 
@@ -531,35 +468,21 @@ pgk_status pgk_sdpa_fixed_cache(const void* q, const void* k_cache, const void* 
     PGK_REQUIRE(q_len >= 1, "pgk_sdpa_fixed_cache: q_len=%d", q_len);
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
     hipStream_t st = resolve_stream(s);
-    const int rep = hq / hc;
-    const bool fast = q_len == 1 && (d == 128 || d == 64) && workspace && aligned16(q) && aligned16(k_cache) && aligned16(v_cache) &&
-                      !(flash_decoding_off() && !ctx_buf);
-    if (fast) {
-        const int nsplit = decode_nsplit(max_seq);
-        int G = 1;
-        if (rep % 4 == 0) G = 4; else if (rep % 2 == 0) G = 2;
-        dim3 grid(nsplit, hq / G);
-        float* ws = (float*)workspace;
-#define PGK_DEC(DD, GG)                                                                                               \
-    if (d == DD && G == GG) {                                                                                         \
-        PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_fixed_cache", {                                                              \
-            decode_phase1_kernel<T, DD, GG><<<grid, 256, 0, st>>>((const T*)q, (const T*)k_cache, (const T*)v_cache, ws, hq, hc, \
-                                                                  max_seq, scale, h_context_len, ctx_buf, nsplit);   \
-            decode_phase2_kernel<T, DD><<<hq, DD, 0, st>>>(ws, (T*)out, nsplit);                                      \
-        });                                                                                                           \
-        PGK_LAUNCH_CHECK();                                                                                           \
-        return PGK_OK;                                                                                                \
-    }
-        PGK_DEC(128, 1) PGK_DEC(128, 2) PGK_DEC(128, 4) PGK_DEC(64, 1) PGK_DEC(64, 2) PGK_DEC(64, 4)
-#undef PGK_DEC
+    if (decode_fast(q_len, d, workspace != nullptr, aligned16(q) && aligned16(k_cache) && aligned16(v_cache), flash_decoding_off(),
+                    ctx_buf != nullptr)) {
+        const DecodePlain ex{h_context_len, ctx_buf, scale};
+        PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_fixed_cache", {
+            if (d == 128) return (launch_split_decode<T, 128>(q, k_cache, v_cache, out, workspace, hq, hc, max_seq, ex, st));
+            return (launch_split_decode<T, 64>(q, k_cache, v_cache, out, workspace, hq, hc, max_seq, ex, st));
+        });
     }
     // general path (q_len > 1, other head dims, or no workspace): strided causal SDPA over the cache prefix.
     // A device-resident context length needs the decode path above.
     PGK_REQUIRE(!ctx_buf, "pgk_sdpa_fixed_cache: context_len_buf requires q_len == 1, head_dim 64/128 and a workspace");
     PGK_REQUIRE(h_context_len >= q_len, "sdpa: context_len %d < q_len %d", h_context_len, q_len);
-    const AttnStrides sd{(long long)q_len * d, d, (long long)max_seq * d, d, (long long)q_len * d, d};
+    const FlashStrides sd{(long long)q_len * d, d, (long long)max_seq * d, d, (long long)q_len * d, d};
     PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_fixed_cache",
-                       return (sdpa_dispatch<T>(q, k_cache, v_cache, out, hq, hc, q_len, h_context_len, d, scale, sd, st)));
+                       return (sdpa_dispatch<T, true>(q, k_cache, v_cache, out, hq, hc, q_len, h_context_len, d, scale, sd, st)));
     return PGK_OK;
 }
 

@@ -358,7 +358,7 @@ static pgk_status flash_launch(const T* q, const T* k, const T* v, T* out, int h
                                int kv_seen = 0) {
     const int kv_pad = ceil_div(kv_len, 64) * 64;
     const int nqt = ceil_div(q_len, FL_BQ);
-    const int nsplit = flash_nsplit(nqt, hq, kv_seen > 0 ? kv_seen : kv_len);
+    const int nsplit = flash_nsplit(nqt, hq, kv_seen > 0 ? kv_seen : kv_len, device_cu_count());
     const size_t vt_bytes = (size_t)hkv * D * kv_pad * sizeof(T);
     const size_t po_bytes = nsplit > 1 ? (size_t)nsplit * q_len * hq * D * sizeof(T) : 0;
     const size_t ml_bytes = nsplit > 1 ? (size_t)nsplit * hq * q_len * 2 * sizeof(float) : 0;
@@ -392,73 +392,47 @@ static pgk_status flash_launch(const T* q, const T* k, const T* v, T* out, int h
     return PGK_OK;
 }
 
-// entry used by ops_attention.hip's dispatcher; dt16: 0 = bf16, 1 = f16
-pgk_status flash_prefill(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
-                         float scale, long long qh, long long qs, long long kh, long long ks, long long oh, long long os,
-                         int dt16, hipStream_t st) {
-    const FlashStrides sd{qh, qs, kh, ks, oh, os};
-    if (dt16 == 0) {
-        if (d == 128) return flash_launch<bf16, 128>((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, hq, hkv, q_len, kv_len, scale, sd, st);
-        return flash_launch<bf16, 64>((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, hq, hkv, q_len, kv_len, scale, sd, st);
-    }
-    if (d == 128) return flash_launch<f16, 128>((const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, hq, hkv, q_len, kv_len, scale, sd, st);
-    return flash_launch<f16, 64>((const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, hq, hkv, q_len, kv_len, scale, sd, st);
+// (dt16, d) -> flash_launch<T, D, X> for any policy; dt16: 0 = bf16, 1 = f16, d: 64 or 128
+template <class X>
+static pgk_status flash_launch_any(int dt16, int d, const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len,
+                                   int kv_len, float scale, const FlashStrides& sd, hipStream_t st, X ex, int kv_seen) {
+    auto run = [&](auto* t, auto dd) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return flash_launch<T, decltype(dd)::value, X>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st,
+                                                       nullptr, nullptr, ex, kv_seen);
+    };
+    const std::integral_constant<int, 128> d128;
+    const std::integral_constant<int, 64> d64;
+    if (dt16 == 0) return d == 128 ? run((bf16*)nullptr, d128) : run((bf16*)nullptr, d64);
+    return d == 128 ? run((f16*)nullptr, d128) : run((f16*)nullptr, d64);
 }
 
-// entry used by pgk_sdpa_irope (ops_llama4.hip), which has checked the arguments: scale is 1/sqrt(d); row i sees
-// kv j <= i + causal_offset (>= 0), so an offset beyond kv_len masks nothing and is clamped to it
+// The entries of attn_plan.h; their callers (ops_attention.hip, ops_llama4.hip, ops_posenc.hip) have checked the arguments.
+pgk_status flash_prefill(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d, float scale,
+                         const FlashStrides& sd, int dt16, hipStream_t st) {
+    return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, scale, sd, st, FlashPlain{}, 0);
+}
+
+// every KV run of every query tile is live, so the split heuristic sees all kv_len keys
+pgk_status flash_prefill_full(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
+                              float scale, const FlashStrides& sd, int dt16, hipStream_t st) {
+    return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, scale, sd, st, FlashFull{}, kv_len);
+}
+
+// scale is 1/sqrt(d); row i sees kv j <= i + causal_offset (>= 0), so an offset beyond kv_len masks nothing and is clamped to it
 pgk_status flash_prefill_irope(const void* q, const void* k, const void* v, const void* positions, void* out, int hq, int hkv, int q_len,
-                               int kv_len, int d, float attn_scale, float floor_scale, int causal_offset, long long qh, long long qs,
-                               long long kh, long long ks, long long oh, long long os, int pos_is_i64, int dt16, hipStream_t st) {
-    const FlashStrides sd{qh, qs, kh, ks, oh, os};
+                               int kv_len, int d, float attn_scale, float floor_scale, int causal_offset, const FlashStrides& sd,
+                               int pos_is_i64, int dt16, hipStream_t st) {
     const int off = causal_offset < kv_len ? causal_offset : kv_len;
     const FlashIrope ex{positions, attn_scale, floor_scale, off, pos_is_i64};
-    const float scale = 1.0f / sqrtf((float)d);
     const int kv_seen = (long long)off + q_len < kv_len ? off + q_len : kv_len;
-#define PGK_IROPE_CASE(T, DD) \
-    return flash_launch<T, DD, FlashIrope>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st, nullptr, nullptr, ex, kv_seen)
-    if (dt16 == 0) {
-        if (d == 128) PGK_IROPE_CASE(bf16, 128);
-        PGK_IROPE_CASE(bf16, 64);
-    }
-    if (d == 128) PGK_IROPE_CASE(f16, 128);
-    PGK_IROPE_CASE(f16, 64);
-#undef PGK_IROPE_CASE
+    return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, 1.0f / sqrtf((float)d), sd, st, ex, kv_seen);
 }
 
-// entry used by pgk_sdpa_alibi / pgk_sdpa_alibi_fixed_cache (ops_posenc.hip), which have checked the arguments (scale > 0,
-// kv_len >= q_len); slopes: [hq] fp32 on the device
+// scale > 0, kv_len >= q_len; slopes: [hq] fp32 on the device
 pgk_status flash_prefill_alibi(const void* q, const void* k, const void* v, const float* slopes, void* out, int hq, int hkv, int q_len,
-                               int kv_len, int d, float scale, long long qh, long long qs, long long kh, long long ks, long long oh,
-                               long long os, int dt16, hipStream_t st) {
-    const FlashStrides sd{qh, qs, kh, ks, oh, os};
-    const FlashAlibi ex{slopes};
-#define PGK_ALIBI_CASE(T, DD) \
-    return flash_launch<T, DD, FlashAlibi>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st, nullptr, nullptr, ex)
-    if (dt16 == 0) {
-        if (d == 128) PGK_ALIBI_CASE(bf16, 128);
-        PGK_ALIBI_CASE(bf16, 64);
-    }
-    if (d == 128) PGK_ALIBI_CASE(f16, 128);
-    PGK_ALIBI_CASE(f16, 64);
-#undef PGK_ALIBI_CASE
-}
-
-// entry used by pgk_sdpa_noncausal (ops_attention.hip), which has checked the arguments.  Every KV run of every query tile is
-// live, so the split heuristic sees all kv_len keys.
-pgk_status flash_prefill_full(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
-                              float scale, long long qh, long long qs, long long kh, long long ks, long long oh, long long os, int dt16,
-                              hipStream_t st) {
-    const FlashStrides sd{qh, qs, kh, ks, oh, os};
-#define PGK_FULL_CASE(T, DD) \
-    return flash_launch<T, DD, FlashFull>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, scale, sd, st, nullptr, nullptr, FlashFull{}, kv_len)
-    if (dt16 == 0) {
-        if (d == 128) PGK_FULL_CASE(bf16, 128);
-        PGK_FULL_CASE(bf16, 64);
-    }
-    if (d == 128) PGK_FULL_CASE(f16, 128);
-    PGK_FULL_CASE(f16, 64);
-#undef PGK_FULL_CASE
+                               int kv_len, int d, float scale, const FlashStrides& sd, int dt16, hipStream_t st) {
+    return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, scale, sd, st, FlashAlibi{slopes}, 0);
 }
 
 // engine entry (fp8 x fp8 prefill, bf16, head_dim 128, q_len > 128): causal attention whose result leaves as the o_proj's fp8

@@ -326,7 +326,7 @@ static pgk_status flash_fp8_launch(const bf16* q, const bf16* k, const bf16* v, 
     constexpr int D = 128;
     const int kv_pad = ceil_div(kv_len, 64) * 64;
     const int nqt = ceil_div(q_len, FL_BQ);
-    const int nsplit = flash_nsplit(nqt, hq, kv_len);      // the bf16 kernel's choice: same occupancy, same tile walk
+    const int nsplit = flash_nsplit(nqt, hq, kv_len, device_cu_count());      // the bf16 kernel's choice: same occupancy, same tile walk
     const size_t vt_bytes = up256((size_t)hkv * D * kv_pad * sizeof(bf16));
     const size_t po_bytes = nsplit > 1 ? up256((size_t)nsplit * q_len * hq * D * sizeof(bf16)) : 0;
     const size_t ml_bytes = nsplit > 1 ? up256((size_t)nsplit * hq * q_len * 2 * sizeof(float)) : 0;

@@ -9,15 +9,8 @@
 // flash kernel and the mask offset is an argument, so sdpa_irope runs at sdpa_causal's speed.
 
 #include "attn_core.hip.h"
-#include "flash_common.hip.h"
 
 namespace pgk {
-
-int decode_nsplit(int max_seq);         // ops_attention.hip: the split count pgk_sdpa_decode_workspace_bytes sizes for
-
-pgk_status flash_prefill_irope(const void* q, const void* k, const void* v, const void* positions, void* out, int hq, int hkv, int q_len,
-                               int kv_len, int d, float attn_scale, float floor_scale, int causal_offset, long long qh, long long qs,
-                               long long kh, long long ks, long long oh, long long os, int pos_is_i64, int dt16, hipStream_t st);
 
 // ---- l2norm ----------------------------------------------------------------------------------------------------------
 // features 64 / 128 (the model's [S * H, head_dim] case): a row is held by the LANES = features / Vec<T>::N lanes that one
@@ -162,62 +155,6 @@ __global__ __launch_bounds__(256) void qk_norm_cache_write_kernel(T* q, const T*
     x.store((is_k ? k_cache : v_cache) + ((size_t)h * max_seq + (size_t)row) * D + c * N);
 }
 
-// ---- sdpa_irope_fixed_cache ------------------------------------------------------------------------------------------
-// decode_phase1_kernel of ops_attention.hip with the query's temperature: the position comes from the host or from
-// pos_buf[0], the context is rows 0 .. pos (clamped to the cache), and t(pos) * scale multiplies the fp32 q values -
-// Q * t is never rounded to 16 bits.  Same chunking, records and phase 2 as pgk_sdpa_fixed_cache.
-template <class T, int D, int G>
-__global__ __launch_bounds__(256) void irope_decode_phase1_kernel(const T* q, const T* kc, const T* vc, float* ws, int hq, int hkv,
-                                                                  int max_seq, float scale, float attn_scale, float floor_scale,
-                                                                  int host_pos, const int32_t* pos_buf, int nsplit) {
-    constexpr int LPR = D / 8, PPW = 64 / LPR, RS = D + 2;
-    __shared__ float lds[4 * PPW * G * RS];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int pos = max(pos_buf ? pos_buf[0] : host_pos, 0);
-    const int ctx = min(pos, max_seq - 1) + 1;
-    const float qmul = irope_temperature(pos, attn_scale, floor_scale) * scale;
-    const int h0 = blockIdx.y * G;                  // G consecutive query heads of one kv head (G divides Hq / Hkv)
-    const int kv_head = h0 / (hq / hkv);
-    const int chunk = decode_chunk_len(ctx, nsplit);
-    const int c0 = min(blockIdx.x * chunk, ctx), c1 = min(c0 + chunk, ctx);
-    float qf[G][8];
-    const int sub = lane % LPR;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        KVLoad<T>::load8(q + (size_t)(h0 + g) * D + sub * 8, qf[g]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[g][j] *= qmul;
-    }
-    DecodeState<G> st;
-    st.init();
-    decode_walk<T, D, G>(kc + (size_t)kv_head * max_seq * D, vc + (size_t)kv_head * max_seq * D, c0, c1, qf, lane, wid, st);
-    decode_block_merge<D, G>(st, lds, ws + ((size_t)h0 * nsplit + blockIdx.x) * RS, (size_t)nsplit * RS, lane, wid);
-}
-
-template <class T, int D>
-static pgk_status launch_irope_decode(const void* q, const void* kc, const void* vc, void* out, float* ws, int hq, int hkv, int max_seq,
-                                      float attn_scale, float floor_scale, int host_pos, const int32_t* pos_buf, hipStream_t st) {
-    const int nsplit = decode_nsplit(max_seq), rep = hq / hkv;
-    const float scale = 1.0f / sqrtf((float)D);
-    // Every K / V row is read once per group of G query heads.  1 / 2 / 4 as in pgk_sdpa_fixed_cache; 5 serves Llama-4
-    // Scout's Hq / Hkv = 40 / 8 in one pass, but only where its grid still has a workgroup per CU (256): with fewer the
-    // walk is latency-bound and G = 1's five times as many workgroups win (measured at 40 / 8 heads, D = 128: 8.4 against
-    // 13.7 us in a cache of 512 rows, 17.3 against 19.9 at 4096; 47.3 against 46.0 at 16384, 96.1 against 86.8 at 65536).
-    int G = rep % 4 == 0 ? 4 : rep % 2 == 0 ? 2 : 1;
-    if (G == 1 && rep % 5 == 0 && (long long)nsplit * (hq / 5) >= 256) G = 5;
-    const dim3 grid(nsplit, hq / G);
-#define PGK_IROPE_DEC(GG)                                                                                                              \
-    case GG:                                                                                                                           \
-        irope_decode_phase1_kernel<T, D, GG><<<grid, 256, 0, st>>>((const T*)q, (const T*)kc, (const T*)vc, ws, hq, hkv, max_seq, scale, \
-                                                                   attn_scale, floor_scale, host_pos, pos_buf, nsplit);               \
-        break;
-    switch (G) { PGK_IROPE_DEC(1) PGK_IROPE_DEC(2) PGK_IROPE_DEC(4) PGK_IROPE_DEC(5) }
-#undef PGK_IROPE_DEC
-    decode_phase2_kernel<T, D><<<hq, D, 0, st>>>(ws, (T*)out, nsplit);
-    PGK_LAUNCH_CHECK();
-    return PGK_OK;
-}
-
 }  // namespace pgk
 
 using namespace pgk;
@@ -263,9 +200,9 @@ pgk_status pgk_sdpa_irope(const void* q, const void* k, const void* v, const voi
                 "pgk_sdpa_irope: pointers must be 16-byte aligned and strides multiples of 8 elements");
     PGK_REQUIRE(q_stride_h >= 0 && q_stride_s >= 0 && kv_stride_h >= 0 && kv_stride_s >= 0 && o_stride_h >= 0 && o_stride_s >= 0,
                 "pgk_sdpa_irope: negative stride");
-    return flash_prefill_irope(q, k, v, positions, out, hq, hkv, q_len, kv_len, d, attn_scale, floor_scale, causal_offset, q_stride_h,
-                               q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s, pos_dt == PGK_I64, dt == PGK_BF16 ? 0 : 1,
-                               resolve_stream(s));
+    const FlashStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
+    return flash_prefill_irope(q, k, v, positions, out, hq, hkv, q_len, kv_len, d, attn_scale, floor_scale, causal_offset, sd,
+                               pos_dt == PGK_I64, dt == PGK_BF16 ? 0 : 1, resolve_stream(s));
 }
 
 pgk_status pgk_llama4_qk_norm_cache_write(void* q, const void* k, const void* v, void* k_cache, void* v_cache, int seq, int hq, int hkv,
@@ -306,13 +243,8 @@ pgk_status pgk_sdpa_irope_fixed_cache(const void* q, const void* k_cache, const 
     PGK_REQUIRE(floor_scale > 0.f, "pgk_sdpa_irope_fixed_cache: floor_scale must be positive");
     PGK_REQUIRE(aligned16(q) && aligned16(k_cache) && aligned16(v_cache), "pgk_sdpa_irope_fixed_cache: pointers must be 16-byte aligned");
     hipStream_t st = resolve_stream(s);
-    float* ws = (float*)workspace;
-    if (dt == PGK_BF16) {
-        if (d == 128) return launch_irope_decode<bf16, 128>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
-        return launch_irope_decode<bf16, 64>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
-    }
-    if (d == 128) return launch_irope_decode<f16, 128>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
-    return launch_irope_decode<f16, 64>(q, k_cache, v_cache, out, ws, hq, hkv, max_seq, attn_scale, floor_scale, h_pos, pos_buf, st);
+    const DecodeIrope ex{h_pos, pos_buf, 1.0f / sqrtf((float)d), attn_scale, floor_scale};
+    return launch_split_decode16(dt, d, q, k_cache, v_cache, out, workspace, hq, hkv, max_seq, ex, resolve_stream(s));
 }
 
 }  // extern "C"

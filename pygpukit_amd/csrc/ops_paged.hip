@@ -124,13 +124,6 @@ __global__ __launch_bounds__(256) void paged_attn_kernel(const T* q, const T* kc
     }
 }
 
-template <class T, int D>
-__global__ void paged_combine_kernel(const float* ws, T* out, int nsplit) {
-    const size_t sh = blockIdx.x;   // seq * num_heads + head
-    for (int d = threadIdx.x; d < D; d += blockDim.x)
-        out[sh * D + d] = from_f<T>(decode_combine<D>(ws + sh * nsplit * (D + 2), nsplit, d));
-}
-
 // K_new/V_new rows -> cache slots.  slot = physical_block * block_size + offset; a negative slot is skipped (padding).
 template <int ITEM>
 __global__ void paged_cache_write_kernel(const char* k_new, const char* v_new, char* kc, char* vc, const int32_t* slot_mapping,
@@ -188,9 +181,7 @@ using namespace pgk;
 extern "C" {
 
 size_t pgk_paged_attention_workspace_bytes(int num_seqs, int num_heads, int head_dim, int max_context) {
-    int nsplit = (max_context + 511) / 512;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > 32) nsplit = 32;
+    const int nsplit = paged_nsplit(max_context);
     return nsplit == 1 ? 0 : (size_t)num_seqs * num_heads * nsplit * (head_dim + 2) * sizeof(float);
 }
 
@@ -208,9 +199,7 @@ pgk_status pgk_paged_attention_v1(const void* q, const void* k_cache, const void
     const int G = num_heads / num_kv_heads;
     PGK_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, "pgk_paged_attention_v1: %d query heads per kv head unsupported", G);
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)head_dim);
-    int nsplit = (max_context + 511) / 512;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > 32) nsplit = 32;
+    const int nsplit = paged_nsplit(max_context);
     PGK_REQUIRE(nsplit == 1 || workspace, "pgk_paged_attention_v1: contexts beyond 512 need the workspace of pgk_paged_attention_workspace_bytes");
     hipStream_t st = resolve_stream(s);
     dim3 grid(nsplit, num_kv_heads, num_seqs);
@@ -219,7 +208,7 @@ pgk_status pgk_paged_attention_v1(const void* q, const void* k_cache, const void
         paged_attn_kernel<TT, DD, GG><<<grid, 256, 0, st>>>((const TT*)q, (const TT*)k_cache, (const TT*)v_cache, block_tables,  \
                                                             context_lens, (float*)workspace, (TT*)out, num_heads, num_kv_heads,   \
                                                             block_size, max_blocks_per_seq, scale, nsplit);             \
-        if (nsplit > 1) paged_combine_kernel<TT, DD><<<num_seqs * num_heads, DD, 0, st>>>((const float*)workspace, (TT*)out, nsplit); \
+        if (nsplit > 1) decode_phase2_kernel<TT, DD><<<num_seqs * num_heads, DD, 0, st>>>((const float*)workspace, (TT*)out, nsplit); \
         PGK_LAUNCH_CHECK();                                                                                             \
         return PGK_OK;                                                                                                  \
     }

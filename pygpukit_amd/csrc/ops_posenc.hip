@@ -10,15 +10,8 @@
 // of a cache row (decode).
 
 #include "attn_core.hip.h"
-#include "flash_common.hip.h"
 
 namespace pgk {
-
-int decode_nsplit(int max_seq);         // ops_attention.hip: the split count pgk_sdpa_decode_workspace_bytes sizes for
-
-pgk_status flash_prefill_alibi(const void* q, const void* k, const void* v, const float* slopes, void* out, int hq, int hkv, int q_len,
-                               int kv_len, int d, float scale, long long qh, long long qs, long long kh, long long ks, long long oh,
-                               long long os, int dt16, hipStream_t st);
 
 // ---- pope_inplace ----------------------------------------------------------------------------------------------------
 // x = round(float(x) + enc[start_pos + s][d]): one fp32 add, one round-to-nearest-even to T.  One launch covers q (the first
@@ -88,65 +81,6 @@ __global__ __launch_bounds__(256) void alibi_add_bias_kernel(float* scores, cons
     scores[gid] = scores[gid] - prod;
 }
 
-// ---- sdpa_alibi_fixed_cache, q_len == 1 ------------------------------------------------------------------------------
-// decode_phase1_kernel of ops_attention.hip with -slope[head] * (ctx - 1 - pos) added in fp32 to the score of cache row pos
-// before the online softmax.  Same chunking, records and phase 2 as pgk_sdpa_fixed_cache.
-template <int G>
-struct AlibiDecodeBias {
-    float slope[G];
-    int last;                                       // the query's position: context_len - 1
-    __device__ __forceinline__ float operator()(int g, int pos) const { return -slope[g] * (float)(last - pos); }
-};
-
-template <class T, int D, int G>
-__global__ __launch_bounds__(256) void alibi_decode_phase1_kernel(const T* q, const T* kc, const T* vc, const float* slopes, float* ws,
-                                                                  int hq, int hkv, int max_seq, float scale, int host_ctx,
-                                                                  const int32_t* ctx_buf, int nsplit) {
-    constexpr int LPR = D / 8, PPW = 64 / LPR, RS = D + 2;
-    __shared__ float lds[4 * PPW * G * RS];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int ctx = max(min(ctx_buf ? ctx_buf[0] : host_ctx, max_seq), 0);
-    const int h0 = blockIdx.y * G;                  // G consecutive query heads of one kv head (G divides Hq / Hkv)
-    const int kv_head = h0 / (hq / hkv);
-    const int chunk = decode_chunk_len(ctx, nsplit);
-    const int c0 = min(blockIdx.x * chunk, ctx), c1 = min(c0 + chunk, ctx);
-    float qf[G][8];
-    AlibiDecodeBias<G> bias;
-    bias.last = ctx - 1;
-    const int sub = lane % LPR;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        KVLoad<T>::load8(q + (size_t)(h0 + g) * D + sub * 8, qf[g]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[g][j] *= scale;
-        bias.slope[g] = slopes[h0 + g];
-    }
-    DecodeState<G> st;
-    st.init();
-    decode_walk<T, D, G>(kc + (size_t)kv_head * max_seq * D, vc + (size_t)kv_head * max_seq * D, c0, c1, qf, lane, wid, st, bias);
-    decode_block_merge<D, G>(st, lds, ws + ((size_t)h0 * nsplit + blockIdx.x) * RS, (size_t)nsplit * RS, lane, wid);
-}
-
-template <class T, int D>
-static pgk_status launch_alibi_decode(const void* q, const void* kc, const void* vc, const float* slopes, void* out, float* ws, int hq,
-                                      int hkv, int max_seq, float scale, int host_ctx, const int32_t* ctx_buf, hipStream_t st) {
-    const int nsplit = decode_nsplit(max_seq), rep = hq / hkv;
-    // head grouping as pgk_sdpa_irope_fixed_cache (ops_llama4.hip, where the five-head case was measured)
-    int G = rep % 4 == 0 ? 4 : rep % 2 == 0 ? 2 : 1;
-    if (G == 1 && rep % 5 == 0 && (long long)nsplit * (hq / 5) >= 256) G = 5;
-    const dim3 grid(nsplit, hq / G);
-#define PGK_ALIBI_DEC(GG)                                                                                                                 \
-    case GG:                                                                                                                              \
-        alibi_decode_phase1_kernel<T, D, GG><<<grid, 256, 0, st>>>((const T*)q, (const T*)kc, (const T*)vc, slopes, ws, hq, hkv, max_seq, \
-                                                                   scale, host_ctx, ctx_buf, nsplit);                                     \
-        break;
-    switch (G) { PGK_ALIBI_DEC(1) PGK_ALIBI_DEC(2) PGK_ALIBI_DEC(4) PGK_ALIBI_DEC(5) }
-#undef PGK_ALIBI_DEC
-    decode_phase2_kernel<T, D><<<hq, D, 0, st>>>(ws, (T*)out, nsplit);
-    PGK_LAUNCH_CHECK();
-    return PGK_OK;
-}
-
 }  // namespace pgk
 
 using namespace pgk;
@@ -207,8 +141,9 @@ pgk_status pgk_sdpa_alibi(const void* q, const void* k, const void* v, const voi
     PGK_REQUIRE(q_stride_h >= 0 && q_stride_s >= 0 && kv_stride_h >= 0 && kv_stride_s >= 0 && o_stride_h >= 0 && o_stride_s >= 0,
                 "pgk_sdpa_alibi: negative stride");
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
-    return flash_prefill_alibi(q, k, v, (const float*)slopes, out, hq, hkv, q_len, kv_len, d, scale, q_stride_h, q_stride_s, kv_stride_h,
-                               kv_stride_s, o_stride_h, o_stride_s, dt == PGK_BF16 ? 0 : 1, resolve_stream(s));
+    const FlashStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
+    return flash_prefill_alibi(q, k, v, (const float*)slopes, out, hq, hkv, q_len, kv_len, d, scale, sd, dt == PGK_BF16 ? 0 : 1,
+                               resolve_stream(s));
 }
 
 pgk_status pgk_sdpa_alibi_fixed_cache(const void* q, const void* k_cache, const void* v_cache, const void* slopes, void* out, int hq, int hkv,
@@ -227,17 +162,13 @@ pgk_status pgk_sdpa_alibi_fixed_cache(const void* q, const void* k_cache, const 
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
     hipStream_t st = resolve_stream(s);
     const float* sl = (const float*)slopes;
-    if (q_len > 1)          // the prefill kernel over the cache in place
-        return flash_prefill_alibi(q, k_cache, v_cache, sl, out, hq, hkv, q_len, h_context_len, d, scale, (long long)q_len * d, d,
-                                   (long long)max_seq * d, d, (long long)q_len * d, d, dt == PGK_BF16 ? 0 : 1, st);
-    PGK_REQUIRE(workspace, "pgk_sdpa_alibi_fixed_cache: q_len == 1 needs a workspace of pgk_sdpa_decode_workspace_bytes");
-    float* ws = (float*)workspace;
-    if (dt == PGK_BF16) {
-        if (d == 128) return launch_alibi_decode<bf16, 128>(q, k_cache, v_cache, sl, out, ws, hq, hkv, max_seq, scale, h_context_len, ctx_buf, st);
-        return launch_alibi_decode<bf16, 64>(q, k_cache, v_cache, sl, out, ws, hq, hkv, max_seq, scale, h_context_len, ctx_buf, st);
+    if (q_len > 1) {        // the prefill kernel over the cache in place
+        const FlashStrides sd{(long long)q_len * d, d, (long long)max_seq * d, d, (long long)q_len * d, d};
+        return flash_prefill_alibi(q, k_cache, v_cache, sl, out, hq, hkv, q_len, h_context_len, d, scale, sd, dt == PGK_BF16 ? 0 : 1, st);
     }
-    if (d == 128) return launch_alibi_decode<f16, 128>(q, k_cache, v_cache, sl, out, ws, hq, hkv, max_seq, scale, h_context_len, ctx_buf, st);
-    return launch_alibi_decode<f16, 64>(q, k_cache, v_cache, sl, out, ws, hq, hkv, max_seq, scale, h_context_len, ctx_buf, st);
+    PGK_REQUIRE(workspace, "pgk_sdpa_alibi_fixed_cache: q_len == 1 needs a workspace of pgk_sdpa_decode_workspace_bytes");
+    const DecodeAlibi ex{h_context_len, ctx_buf, scale, sl};
+    return launch_split_decode16(dt, d, q, k_cache, v_cache, out, workspace, hq, hkv, max_seq, ex, st);
 }
 
 }  // extern "C"

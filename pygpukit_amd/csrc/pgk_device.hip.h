@@ -172,4 +172,20 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
     return t;
 }
 
+// Llama-4 iRoPE temperature of a query position (reference: native/ops/nn/llama4_kernels.cuh:228):
+//   t = log1pf(floorf((float)(pos + 1) / floor_scale)) * attn_scale + 1, every step rounded to fp32 in that order.
+// log1pf is taken as the CORRECTLY ROUNDED value (evaluated in double, rounded once) and the multiply-add is not
+// contracted into an FMA, so a host restatement that rounds after every step reproduces t bit for bit whatever
+// libm it runs on.  One evaluation per query row, outside every loop.
+__device__ __forceinline__ float irope_temperature(long long pos, float attn_scale, float floor_scale) {
+#pragma clang fp contract(off)
+    const float steps = floorf((float)(pos + 1) / floor_scale);
+    const float lg = (float)log1p((double)steps);
+    const float scaled = lg * attn_scale;
+    return scaled + 1.0f;
+}
+__device__ __forceinline__ long long irope_position(const void* positions, int i, int pos_is_i64) {
+    return pos_is_i64 ? (long long)static_cast<const int64_t*>(positions)[i] : (long long)static_cast<const int32_t*>(positions)[i];
+}
+
 }  // namespace pgk

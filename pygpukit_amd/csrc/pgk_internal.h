@@ -17,6 +17,9 @@ int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3
 // NULL -> the calling thread's current stream (default: the device's library stream).
 hipStream_t resolve_stream(pgk_stream s);
 
+// multiProcessorCount of the current device, from a per-device table filled on first use (runtime.hip); 256 if the query fails.
+int device_cu_count();
+
 inline size_t dtype_size(pgk_dtype dt) {
     switch (dt) {
         case PGK_F64: case PGK_I64: return 8;

@@ -57,6 +57,21 @@ hipStream_t resolve_stream(pgk_stream s) {
     return default_stream();
 }
 
+// Compute units of the current device: asked of the runtime once per device, 256 (an MI355X) while the query fails.
+int device_cu_count() {
+    static std::mutex mu;
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!cus[dev]) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) return 256;
+        cus[dev] = prop.multiProcessorCount;
+    }
+    return cus[dev];
+}
+
 // ------------------------------------------------------------------------------------------
 // Pooled allocator.  Size classes: powers of two from 512 B to 1 MiB, then multiples of 2 MiB.
 // A hit costs no driver call, which also makes allocation legal while a stream is being captured.
