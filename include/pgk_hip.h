@@ -780,6 +780,37 @@ pgk_status pgk_patchify(const void* in, void* out, int B, int C, int H, int W, i
 /* in [B * (H/p) * (W/p), p * p * Co] with columns (ph, pw, c) -> out [B, Co, H, W]. */
 pgk_status pgk_unpatchify(const void* in, void* out, int B, int Co, int H, int W, int p, pgk_dtype dt, pgk_stream s);
 
+/* ------------------------------------------------------------------ VAE decoder ------ */
+/* conv2d (ops_conv2d.hip; reference: src/pygpukit/ops/conv.py conv2d):
+ *   out[n][m][oy][ox] = bias[m] + sum_{c, ky, kx} weight[m][c][ky][kx] * X[n][c][oy * sh + ky * dh - ph][ox * sw + kx * dw - pw]
+ * with zeros outside X.  X is x itself, or with upsample == 2 its nearest-neighbour 2x: X[c][y][x] = x[c][y >> 1][x >> 1], of
+ * size 2H x 2W, never materialised.  x is [N,C_in,H,W], or [N,H,W,C_in] with channels_last_in; out is [N,C_out,Ho,Wo], or
+ * [N,Ho,Wo,C_out] with channels_last_out; add (or NULL) has out's shape and layout and is added in fp32 after the bias; one
+ * rounding.  bf16 / f16 run an implicit GEMM on the 32x32x16 MFMA when pgk_conv2d_plan says 1; it reads the weight as the image
+ * [KH * KW][C_out padded to 64][C_in padded to 32] that pgk_conv2d_pack_weight writes (packed_weight, 16-byte aligned, or NULL:
+ * packed per call into pool workspace).  Everything else runs the tiled FMA kernel on `weight`.  One launch (+ the pack
+ * pre-pass), never synchronises the host.  N <= 65535; H, W (after the upsample, with padding) < 2^30; global offsets are
+ * size_t. */
+pgk_status pgk_conv2d(const void* x, const void* weight, const void* packed_weight, const void* bias, const void* add, void* out,
+                      int N, int C_in, int C_out, int H, int W, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w,
+                      int dil_h, int dil_w, int upsample, int channels_last_in, int channels_last_out, pgk_dtype dt, pgk_stream s);
+/* Host only: 1 = MFMA kernel (16-bit dtype, KH == KW in {1, 3}, stride_h == stride_w in {1, 2}, dilation 1, PGK_CONV_MFMA
+ * not "0"), 0 = FMA kernel, -1 = invalid shape or dtype. */
+int pgk_conv2d_plan(int C_in, int C_out, int H, int W, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                    int dil_w, int upsample, pgk_dtype dt);
+size_t pgk_conv2d_packed_elems(int C_in, int C_out, int KH, int KW);
+pgk_status pgk_conv2d_pack_weight(const void* weight, void* packed, int C_in, int C_out, int KH, int KW, pgk_dtype dt, pgk_stream s);
+/* group_norm (ops_groupnorm.hip): x [N,C,HW] (or [N,HW,C] with channels_last), G groups of C / G consecutive channels;
+ *   y = (x - mean_g) / sqrt(var_g + eps) * gamma[c] + beta[c], population variance over the group's (C / G) * HW elements;
+ * act 1 applies SiLU to the fp32 value; one rounding.  Statistics are Welford (count, mean, M2) triples merged with Chan's
+ * formula in a fixed order - no atomics, run-to-run identical.  Plan 0 ("block"): one workgroup per (image, group), one launch.
+ * Plan 1 ("split"): launch 1 writes one partial per (image, pixel chunk, group) into pool workspace, launch 2 re-merges the
+ * group's partials in chunk order in every workgroup and normalises its chunk.  PGK_GN_SPLIT=0/1 forces the plan. */
+pgk_status pgk_group_norm(const void* x, const void* gamma, const void* beta, void* out, int N, int C, int HW, int G, float eps,
+                          int act, int channels_last, pgk_dtype dt, pgk_stream s);
+/* Host only: 0 = block, 1 = split, -1 = invalid. */
+int pgk_group_norm_plan(int N, int C, int HW, int G, pgk_dtype dt, int channels_last);
+
 /* ------------------------------------------------------------------------ RCCL ------ */
 /* New functionality (the reference is single-GPU, docs/scheduler.md:358): data-parallel batch
  * decode over one 8xMI355X node.  One process per GPU; RCCL over xGMI only for the one-time weight

@@ -107,6 +107,9 @@ _PROTOS = {
     "pgk_sdpa_noncausal": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
     "pgk_conv1d": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V],
     "pgk_conv1d_pack_weight": [_V, _V, _I, _I, _I, _I, _V],
+    "pgk_conv2d": [_V, _V, _V, _V, _V, _V] + [_I] * 17 + [_V],
+    "pgk_conv2d_pack_weight": [_V, _V, _I, _I, _I, _I, _I, _V],
+    "pgk_group_norm": [_V, _V, _V, _V, _I, _I, _I, _I, _F, _I, _I, _I, _V],
     "pgk_ln_linear": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _F, _I, _I, _V],
     "pgk_ln_linear_qkv_cache": [_V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _F, _I, _V, _I, _V],
     "pgk_embed_token_position": [_V, _V, _V, _I, _I, _I, _V, _I, _V],
@@ -160,6 +163,8 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_gemm_nvf4_workspace_bytes": ([_I, _I, _I], C.c_size_t),
                "pgk_lstm_plan": ([_I, _I, _I], C.c_int),
                "pgk_conv1d_plan": ([_I, _I, _I, _I, _I, _I, _I], C.c_int), "pgk_conv1d_packed_elems": ([_I, _I, _I], C.c_size_t),
+               "pgk_conv2d_plan": ([_I] * 14, C.c_int), "pgk_conv2d_packed_elems": ([_I, _I, _I, _I], C.c_size_t),
+               "pgk_group_norm_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
                "pgk_ln_linear_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
                "pgk_gemm_plan": ([C.c_char_p, _I, _I, _I, _I, _I], C.c_char_p),
                "pgk_base_op_plan": ([C.c_char_p, _Z, _I, _I, _I], C.c_char_p), "pgk_base_op_grid": ([C.c_char_p, _Z, _I, _I, _I], C.c_int),

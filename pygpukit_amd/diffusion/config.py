@@ -1,5 +1,6 @@
 """Architecture descriptions of the diffusion transformers (reference: src/pygpukit/diffusion/config.py: the DiTSpec / PixArtSpec
-field names and PIXART_SIGMA_SPEC's values; SD3, Flux and the VAE specs belong to models this package does not build yet)."""
+field names and PIXART_SIGMA_SPEC's values, VAESpec and the three VAE specs; the SD3 and Flux transformer specs belong to models
+this package does not build yet)."""
 
 from __future__ import annotations
 
@@ -35,4 +36,25 @@ PIXART_SIGMA_SPEC = PixArtSpec(name="pixart_sigma", hidden_size=1152, num_layers
                                text_encoder_dim=4096, pos_embed_type="sinusoidal", in_channels=4, out_channels=8,
                                cross_attention_dim=4096)
 
-__all__ = ["DiTSpec", "PixArtSpec", "PIXART_SIGMA_SPEC"]
+
+@dataclass(frozen=True)
+class VAESpec:
+    """The reference's fields and defaults, plus shift_factor [build-defined]: decode computes latent / scaling_factor +
+    shift_factor (diffusers' SD3 and Flux VAEs carry one; 0.0 reproduces the reference)."""
+    name: str
+    in_channels: int = 3
+    out_channels: int = 3
+    latent_channels: int = 4
+    scaling_factor: float = 0.18215   # SD 1.5
+    block_out_channels: "tuple[int, ...]" = (128, 256, 512, 512)
+    layers_per_block: int = 2
+    norm_num_groups: int = 32
+    norm_eps: float = 1e-6
+    shift_factor: float = 0.0
+
+
+SDXL_VAE_SPEC = VAESpec(name="sdxl_vae", latent_channels=4, scaling_factor=0.13025, block_out_channels=(128, 256, 512, 512))
+SD3_VAE_SPEC = VAESpec(name="sd3_vae", latent_channels=16, scaling_factor=1.5305, block_out_channels=(128, 256, 512, 512))
+FLUX_VAE_SPEC = VAESpec(name="flux_vae", latent_channels=16, scaling_factor=0.3611, block_out_channels=(128, 256, 512, 512))
+
+__all__ = ["DiTSpec", "PixArtSpec", "PIXART_SIGMA_SPEC", "VAESpec", "SDXL_VAE_SPEC", "SD3_VAE_SPEC", "FLUX_VAE_SPEC"]

@@ -1,6 +1,6 @@
 """pygpukit_amd.ops: operator surface mirroring pygpukit.ops on the LLM-inference hot path."""
 
-from pygpukit_amd.ops.conv import conv1d
+from pygpukit_amd.ops.conv import conv1d, conv2d
 from pygpukit_amd.ops.elementwise import add, add_inplace, clamp, copy_to, div, mul, mul_inplace, sub, where
 from pygpukit_amd.ops.embedding import (embedding_lookup, embedding_lookup_batch, embedding_lookup_ptr,
                                        kv_cache_prefill, kv_cache_prefill_gqa, kv_cache_update, kv_cache_update_gqa, kv_cache_update_gqa_ptr)
@@ -22,7 +22,7 @@ from pygpukit_amd.ops.nn import (fa3_fp8_available, get_sm_version, quantize_fp8
                                 bias_add_inplace, geglu, gelu, glu_packed, layernorm, lstm_bidirectional, lstm_forward, relu2, rmsnorm, rmsnorm_residual, rope_inplace,
                                 rope_inplace_f32table, sdpa_causal, sdpa_causal_fixed_cache, sdpa_causal_fixed_cache_ptr,
                                 sdpa_causal_strided, sdpa_noncausal, sdpa_noncausal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh,
-                                embed_token_position_ptr, ln_linear, ln_linear_plan, ln_linear_qkv_cache_ptr)
+                                embed_token_position_ptr, ln_linear, ln_linear_plan, ln_linear_qkv_cache_ptr, group_norm, group_norm_silu)
 from pygpukit_amd.ops.plan import BASE_PLAN_OPS, base_op_grid, base_op_plan
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis
 from pygpukit_amd.ops.unary import abs, cos, exp, log, neg, relu, rsqrt, sin, sqrt
