@@ -598,6 +598,18 @@ pgk_status pgk_engine_kv_ptr(pgk_engine e, int layer, void** k, void** v);
 pgk_status pgk_engine_state_ptr(pgk_engine e, void** tokens, void** positions);
 /* number of kernel launches one decode step enqueues (for reporting) */
 pgk_status pgk_engine_launches_per_step(pgk_engine e, int* n);
+/* Read-only: the attention launches of ONE decode step of `batch` sequences whose largest position is `max_position`
+ * (what pgk_engine_set_state + pgk_engine_decode_step, or a replay of a capture of that batch, would run), computed by
+ * the functions the launcher itself calls; no device work, no state change.  `out` receives one line per chunk:
+ *   chunk b0=<first sequence> m=<sequences> form=gemv|batched|tiled|packed attn=<kernel> heads=<g[+g..]> nsplit=<slices>
+ *         span=<rows the slices cover> out=f32|bf16 tail=none|merge|merge_oproj_bf16|merge_oproj_fp8
+ * attn: attn_oproj_mfma / attn_oproj (fused with o_proj), attn_mfma_direct / attn_decode_direct (whole context, one
+ * workgroup per sequence and kv head), attn_decode_split; heads: query heads per kv head of each launch (GQA head chunks).
+ * One exception for replays: a SHORT step (largest position below 384 for one sequence, 512 for a batch) whose chunk has
+ * no whole-context kernel - a single sequence with fp8 / NVF4 W_o or with a GQA group other than 1 / 2 / 4 - was captured
+ * with the cache length as its span; the replay runs the kernels named here over more slices than nsplit / span say,
+ * which report the eager step. */
+pgk_status pgk_engine_attn_plan(pgk_engine e, int batch, int max_position, char* out, size_t n);
 
 /* ------------------------------------------------------------------ Mixture of Experts ------ */
 /* Routing, permutation and grouped expert GEMMs (ops_moe.hip).  Restates native/ops/moe/topk_kernels.cuh,

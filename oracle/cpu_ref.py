@@ -811,7 +811,8 @@ def build_qwen3_ref(cfg: dict, weights: dict, max_pos: int = 2048) -> RefModel:
         mlp = RefMLP("silu", gate=lw["gate"], up=lw["up"], down=lw["down"])
         blocks.append(RefBlock(RefNorm(lw["attn_norm"], None, "rmsnorm", eps), attn,
                                RefNorm(lw["mlp_norm"], None, "rmsnorm", eps), mlp))
-    return RefModel(weights["embed"], blocks, RefNorm(weights["final_norm"], None, "rmsnorm", eps))
+    # "lm_head" in the weight dict: an untied output matrix [V, H] (absent: tied to the embedding, as Qwen3-0.6B)
+    return RefModel(weights["embed"], blocks, RefNorm(weights["final_norm"], None, "rmsnorm", eps), lm_head=weights.get("lm_head"))
 
 
 def build_qwen3_ref_fp8a8(cfg: dict, weights: dict, max_pos: int = 2048) -> RefModel:

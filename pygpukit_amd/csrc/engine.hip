@@ -201,14 +201,8 @@ static pgk_status decode_chunk(const StepCtx& cx, bool last) {
     const hipStream_t st = cx.st;
     float* h = e->h + (size_t)b0 * H;
     float* h2 = e->h2 + (size_t)b0 * H;
-    // fused attention+o_proj recomputes a KV head's attention in every row-slice workgroup: right for one
-    // sequence at short context, wasteful for a batch.
-    // (two sequences ran the fused kernel too until round 3: its 96-KB workgroups are one per CU, so 2 x 256 of them took two
-    // rounds - 9.4 us per layer against 3.7 + 2.4 for whole-context attention + an o_proj GEMV: 0.80 -> 0.66 ms per step)
-    const bool fused = e->fused_attn && cx.short_ctx && M == 1;
-    const bool direct = !fused && cx.short_ctx && M >= 2;
-    // long contexts (or fp8 W_o): split-KV slices, then merge + o_proj partials in one launch; the gate/up prologue adds them
-    const bool merged = !fused && !direct && M <= 2 && e->merged_oproj;
+    const AttnFlags af = attn_flags(e, CF_GEMV, M, cx.short_ctx);   // engine_state.hip.h
+    const bool fused = af.fused, direct = af.direct, merged = af.merged;
     const bool partials = fused || merged;
     for (int l = 0; l < c.num_layers; ++l) {
         const auto& L = e->layers[l];
@@ -218,7 +212,7 @@ static pgk_status decode_chunk(const StepCtx& cx, bool last) {
         if (pgk_status r = counted(cx.launches, launch_fused_auto<WT, XT, M, PRO_NORM, EPI_STORE>(a, a.N, st))) return r;
         mark(KC_ATTN);
         // 2. attention (QK-norm, RoPE, KV write fused; on the fused path also the o_proj partial products)
-        if (pgk_status r = launch_attn(cx, l, fused, direct, false, merged)) return r;
+        if (pgk_status r = launch_attn(cx, l, af)) return r;
         const float* mlp_in = h;
         if (!partials) {
             mark(KC_OPROJ);
@@ -260,7 +254,8 @@ static pgk_status decode_chunk_batched(const StepCtx& cx, bool last) {
     float* h = e->h + (size_t)b0 * H;
     bf16* x16 = e->x16 + (size_t)b0 * H;
     const bool tiled = M > 16;
-    const bool direct = cx.short_ctx && M >= 3;
+    const AttnFlags af = attn_flags(e, tiled ? CF_TILED : CF_BATCHED, M, cx.short_ctx);
+    const bool direct = af.direct;
     // tiled: the consumer reads rows that a launch of their own has normalised to bf16
     auto norm_x16 = [&](FusedArgs& a) -> pgk_status {
         if (!tiled) return PGK_OK;
@@ -277,7 +272,7 @@ static pgk_status decode_chunk_batched(const StepCtx& cx, bool last) {
         if (!FP8 && e->packed_ok) a.wp = e->packed[l].qkv;
         if (pgk_status r = counted(cx.launches, batched_proj(FP8, tiled ? PRO_PLAIN : PRO_NORM, EPI_STORE, a, M, st))) return r;
         mark(KC_ATTN);
-        if (pgk_status r = launch_attn(cx, l, false, direct, true)) return r;
+        if (pgk_status r = launch_attn(cx, l, af)) return r;
         mark(KC_OPROJ);
         a = o_args(e, L, b0);
         if (direct || tiled) a.xin16 = e->attnv16 + (size_t)b0 * QD;   // the whole-context attention kernel wrote bf16
@@ -317,7 +312,8 @@ static pgk_status decode_chunk_packed(const StepCtx& cx, bool last) {
     const hipStream_t st = cx.st;
     float* h = e->h + (size_t)b0 * H;
     bf16* x16 = e->x16 + (size_t)b0 * H;
-    const bool direct = cx.short_ctx && M >= 3;
+    const AttnFlags af = attn_flags(e, CF_PACKED, M, cx.short_ctx);
+    const bool direct = af.direct;
     const int s_o = pkgemm_pick_splits(M, H, QD), s_d = pkgemm_pick_splits(M, H, I);
     int pending = 0;
     auto norm = [&](const bf16* gamma) -> pgk_status {
@@ -336,7 +332,7 @@ static pgk_status decode_chunk_packed(const StepCtx& cx, bool last) {
         else if (pgk_status r = norm((const bf16*)L.attn_norm)) return r;
         if (pgk_status r = counted(cx.launches, pkgemm_nt(x16, H, P.qkv, e->qkv + (size_t)b0 * NQKV, NQKV, PK_EPI_SLAB, 1, M, NQKV, H, &nrm, st))) return r;
         mark(KC_ATTN);
-        if (pgk_status r = launch_attn(cx, l, false, direct, true)) return r;
+        if (pgk_status r = launch_attn(cx, l, af)) return r;
         mark(KC_OPROJ);
         bf16* attn16 = e->attnv16 + (size_t)b0 * QD;
         if (!direct) {   // long contexts: the merge kernel leaves fp32 rows
@@ -374,24 +370,22 @@ static pgk_status decode_step_impl(Engine* e, int batch, hipStream_t st, int* la
         const int rem = batch - b0;
         auto chunk = [&](int m) { return StepCtx{e, b0, m, st, launches, short_ctx}; };
         pgk_status r;
-        // the MFMA projections cost the same for 3 as for 16 sequences (~1.0-1.2 ms per step on Qwen3-0.6B); the GEMV
-        // kernels exist for M = 1, 2, 4, 8 only, so 3 / 5 / 6 / 7 sequences would take two or three weight passes there
-        // (measured: 7 sequences 2.46 ms against 1.05).  GEMV stays for exactly 1, 2 and 4 (0.70 / 0.93 / 0.82 ms).
-        const bool mfma_ok = e->batched_mfma && (rem >= e->batched_min || (e->batched_min == 5 && rem == 3));
+        const ChunkChoice ch = next_chunk(e, rem);   // engine_state.hip.h
+        const int m = ch.m;
         if constexpr (std::is_same<WT, nvf4x2>::value) {
-            // NVF4 (w4a16): GEMV chunks of <= 8 sequences only, each re-reading the weights; batched_mfma is off for it
-        } else if (mfma_ok) {
-            const int m = rem > e->batched_max ? e->batched_max : rem;
-            if (m > 16 && e->packed_decode) r = decode_chunk_packed(chunk(m), rem == m);
+            // NVF4 (w4a16): GEMV chunks only (next_chunk); the MFMA chunk kernels are not instantiated for it
+        } else if (ch.form != CF_GEMV) {
+            if (ch.form == CF_PACKED) r = decode_chunk_packed(chunk(m), rem == m);
             else r = decode_chunk_batched<WT>(chunk(m), rem == m);
             b0 += m;
             if (r != PGK_OK) return r;
             continue;
         }
-        if (rem >= 8) { r = decode_chunk<WT, bf16, 8>(chunk(8), rem == 8); b0 += 8; }
-        else if (rem >= 4) { r = decode_chunk<WT, bf16, 4>(chunk(4), rem == 4); b0 += 4; }
-        else if (rem >= 2) { r = decode_chunk<WT, float, 2>(chunk(2), rem == 2); b0 += 2; }
-        else { r = decode_chunk<WT, float, 1>(chunk(1), true); b0 += 1; }
+        if (m == 8) r = decode_chunk<WT, bf16, 8>(chunk(8), rem == 8);
+        else if (m == 4) r = decode_chunk<WT, bf16, 4>(chunk(4), rem == 4);
+        else if (m == 2) r = decode_chunk<WT, float, 2>(chunk(2), rem == 2);
+        else r = decode_chunk<WT, float, 1>(chunk(1), true);
+        b0 += m;
         if (r != PGK_OK) return r;
     }
     return PGK_OK;
@@ -937,6 +931,44 @@ pgk_status pgk_engine_state_ptr(pgk_engine eh, void** tokens, void** positions) 
     PGK_REQUIRE(eh && tokens && positions, "pgk_engine_state_ptr: null argument");
     *tokens = ((Engine*)eh)->tokens;
     *positions = ((Engine*)eh)->positions;
+    return PGK_OK;
+}
+
+// Read-only: what the attention of ONE decode step of `batch` sequences whose largest position is `max_position` launches,
+// one line per chunk of the step, from the functions the launchers themselves call (next_chunk, attn_flags, attn_choice,
+// head_chunk) at the tier pgk_engine_set_state(max_position) + pgk_engine_decode_step - or pgk_engine_replay of a
+// capture of the same batch - selects.  Touches neither the device nor the engine's state.
+//   chunk b0=<first sequence> m=<sequences> form=gemv|batched|tiled|packed attn=<kernel> heads=<g[+g..]> nsplit=<n> span=<rows> out=f32|bf16 tail=<what follows>
+pgk_status pgk_engine_attn_plan(pgk_engine eh, int batch, int max_position, char* out, size_t n) {
+    PGK_REQUIRE(eh && out && n > 0, "pgk_engine_attn_plan: null argument");
+    const Engine* e = (const Engine*)eh;
+    PGK_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch, "pgk_engine_attn_plan: batch %d outside [1,%d]", batch, e->cfg.max_batch);
+    PGK_REQUIRE(max_position >= 0 && max_position < e->cfg.max_seq_len, "pgk_engine_attn_plan: position %d outside cache of %d", max_position,
+                e->cfg.max_seq_len);
+    static const char* const forms[] = {"gemv", "batched", "tiled", "packed"};
+    static const char* const kernels[] = {"attn_oproj_mfma", "attn_oproj", "attn_mfma_direct", "attn_decode_direct", "attn_decode_split"};
+    static const char* const tails[] = {"none", "merge", "merge_oproj_bf16", "merge_oproj_fp8"};
+    const bool short_ctx = step_is_short_at(e, batch, max_position);      // enqueue_step / pick_tier
+    // enqueue_step's slicing.  (A replayed SHORT step whose chunk has no whole-context kernel - one sequence with fp8 W_o or a GQA
+    // group other than 1 / 2 / 4 - was captured with the cache length as its span instead: same kernels, more slices.)
+    const int step_span = span_for_at(e, max_position);
+    const int G = e->cfg.num_heads / e->cfg.num_kv_heads;
+    size_t used = 0;
+    out[0] = 0;
+    for (int b0 = 0; b0 < batch;) {
+        const ChunkChoice ch = next_chunk(e, batch - b0);
+        const AttnFlags af = attn_flags(e, ch.form, ch.m, short_ctx);
+        const AttnChoice pick = attn_choice(e, ch.m, step_span, af);
+        char heads[64];
+        size_t hu = 0;
+        for (int off = 0; off < G; off += head_chunk(G, off))
+            hu += (size_t)snprintf(heads + hu, hu < sizeof heads ? sizeof heads - hu : 0, "%s%d", off ? "+" : "", head_chunk(G, off));
+        const int w = snprintf(out + used, n - used, "chunk b0=%d m=%d form=%s attn=%s heads=%s nsplit=%d span=%d out=%s tail=%s\n", b0, ch.m,
+                               forms[ch.form], kernels[pick.kernel], heads, pick.nsplit, pick.span, pick.out_bf16 ? "bf16" : "f32", tails[pick.tail]);
+        PGK_REQUIRE(w > 0 && (size_t)w < n - used, "pgk_engine_attn_plan: the plan needs more than %zu bytes", n);
+        used += (size_t)w;
+        b0 += ch.m;
+    }
     return PGK_OK;
 }
 

@@ -877,11 +877,43 @@ static hipError_t launch_attn_decode(bool direct, dim3 grid, hipStream_t st, con
     return direct ? launch_k(attn_decode_kernel<D, G, true>, grid, dim3(256), 0, st, a) : launch_k(attn_decode_kernel<D, G, false>, grid, dim3(256), 0, st, a);
 }
 
+// Which attention kernel a chunk of m sequences launches, over how many split-KV slices, and what follows it: the one
+// place where this is decided.  launch_attn_d executes the choice; pgk_engine_attn_plan prints it.
+enum AttnKernel { AK_FUSED_MFMA = 0, AK_FUSED_DOT2, AK_DIRECT_MFMA, AK_DIRECT, AK_SPLIT };
+enum AttnTail { AT_NONE = 0, AT_MERGE, AT_MERGE_OPROJ_BF16, AT_MERGE_OPROJ_FP8 };
+struct AttnChoice { AttnKernel kernel; AttnTail tail; int nsplit, span; bool out_bf16; };
+inline AttnChoice attn_choice(const Engine* e, int m, int step_span, const AttnFlags& f) {
+    const auto& c = e->cfg;
+    const int D = c.head_dim, G = c.num_heads / c.num_kv_heads;
+    AttnChoice ch{};
+    ch.span = (step_span > 0 && step_span < c.max_seq_len) ? step_span : c.max_seq_len;
+    // KV slices per (sequence, kv head): as many as fit ONE wave of workgroups over the chip (a 257th workgroup waits
+    // for a free CU and adds a tail: 33 slices x 8 heads measured 5 % slower than 32 at context 2048), never more than
+    // the workspace was sized for (e->nsplit: ~64 positions per slice at the full cache length)
+    // (batches stream enough KV bytes to want two workgroups per CU: measured 22.1 vs 24.6 us at 8 x 2048 positions)
+    int ns = e->cu_count * (m >= 4 ? 2 : 1) / (c.num_kv_heads * m);
+    const int ns_cap = ceil_div(ch.span, 64) < e->nsplit ? ceil_div(ch.span, 64) : e->nsplit;     // ~64 positions per slice at least, by the TIER (not the cache: a tier slices alike on every cache)
+    ns = ns < 1 ? 1 : (ns > ns_cap ? ns_cap : ns);
+    // slices are cut by absolute position in whole position-group steps: launch only as many as the step's context tier needs
+    // (the tier, not the cache length: with slices of a 4096-row cache a context of 400 kept 3 of 27 slices busy - 0.671 ms per
+    // step against 0.623 on a 1024-row cache)
+    ch.nsplit = f.direct ? 1 : ceil_div(ch.span, decode_chunk_len(ch.span, ns, 4 * (64 / (D / 8))));
+    ch.out_bf16 = f.direct && f.direct_bf16;
+    if (!group_instantiated(G)) ch.kernel = f.direct ? AK_DIRECT : AK_SPLIT;   // head-chunk launches: attn_decode_kernel only
+    else if (f.fused) ch.kernel = (D == 128 && e->attn_mfma) ? AK_FUSED_MFMA : AK_FUSED_DOT2;
+    else if (f.direct) ch.kernel = (D == 128 && e->attn_mfma && m * (int)c.num_kv_heads <= e->cu_count) ? AK_DIRECT_MFMA : AK_DIRECT;
+    else ch.kernel = AK_SPLIT;
+    const bool f8 = c.weight_format == 1 || c.weight_format == 2;
+    ch.tail = f.merged ? (f8 ? AT_MERGE_OPROJ_FP8 : AT_MERGE_OPROJ_BF16) : ((!f.fused && !f.direct) ? AT_MERGE : AT_NONE);
+    return ch;
+}
+
 // `fused`: attention + o_proj partials in one kernel (one sequence at short context); `direct`: one workgroup per
 // (sequence, kv head) walks the whole (short) context and writes the normalised output - no merge launch; otherwise
 // split-KV slices, then `merged` (merge + o_proj partials in one launch) or the merge kernel.  Counts its own launches.
 template <int D>
-static pgk_status launch_attn_d(const StepCtx& cx, int layer, bool fused, bool direct, bool direct_bf16, bool merged) {
+static pgk_status launch_attn_d(const StepCtx& cx, int layer, const AttnFlags& af) {
+    const bool fused = af.fused, direct = af.direct;
     Engine* e = cx.e;
     const int b0 = cx.b0, m = cx.M;
     const hipStream_t st = cx.st;
@@ -899,38 +931,27 @@ static pgk_status launch_attn_d(const StepCtx& cx, int layer, bool fused, bool d
     a.kcache = e->kcache + lofs; a.vcache = e->vcache + lofs;
     a.positions = e->positions + b0;
     a.hq = c.num_heads; a.hkv = c.num_kv_heads; a.max_seq = c.max_seq_len;
-    const int span = (e->step_span > 0 && e->step_span < c.max_seq_len) ? e->step_span : c.max_seq_len;
-    a.span = span;
+    const AttnChoice pick = attn_choice(e, m, e->step_span, af);
+    a.span = pick.span;
     a.scale = 1.0f / sqrtf((float)D);
     a.part = e->part + (size_t)b0 * c.num_heads * e->nsplit * (D + 2);
-    // KV slices per (sequence, kv head): as many as fit ONE wave of workgroups over the chip (a 257th workgroup waits
-    // for a free CU and adds a tail: 33 slices x 8 heads measured 5 % slower than 32 at context 2048), never more than
-    // the workspace was sized for (e->nsplit: ~64 positions per slice at the full cache length)
-    // (batches stream enough KV bytes to want two workgroups per CU: measured 22.1 vs 24.6 us at 8 x 2048 positions)
-    int ns = e->cu_count * (m >= 4 ? 2 : 1) / (c.num_kv_heads * m);
-    const int ns_cap = ceil_div(span, 64) < e->nsplit ? ceil_div(span, 64) : e->nsplit;     // ~64 positions per slice at least, by the TIER (not the cache: a tier slices alike on every cache)
-    ns = ns < 1 ? 1 : (ns > ns_cap ? ns_cap : ns);
-    // slices are cut by absolute position in whole position-group steps: launch only as many as the step's context tier needs
-    // (the tier, not the cache length: with slices of a 4096-row cache a context of 400 kept 3 of 27 slices busy - 0.671 ms per
-    // step against 0.623 on a 1024-row cache)
-    a.nsplit = ceil_div(span, decode_chunk_len(span, ns, 4 * (64 / (D / 8))));
+    a.nsplit = pick.nsplit;
     a.w_o = (const bf16*)L.w_o; a.w_o_scale = (const bf16*)L.s_o; a.H = c.hidden_size; a.rows_per_block = e->oproj_rows;
     a.opart = e->opart ? e->opart + (size_t)b0 * c.num_kv_heads * c.hidden_size : nullptr;
     if (direct) {
-        a.nsplit = 1;
         a.attn_direct = e->attnv + (size_t)b0 * c.num_heads * D;
-        if (direct_bf16) a.attn_direct16 = e->attnv16 + (size_t)b0 * c.num_heads * D;
+        if (pick.out_bf16) a.attn_direct16 = e->attnv16 + (size_t)b0 * c.num_heads * D;
     }
     dim3 grid = fused ? dim3((c.hidden_size / e->oproj_rows) * c.num_kv_heads, 1, m) : dim3(a.nsplit, c.num_kv_heads, m);
     hipError_t he = hipSuccess;
     a.g_total = G;
     a.g_off = 0;
-    if (G != 1 && G != 2 && G != 4) {
+    if (!group_instantiated(G)) {
         // any other group size (Qwen2.5-7B: 28 / 4 = 7): chunks of 4, 2 and 1 query heads per kv head, one launch each -
         // every chunk re-reads the kv head's K/V rows, which is what the reference's GQA-expanded cache costs for ALL heads
         PGK_REQUIRE(!fused, "engine: fused attention needs a GQA group of 1, 2 or 4");
         for (int off = 0; off < G;) {
-            const int gc = (G - off >= 4) ? 4 : ((G - off >= 2) ? 2 : 1);
+            const int gc = head_chunk(G, off);
             a.g_off = off;
             he = with_group(gc, [&](auto g) { return launch_attn_decode<D, decltype(g)::value>(direct, grid, st, a); });
             PGK_CHECK_HIP(he);
@@ -940,29 +961,31 @@ static pgk_status launch_attn_d(const StepCtx& cx, int layer, bool fused, bool d
     } else {
         he = with_group(G, [&](auto g) {
             constexpr int GG = decltype(g)::value;
-            if (fused && D == 128 && e->attn_mfma) return launch_attn_mfma<GG>(grid, st, a);
-            if (fused) return launch_k(attn_oproj_kernel<D, GG>, grid, dim3(256), 0, st, a);
-            if (direct && D == 128 && e->attn_mfma && m * (int)c.num_kv_heads <= e->cu_count) return launch_attn_mfma<GG, false>(dim3(c.num_kv_heads, 1, m), st, a);
-            return launch_attn_decode<D, GG>(direct, grid, st, a);
+            if constexpr (D == 128) {
+                if (pick.kernel == AK_FUSED_MFMA) return launch_attn_mfma<GG>(grid, st, a);
+                if (pick.kernel == AK_DIRECT_MFMA) return launch_attn_mfma<GG, false>(dim3(c.num_kv_heads, 1, m), st, a);
+            }
+            if (pick.kernel == AK_FUSED_DOT2) return launch_k(attn_oproj_kernel<D, GG>, grid, dim3(256), 0, st, a);
+            return launch_attn_decode<D, GG>(pick.kernel == AK_DIRECT, grid, st, a);
         });
         PGK_CHECK_HIP(he);
         ++*cx.launches;
     }
-    if (merged) {
+    if (pick.tail == AT_MERGE_OPROJ_BF16 || pick.tail == AT_MERGE_OPROJ_FP8) {
         // split-KV merge + o_proj partial products in one launch (attn_merge_oproj_kernel)
-        PGK_REQUIRE(!fused && !direct && (G == 1 || G == 2 || G == 4), "engine: merged o_proj on an unsupported attention path");
+        PGK_REQUIRE(!fused && !direct && group_instantiated(G), "engine: merged o_proj on an unsupported attention path");
         mark(KC_OPROJ);
         a.rows_per_block = e->moproj_rows;
         const dim3 g2((c.hidden_size / e->moproj_rows) * c.num_kv_heads, 1, m);
         PGK_REQUIRE(c.weight_format != 3, "engine: merged o_proj has no NVF4 form");
-        const bool f8 = c.weight_format == 1 || c.weight_format == 2;
+        const bool f8 = pick.tail == AT_MERGE_OPROJ_FP8;
         he = with_group(G, [&](auto g) {
             constexpr int GG = decltype(g)::value;
             return f8 ? launch_k(attn_merge_oproj_kernel<D, GG, true>, g2, dim3(256), 0, st, a) : launch_k(attn_merge_oproj_kernel<D, GG, false>, g2, dim3(256), 0, st, a);
         });
         PGK_CHECK_HIP(he);
         ++*cx.launches;
-    } else if (!fused && !direct) {
+    } else if (pick.tail == AT_MERGE) {
         PGK_CHECK_HIP(launch_k(attn_merge_kernel<D>, dim3(c.num_heads, m), dim3(D), 0, st, (const float*)a.part,
                                e->attnv + (size_t)b0 * c.num_heads * D, (int)c.num_heads, (int)a.nsplit));
         ++*cx.launches;
@@ -970,9 +993,8 @@ static pgk_status launch_attn_d(const StepCtx& cx, int layer, bool fused, bool d
     return PGK_OK;
 }
 
-static pgk_status launch_attn(const StepCtx& cx, int layer, bool fused, bool direct, bool direct_bf16 = false, bool merged = false) {
-    return cx.e->cfg.head_dim == 128 ? launch_attn_d<128>(cx, layer, fused, direct, direct_bf16, merged)
-                                     : launch_attn_d<64>(cx, layer, fused, direct, direct_bf16, merged);
+static pgk_status launch_attn(const StepCtx& cx, int layer, const AttnFlags& af) {
+    return cx.e->cfg.head_dim == 128 ? launch_attn_d<128>(cx, layer, af) : launch_attn_d<64>(cx, layer, af);
 }
 
 }  // namespace pgk

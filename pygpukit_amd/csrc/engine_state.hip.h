@@ -99,17 +99,19 @@ inline pgk_status dev_alloc(Engine* e, void** p, size_t bytes, size_t* acct) {
 // is a speed hint only - both sequences are correct at any context - so a caller that rewrites the device-resident
 // positions behind the library's back loses speed, never correctness; an unknown bound selects the long sequence.
 inline int short_limit(int batch) { return batch == 1 ? SHORT_CTX_B1 : SHORT_CTX; }
-inline bool step_is_short(const Engine* e, int batch) { return e->short_path && e->pos_hi >= 0 && e->pos_hi + 1 <= short_limit(batch); }
+inline bool step_is_short_at(const Engine* e, int batch, int pos_hi) { return e->short_path && pos_hi >= 0 && pos_hi + 1 <= short_limit(batch); }
+inline bool step_is_short(const Engine* e, int batch) { return step_is_short_at(e, batch, e->pos_hi); }
 
 // The split-KV slicing a step at the host-side position bound needs: the smallest of 1024, 2048, ... that covers the context, capped at
 // the cache length (an unknown bound: the cache length).
-inline int span_for(const Engine* e) {
+inline int span_for_at(const Engine* e, int pos_hi) {
     const int cap = e->cfg.max_seq_len;
-    if (e->pos_hi < 0) return cap;
+    if (pos_hi < 0) return cap;
     int span = 1024;
-    while (span < e->pos_hi + 1 && span < cap) span *= 2;
+    while (span < pos_hi + 1 && span < cap) span *= 2;
     return span < cap ? span : cap;
 }
+inline int span_for(const Engine* e) { return span_for_at(e, e->pos_hi); }
 
 // The captured step the next replay takes: the short-context sequence while the position bound allows it (and it was captured),
 // otherwise the split-KV tier whose slices cover the context; both kinds are correct at any context they cover.
@@ -129,6 +131,48 @@ inline pgk_status counted(int* launches, pgk_status r) {
     if (launches) ++*launches;
     return r;
 }
+
+// ---- the step's decisions as pure functions of the engine's host state: the launchers call them, and so does the read-only
+// plan query (pgk_engine_attn_plan), which therefore names what a step would launch without restating any of it ----------
+
+// How the step cuts its sequences into chunks: the next chunk of a step with `rem` sequences left.
+enum ChunkForm { CF_GEMV = 0, CF_BATCHED, CF_TILED, CF_PACKED };
+struct ChunkChoice { ChunkForm form; int m; };
+inline ChunkChoice next_chunk(const Engine* e, int rem) {
+    // the MFMA projections cost the same for 3 as for 16 sequences (~1.0-1.2 ms per step on Qwen3-0.6B); the GEMV
+    // kernels exist for M = 1, 2, 4, 8 only, so 3 / 5 / 6 / 7 sequences would take two or three weight passes there
+    // (measured: 7 sequences 2.46 ms against 1.05).  GEMV stays for exactly 1, 2 and 4 (0.70 / 0.93 / 0.82 ms).
+    // NVF4 (w4a16): GEMV chunks of <= 8 sequences only, each re-reading the weights; batched_mfma is off for it
+    const bool mfma_ok = e->cfg.weight_format != 3 && e->batched_mfma && (rem >= e->batched_min || (e->batched_min == 5 && rem == 3));
+    if (mfma_ok) {
+        const int m = rem > e->batched_max ? e->batched_max : rem;
+        return {m > 16 ? (e->packed_decode ? CF_PACKED : CF_TILED) : CF_BATCHED, m};
+    }
+    return {CF_GEMV, rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1};
+}
+
+// Which attention launch sequence a chunk of M sequences takes.  `fused`: attention + o_proj partials in one kernel (one
+// sequence at short context); `direct`: one workgroup per (sequence, kv head) walks the whole (short) context and writes the
+// normalised output (`direct_bf16`: as bf16 rows for an MFMA o_proj) - no merge launch; otherwise split-KV slices, then
+// `merged` (merge + o_proj partials in one launch) or the merge kernel.
+struct AttnFlags { bool fused, direct, direct_bf16, merged; };
+inline AttnFlags attn_flags(const Engine* e, ChunkForm form, int M, bool short_ctx) {
+    if (form != CF_GEMV) return {false, short_ctx && M >= 3, true, false};
+    // fused attention+o_proj recomputes a KV head's attention in every row-slice workgroup: right for one
+    // sequence at short context, wasteful for a batch.
+    // (two sequences ran the fused kernel too until round 3: its 96-KB workgroups are one per CU, so 2 x 256 of them took two
+    // rounds - 9.4 us per layer against 3.7 + 2.4 for whole-context attention + an o_proj GEMV: 0.80 -> 0.66 ms per step)
+    const bool fused = e->fused_attn && short_ctx && M == 1;
+    const bool direct = !fused && short_ctx && M >= 2;
+    // long contexts (or fp8 W_o): split-KV slices, then merge + o_proj partials in one launch; the gate/up prologue adds them
+    const bool merged = !fused && !direct && M <= 2 && e->merged_oproj;
+    return {fused, direct, false, merged};
+}
+
+// GQA groups other than the instantiated 1 / 2 / 4 query heads per kv head run as several launches over head chunks of
+// 4, 2 and 1 heads: the size of the chunk that starts at head `off` of a group of G.
+inline bool group_instantiated(int G) { return G == 1 || G == 2 || G == 4; }
+inline int head_chunk(int G, int off) { return group_instantiated(G) ? G : ((G - off >= 4) ? 4 : ((G - off >= 2) ? 2 : 1)); }
 
 // Host entries the prefill and the decode step's packed path (one row per SEQUENCE) share; defined in engine_prefill.hip.
 // h[r] += the *pending split-K slabs of the projection in front of this norm (then *pending = 0), x[r] = bf16(rmsnorm(h[r]) * gamma)

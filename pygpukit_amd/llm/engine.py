@@ -235,6 +235,18 @@ class Engine:
         _hip.call("pgk_engine_launches_per_step", self.handle, C.byref(n))
         return n.value
 
+    def attn_plan(self, batch: int = 1, max_position: int = 0) -> list[dict]:
+        """What the attention of one decode step of `batch` sequences with largest position `max_position` launches, per
+        chunk of the step: {"b0", "m", "form", "attn", "heads", "nsplit", "span", "out", "tail"} (pgk_engine_attn_plan:
+        the launcher's own decision functions, read-only - it neither runs nor changes anything)."""
+        buf = C.create_string_buffer(8192)
+        _hip.call("pgk_engine_attn_plan", self.handle, batch, max_position, buf, len(buf))
+        out = []
+        for line in buf.value.decode().splitlines():
+            d = dict(kv.split("=", 1) for kv in line.split()[1:])
+            out.append({k: int(v) if k in ("b0", "m", "nsplit", "span") else v for k, v in d.items()})
+        return out
+
     # ------------------------------------------------------------------ convenience
     def generate_greedy(self, prompt, max_new_tokens: int, *, use_graph: bool = True) -> list[int]:
         """Prompt + max_new_tokens greedy tokens for one sequence (slot 0): prefill, argmax of the last
