@@ -792,6 +792,31 @@ pgk_status pgk_patchify(const void* in, void* out, int B, int C, int H, int W, i
 /* in [B * (H/p) * (W/p), p * p * Co] with columns (ph, pw, c) -> out [B, Co, H, W]. */
 pgk_status pgk_unpatchify(const void* in, void* out, int B, int Co, int H, int W, int p, pgk_dtype dt, pgk_stream s);
 
+/* ------------------------------------------------------------------ FLUX ------ */
+/* (ops_flux.hip; reference: src/pygpukit/diffusion/models/flux/)
+ * Per-head RMSNorm of Q and K with learned weights, then interleaved-pair RoPE, in place, one launch.  Row r = b * seq + p of Q
+ * lies at q + r * row_stride + h * head_stride (elements of dt), K likewise from k; a fused [B * seq, 3 H D] projection has
+ * row_stride = 3 H D, head_stride = D, k = q + H D.  Rows with p < split use wq_a / wk_a [head_dim], the others wq_b / wk_b (in
+ * w_dt: dt or PGK_F32); a pair that no row uses may be NULL.  cos / sin are [seq, head_dim] fp32, indexed by p.  In fp32,
+ * rounded once at the store:
+ *     n[j] = x[j] / sqrt(mean_j(x^2) + eps) * w[j];   out[j] = n[j] * cos[p, j] + rot[j] * sin[p, j],
+ *     rot[2i] = -n[2i+1], rot[2i+1] = n[2i].
+ * head_dim 64 / 128 with every pointer and both strides on 16 bytes: the vector kernel (a head is 8 / 16 / 32 lanes of one
+ * 16-byte vector); any other even head_dim <= 256 or any misalignment: a wave per head.  An odd head_dim is PGK_ERR_INVALID.
+ * Nothing outside the head_dim columns of each Q and K head is read or written. */
+pgk_status pgk_flux_qk_norm_rope(void* q, void* k, int64_t row_stride, int64_t head_stride, const void* wq_a, const void* wk_a,
+                                 const void* wq_b, const void* wk_b, const float* cos, const float* sin, int batch, int seq, int split,
+                                 int heads, int head_dim, float eps, pgk_dtype dt, pgk_dtype w_dt, pgk_stream s);
+/* Host only: "flux_qk_norm_rope_vec" or "flux_qk_norm_rope_scalar"; NULL and pgk_last_error for an odd or oversized head_dim. */
+const char* pgk_flux_qk_norm_rope_plan(int head_dim, pgk_dtype dt, int aligned);
+/* out[r * out_stride + c] = gelu(x[r * cols + c]) (tanh form, the gelu op's device function: bit-identical to it); 16-byte
+ * accesses when both pointers, cols and out_stride allow. */
+pgk_status pgk_flux_gelu_pack(const void* x, void* out, int64_t rows, int cols, int64_t out_stride, pgk_dtype dt, pgk_stream s);
+/* in [B, h * w, C * 4] with columns (c, ph, pw) -> out [B, C, 2h, 2w]; a pure move of 2- or 4-byte elements. */
+pgk_status pgk_flux_unpack_latents(const void* in, void* out, int B, int C, int h, int w, pgk_dtype dt, pgk_stream s);
+/* sample[i] = fma(dt_step, (float)v[i], sample[i]): the flow-matching Euler update; sample fp32, v in v_dt. */
+pgk_status pgk_flow_euler_step(float* sample, const void* v, size_t n, float dt_step, pgk_dtype v_dt, pgk_stream s);
+
 /* ------------------------------------------------------------------ VAE decoder ------ */
 /* conv2d (ops_conv2d.hip; reference: src/pygpukit/ops/conv.py conv2d):
  *   out[n][m][oy][ox] = bias[m] + sum_{c, ky, kx} weight[m][c][ky][kx] * X[n][c][oy * sh + ky * dh - ph][ox * sw + kx * dw - pw]

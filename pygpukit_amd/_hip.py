@@ -149,6 +149,9 @@ _PROTOS = {
     "pgk_grouped_gemm_sorted": [_V, _V, _V, _V, _I, _V, _I, _V, _V, _I, _I, _I, _I, _I, _V],
     "pgk_adaln_fused": [_V, _V, _V, _V, _V, _V, _I64, _V, _V, _I64, _V, _V, _I64, _I, _I, _I, _F, _I, _I, _I, _I, _V],
     "pgk_patchify": [_V, _V, _I, _I, _I, _I, _I, _I, _V], "pgk_unpatchify": [_V, _V, _I, _I, _I, _I, _I, _I, _V],
+    "pgk_flux_qk_norm_rope": [_V, _V, _I64, _I64, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _I, _V],
+    "pgk_flux_gelu_pack": [_V, _V, _I64, _I, _I64, _I, _V], "pgk_flux_unpack_latents": [_V, _V, _I, _I, _I, _I, _I, _V],
+    "pgk_flow_euler_step": [_V, _V, _Z, _F, _I, _V],
     "pgk_comm_unique_id": [C.c_char_p], "pgk_comm_init": [c_void_pp, C.c_char_p, _I, _I], "pgk_comm_destroy": [_V],
     "pgk_comm_broadcast": [_V, _V, _Z, _I, _V], "pgk_comm_all_gather": [_V, _V, _V, _Z, _V],
     "pgk_comm_all_reduce_max_f64": [_V, _V, _I, _V], "pgk_comm_barrier": [_V, _V],
@@ -171,6 +174,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_base_op_plan": ([C.c_char_p, _Z, _I, _I, _I], C.c_char_p), "pgk_base_op_grid": ([C.c_char_p, _Z, _I, _I, _I], C.c_int),
                "pgk_audio_log_mel_plan": ([_I, _I, _I], C.c_int),
                "pgk_adaln_plan": ([_I, _I, _I], C.c_char_p),
+               "pgk_flux_qk_norm_rope_plan": ([_I, _I, _I], C.c_char_p),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}
