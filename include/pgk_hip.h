@@ -610,6 +610,26 @@ pgk_status pgk_engine_launches_per_step(pgk_engine e, int* n);
  * with the cache length as its span; the replay runs the kernels named here over more slices than nsplit / span say,
  * which report the eager step. */
 pgk_status pgk_engine_attn_plan(pgk_engine e, int batch, int max_position, char* out, size_t n);
+/* Read-only: the PROJECTION launches (w_qkv, w_o, w_gate_up, w_down, lm_head), computed by the functions the launchers
+ * themselves call; no device work, no state change.
+ * prefill_n == 0: one decode step of `batch` sequences whose largest position is `max_position`.  Per chunk one line
+ *   chunk b0=<first sequence> m=<sequences> form=gemv|batched|tiled|packed act=f32|bf16 oproj=fused|merged|own
+ *         carried=<0|1> normrows=<0|1> attn16=direct|normrows|none
+ * (act: the activation type the chunk's projections read; oproj: inside the fused attention kernel, inside the split-KV
+ * merge kernel, or a launch of its own; carried: o_proj / down_proj carry the next RMSNorm; normrows: norm_rows_bf16
+ * launches in front of the consumers; attn16: who writes o_proj's bf16 input rows), followed by one line per projection:
+ *   proj name=<p> kernel=fused_gemv m=<M> act=.. w=bf16|fp8|nvf4 pro=norm|plain|norm_sum r=<rows per wave> c=<preload
+ *        depth, 0: the generic loop> grid=<workgroups> n=<outputs> k=<K>
+ *   proj name=<p> kernel=batched_reg|batched_lds|batched_mt w=bf16|fp8 rows=<weight rows per workgroup> mp=<LDS image
+ *        rows> tiles=<M tiles of 16 per workgroup> copy=<1: reads the fragment-major copy> grid=.. n=.. k=..
+ *   proj name=<p> kernel=pkgemm|pkgemm_resid splits=<split-K slabs> n=.. k=..
+ * (no `o` line where o_proj is fused or merged).
+ * prefill_n > 0: one pgk_engine_prefill call of prefill_n tokens (batch / max_position ignored); one line
+ *   prefill n=.. path=ws|pk|gemm|fp8act ws=.. pk=.. pk_heads=.. carried=.. pkd=.. nvf4=.. fp8act=.. fuse_heads=..
+ *           fuse_heads8=.. fuse_sw16=.. fuse_sw8=.. s_qkv=.. s_o=.. s_gu=.. s_d=..
+ * path: wsgemm_nt, pkgemm_nt, the 128- / 256-tile engine_gemm_* kernels, gemm_fp8_*; s_*: the split-K slabs of the
+ * family that runs. */
+pgk_status pgk_engine_linear_plan(pgk_engine e, int batch, int max_position, int prefill_n, char* out, size_t n);
 
 /* ------------------------------------------------------------------ Mixture of Experts ------ */
 /* Routing, permutation and grouped expert GEMMs (ops_moe.hip).  Restates native/ops/moe/topk_kernels.cuh,

@@ -269,7 +269,7 @@ static pgk_status decode_chunk_batched(const StepCtx& cx, bool last) {
         if (pgk_status r = norm_x16(a)) return r;
         // 16-row workgroups (N / 16 >= 192) stream the fragment-major copy where the engine holds one: one coalesced KiB per
         // load instead of 64 separate 16-byte pieces of the row-major matrix (the batched lm_head's gain)
-        if (!FP8 && e->packed_ok) a.wp = e->packed[l].qkv;
+        if (batched_layer_copy(e, FP8)) a.wp = e->packed[l].qkv;
         if (pgk_status r = counted(cx.launches, batched_proj(FP8, tiled ? PRO_PLAIN : PRO_NORM, EPI_STORE, a, M, st))) return r;
         mark(KC_ATTN);
         if (pgk_status r = launch_attn(cx, l, af)) return r;
@@ -284,14 +284,14 @@ static pgk_status decode_chunk_batched(const StepCtx& cx, bool last) {
         a = gate_up_args(e, L, b0);
         a.out16 = e->act16 + (size_t)b0 * I;        // SiLU(g) * u leaves as bf16: down_proj rounds it to bf16 anyway
         if (pgk_status r = norm_x16(a)) return r;
-        if (!FP8 && e->packed_ok) a.wp = e->packed[l].gate_up;
+        if (batched_layer_copy(e, FP8)) a.wp = e->packed[l].gate_up;
         if (pgk_status r = counted(cx.launches, batched_proj(FP8, tiled ? PRO_PLAIN : PRO_NORM, EPI_SWIGLU, a, M, st))) return r;
         mark(KC_DOWN);
         a = down_args(e, L, b0);
         a.xin16 = e->act16 + (size_t)b0 * I;
         if (pgk_status r = counted(cx.launches, batched_proj(FP8, PRO_PLAIN, EPI_RESID, a, M, st))) return r;
     }
-    const int nblk = ceil_div(c.vocab_size, 16) < 2048 ? ceil_div(c.vocab_size, 16) : 2048;
+    const int nblk = batched_lm_blocks(c.vocab_size);   // engine_state.hip.h
     return finish_chunk(cx, last, nblk, e->lm_cap, [&](FusedArgs& a) -> pgk_status {
         a.wp = e->packed_lm;
         // the final norm keeps its launch: 2048 lm_head workgroups re-deriving the row statistic would read 128 MB of partials
@@ -352,7 +352,7 @@ static pgk_status decode_chunk_packed(const StepCtx& cx, bool last) {
         if (pgk_status r = counted(cx.launches, pkgemm_nt(act16, I, P.down, e->dec_slabs, H, PK_EPI_SLAB, s_d, M, H, I, nullptr, st))) return r;
         pending = s_d;
     }
-    const int nblk = ceil_div(c.vocab_size, 16) < 2048 ? ceil_div(c.vocab_size, 16) : 2048;
+    const int nblk = batched_lm_blocks(c.vocab_size);   // engine_state.hip.h
     if (pgk_status r = norm(e->final_norm)) return r;     // also folds the last down_proj's slabs into the residual stream
     return finish_chunk(cx, last, nblk, e->lm_cap, [&](FusedArgs& a) {
         a.xin16 = x16;
@@ -969,6 +969,112 @@ pgk_status pgk_engine_attn_plan(pgk_engine eh, int batch, int max_position, char
         used += (size_t)w;
         b0 += ch.m;
     }
+    return PGK_OK;
+}
+
+// Read-only: what the PROJECTIONS of one decode step (prefill_n == 0: `batch` sequences, largest position `max_position`) or of
+// one prefill call of prefill_n tokens launch, from the functions the launchers themselves call (next_chunk, attn_flags,
+// gemv_rows / gemv_preload / gemv_grid, batched_is_reg / batched_reg_rows / mt_rows_per_group / mt_tiles / batched_reads_copy,
+// pkgemm_pick_splits, prefill_choice).  Touches neither the device nor the engine's state.  Decode: per chunk one line
+//   chunk b0=<first sequence> m=<sequences> form=gemv|batched|tiled|packed act=f32|bf16 oproj=fused|merged|own carried=<0|1> normrows=<0|1> attn16=direct|normrows|none
+// and one line per projection (qkv, o, gate_up, down, lm_head; o is absent where it runs inside the attention / merge kernel)
+//   proj name=<p> kernel=fused_gemv m=<M> act=f32|bf16 w=bf16|fp8|nvf4 pro=norm|plain|norm_sum r=<rows per wave> c=<preload depth> grid=<workgroups> n=<N> k=<K>
+//   proj name=<p> kernel=batched_reg|batched_lds|batched_mt w=bf16|fp8 rows=<per workgroup> mp=<LDS image rows> tiles=<M tiles> copy=<0|1> grid=<workgroups> n=<N> k=<K>
+//   proj name=<p> kernel=pkgemm|pkgemm_resid splits=<K slabs> n=<N> k=<K>
+// Prefill: one line
+//   prefill n=<tokens> path=ws|pk|gemm|fp8act ws=.. pk=.. pk_heads=.. carried=.. pkd=.. nvf4=.. fp8act=.. fuse_heads=.. fuse_heads8=.. fuse_sw16=.. fuse_sw8=..
+//           s_qkv=.. s_o=.. s_gu=.. s_d=..   (the split-K slabs of the family that runs: wsgemm_nt, pkgemm_nt or engine_gemm_nt_slabs)
+pgk_status pgk_engine_linear_plan(pgk_engine eh, int batch, int max_position, int prefill_n, char* out, size_t n) {
+    PGK_REQUIRE(eh && out && n > 0, "pgk_engine_linear_plan: null argument");
+    const Engine* e = (const Engine*)eh;
+    const auto& c = e->cfg;
+    size_t used = 0;
+    out[0] = 0;
+    auto emit = [&](const char* fmt, auto... args) -> bool {
+        const int w = snprintf(out + used, n - used, fmt, args...);
+        if (w <= 0 || (size_t)w >= n - used) return false;
+        used += (size_t)w;
+        return true;
+    };
+    const int H = c.hidden_size, I = c.intermediate_size, QD = c.num_heads * c.head_dim, NQKV = e->qkv_dim(), V = c.vocab_size;
+    if (prefill_n > 0) {
+        PGK_REQUIRE(prefill_n <= c.max_seq_len, "pgk_engine_linear_plan: %d tokens outside cache of %d", prefill_n, c.max_seq_len);
+        const PrefillChoice p = prefill_choice(e, prefill_n);   // engine_prefill.hip
+        const char* path = p.fp8act ? "fp8act" : (p.pk ? "pk" : (p.ws ? "ws" : "gemm"));
+        const int s_qkv = p.ws && !p.pk ? p.s_qkv : 1, s_gu = p.ws && !p.pk ? p.s_gu : 1;
+        const int s_o = p.fp8act ? 1 : (p.pk ? (p.carried ? 1 : p.pk_so) : (p.ws ? p.s_o : p.g_so));
+        const int s_d = p.fp8act ? 1 : (p.pk ? (p.carried ? 1 : p.pk_sd) : (p.ws ? p.s_d : p.g_sd));
+        PGK_REQUIRE(emit("prefill n=%d path=%s ws=%d pk=%d pk_heads=%d carried=%d pkd=%d nvf4=%d fp8act=%d fuse_heads=%d fuse_heads8=%d fuse_sw16=%d fuse_sw8=%d "
+                         "s_qkv=%d s_o=%d s_gu=%d s_d=%d\n", prefill_n, path, (int)p.ws, (int)p.pk, (int)p.pk_heads, (int)p.carried, (int)p.pkd, (int)p.nv4,
+                         (int)p.fp8act, (int)p.fuse_heads, (int)p.fuse_heads8, (int)p.fuse_sw16, (int)p.fuse_sw8, s_qkv, s_o, s_gu, s_d),
+                    "pgk_engine_linear_plan: the plan needs more than %zu bytes", n);
+        return PGK_OK;
+    }
+    PGK_REQUIRE(batch >= 1 && batch <= c.max_batch, "pgk_engine_linear_plan: batch %d outside [1,%d]", batch, c.max_batch);
+    PGK_REQUIRE(max_position >= 0 && max_position < c.max_seq_len, "pgk_engine_linear_plan: position %d outside cache of %d", max_position, c.max_seq_len);
+    static const char* const forms[] = {"gemv", "batched", "tiled", "packed"};
+    const bool short_ctx = step_is_short_at(e, batch, max_position) && e->short_path;      // enqueue_step / decode_step
+    const bool fp8 = c.weight_format == 1 || c.weight_format == 2;
+    const int nw = c.weight_format == 3 ? GEMV_NW_NVF4 : (fp8 ? GEMV_NW_FP8 : GEMV_NW_BF16);   // decode_step: WT
+    const char* wname = c.weight_format == 3 ? "nvf4" : (fp8 ? "fp8" : "bf16");
+    bool ok = true;
+    for (int b0 = 0; b0 < batch && ok;) {
+        const ChunkChoice ch = next_chunk(e, batch - b0);
+        const AttnFlags af = attn_flags(e, ch.form, ch.m, short_ctx);
+        const int M = ch.m;
+        if (ch.form == CF_GEMV) {
+            const bool partials = af.fused || af.merged;                  // decode_chunk
+            const char* act = M >= 4 ? "bf16" : "f32";                    // decode_step_impl: XT
+            ok = emit("chunk b0=%d m=%d form=gemv act=%s oproj=%s carried=0 normrows=0 attn16=none\n", b0, M, act, af.fused ? "fused" : (af.merged ? "merged" : "own"));
+            auto gemv = [&](const char* name, int wnw, const char* wn, const char* pro, bool swiglu, int n_out, int K, int r, int force_grid) {
+                if (r == 0) r = gemv_rows(wnw, M, swiglu, n_out, K);      // launch_fused_auto
+                ok = ok && emit("proj name=%s kernel=fused_gemv m=%d act=%s w=%s pro=%s r=%d c=%d grid=%d n=%d k=%d\n", name, M, act, wn, pro, r,
+                                gemv_preload(wnw, r, K), gemv_grid(r, swiglu, n_out, force_grid), n_out, K);
+            };
+            gemv("qkv", nw, wname, "norm", false, NQKV, H, 0, 0);
+            if (!partials) gemv("o", nw, wname, "plain", false, H, QD, 0, 0);
+            gemv("gate_up", nw, wname, partials && M <= 2 ? "norm_sum" : "norm", true, I, H, 0, 0);
+            gemv("down", nw, wname, "plain", false, H, I, 0, 0);
+            gemv("lm_head", GEMV_NW_BF16, "bf16", "norm", false, V, H, 4, e->lm_blocks);
+        } else if (ch.form == CF_PACKED) {
+            const bool carried = e->packed_resid;                          // decode_chunk_packed
+            ok = emit("chunk b0=%d m=%d form=packed act=bf16 oproj=own carried=%d normrows=0 attn16=%s\n", b0, M, carried ? 1 : 0, af.direct ? "direct" : "normrows");
+            ok = ok && emit("proj name=qkv kernel=pkgemm splits=1 n=%d k=%d\n", NQKV, H);
+            ok = ok && emit("proj name=o kernel=%s splits=%d n=%d k=%d\n", carried ? "pkgemm_resid" : "pkgemm", carried ? 1 : pkgemm_pick_splits(M, H, QD), H, QD);
+            ok = ok && emit("proj name=gate_up kernel=pkgemm splits=1 n=%d k=%d\n", 2 * I, H);
+            ok = ok && emit("proj name=down kernel=%s splits=%d n=%d k=%d\n", carried ? "pkgemm_resid" : "pkgemm", carried ? 1 : pkgemm_pick_splits(M, H, I), H, I);
+            const int rows = mt_rows_per_group(V, true);
+            ok = ok && emit("proj name=lm_head kernel=batched_mt w=bf16 rows=%d mp=0 tiles=%d copy=%d grid=%d n=%d k=%d\n", rows, mt_tiles(M),
+                            batched_reads_copy(false, rows, e->packed_lm != nullptr) ? 1 : 0, batched_lm_blocks(V), V, H);
+        } else {
+            const bool tiled = ch.form == CF_TILED;                        // decode_chunk_batched
+            ok = emit("chunk b0=%d m=%d form=%s act=bf16 oproj=own carried=0 normrows=%d attn16=%s\n", b0, M, forms[ch.form], tiled ? 1 : 0,
+                      af.direct ? "direct" : (tiled ? "normrows" : "none"));
+            auto bat = [&](const char* name, bool wfp8, bool logits, bool have_copy, int N, int K) {
+                const char* wn = wfp8 ? "fp8" : "bf16";
+                if (tiled) {             // launch_batched_tiled / launch_batched_mt
+                    const int rows = mt_rows_per_group(N, logits);
+                    ok = ok && emit("proj name=%s kernel=batched_mt w=%s rows=%d mp=0 tiles=%d copy=%d grid=%d n=%d k=%d\n", name, wn, rows, mt_tiles(M),
+                                    batched_reads_copy(wfp8, rows, have_copy) ? 1 : 0, logits ? batched_lm_blocks(V) : ceil_div(N, rows), N, K);
+                } else if (batched_is_reg(K)) {   // launch_batched / launch_batched_reg
+                    const int rows = batched_reg_rows(N, logits);
+                    ok = ok && emit("proj name=%s kernel=batched_reg w=%s rows=%d mp=0 tiles=1 copy=%d grid=%d n=%d k=%d\n", name, wn, rows,
+                                    batched_reads_copy(wfp8, rows, have_copy) ? 1 : 0, logits ? batched_lm_blocks(V) : ceil_div(N, rows), N, K);
+                } else {
+                    ok = ok && emit("proj name=%s kernel=batched_lds w=%s rows=16 mp=%d tiles=1 copy=0 grid=%d n=%d k=%d\n", name, wn, M <= 8 ? 8 : 16,
+                                    logits ? batched_lm_blocks(V) : ceil_div(N, 16), N, K);
+                }
+            };
+            const bool lcopy = batched_layer_copy(e, fp8);
+            bat("qkv", fp8, false, lcopy, NQKV, H);
+            bat("o", fp8, false, false, H, QD);
+            bat("gate_up", fp8, false, lcopy, I, H);
+            bat("down", fp8, false, false, H, I);
+            bat("lm_head", false, true, e->packed_lm != nullptr, V, H);
+        }
+        b0 += ch.m;
+    }
+    PGK_REQUIRE(ok, "pgk_engine_linear_plan: the plan needs more than %zu bytes", n);
     return PGK_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "engine_common.hip.h"
+#include "engine_state.hip.h"
 
 namespace pgk {
 

@@ -617,17 +617,11 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
     tls.end();
 }
 
-// (Tried for the N = hidden projections at batch 64: 16 rows per workgroup - 64 workgroups, a quarter of the activation
-// traffic: 17.2 / 12.1 us against 15.5 / 11.1; and the weights of 16 rows parked in LDS with one wave per 16-row batch tile,
-// no cross-wave reduction: 16.4 us average.  A workgroup keeps at most ~64 KB of loads in flight, so 64 workgroups cannot
-// pull the 6 MB of weights plus their activation rows faster than 256 four-row workgroups that each re-read the rows.)
-static int mt_rows_per_group(int N, int epi) { return (epi == EPI_LOGITS || ceil_div(N, 16) >= 192) ? 16 : 4; }
-
 template <class WT, int EPI, int S>
 static pgk_status launch_batched_mt(const FusedArgs& a, int M, hipStream_t st, int nblk_logits) {
-    const int rpg = mt_rows_per_group(a.N, EPI);
+    const int rpg = mt_rows_per_group(a.N, EPI == EPI_LOGITS);   // engine_state.hip.h
     const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ceil_div(a.N, rpg);
-    const bool two = M <= 32;
+    const bool two = mt_tiles(M) == 2;
     hipError_t he = hipSuccess;
     if constexpr (EPI == EPI_LOGITS) {
         if (two) he = launch_k(batched_mt_kernel<WT, EPI, S, 16, 2>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
@@ -659,8 +653,7 @@ static pgk_status launch_batched_tiled(const FusedArgs& a, int M, hipStream_t st
 
 template <class WT, int PRO, int EPI, int S>
 static pgk_status launch_batched_reg(const FusedArgs& a, int M, hipStream_t st, int nblk_logits) {
-    // enough workgroups to pull HBM bandwidth: fewer weight rows per workgroup when N / 16 would leave CUs idle
-    int rpg = (EPI == EPI_LOGITS || ceil_div(a.N, 16) >= 192) ? 16 : (ceil_div(a.N, 8) >= 192 ? 8 : 4);
+    const int rpg = batched_reg_rows(a.N, EPI == EPI_LOGITS);   // engine_state.hip.h
     const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ceil_div(a.N, rpg);
     const float* x = (PRO == PRO_NORM) ? a.h : a.xin;
     hipError_t he;
@@ -688,10 +681,13 @@ static pgk_status launch_batched(const FusedArgs& a, int M, hipStream_t st, int 
     PGK_REQUIRE(a.K % 128 == 0 && M >= 1 && M <= 16, "batched decode projection: K=%d must be a multiple of 128 and M=%d in [1,16]", a.K, M);
     const int steps = a.K / 128, ngroups = ceil_div(a.N, 16);
     // register-resident activations at the instantiated widths; the LDS-image kernel below for every other K
-    if (steps == 8) return launch_batched_reg<WT, PRO, EPI, 8>(a, M, st, nblk_logits);
-    if (steps == 16) return launch_batched_reg<WT, PRO, EPI, 16>(a, M, st, nblk_logits);
-    if (steps == 24) return launch_batched_reg<WT, PRO, EPI, 24>(a, M, st, nblk_logits);
-    if (steps == 32) return launch_batched_reg<WT, PRO, EPI, 32>(a, M, st, nblk_logits);
+    if (batched_is_reg(a.K)) {   // engine_state.hip.h
+        if (steps == 8) return launch_batched_reg<WT, PRO, EPI, 8>(a, M, st, nblk_logits);
+        if (steps == 16) return launch_batched_reg<WT, PRO, EPI, 16>(a, M, st, nblk_logits);
+        if (steps == 24) return launch_batched_reg<WT, PRO, EPI, 24>(a, M, st, nblk_logits);
+        if (steps == 32) return launch_batched_reg<WT, PRO, EPI, 32>(a, M, st, nblk_logits);
+        return set_error(PGK_ERR_UNSUPPORTED, "batched decode projection: K=%d has no register-fragment kernel", a.K);
+    }
     // the prologue (RMSNorm of the M rows) is per workgroup: large N (lm_head) runs 2048 workgroups over several groups each
     const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ngroups;
     constexpr int NT = (EPI == EPI_SWIGLU) ? 2 : 1;

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "engine_common.hip.h"
+#include "engine_state.hip.h"
 
 namespace pgk {
 
@@ -399,7 +400,6 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
 
 template <class WT, class XT, int M, int R, int PRO, int EPI, int C>
 static pgk_status launch_fused_c(const FusedArgs& a, int n_out, hipStream_t st, int force_grid) {
-    constexpr int OUT_PER_TRIP = (EPI == EPI_SWIGLU) ? R / 2 : R;
     const size_t lds = (size_t)M * a.K * sizeof(XT);
     PGK_REQUIRE(lds <= 156 * 1024, "engine: %d activation rows of K=%d do not fit LDS", M, a.K);
     auto kfn = &fused_gemv_kernel<WT, XT, M, R, PRO, EPI, C>;
@@ -408,8 +408,7 @@ static pgk_status launch_fused_c(const FusedArgs& a, int n_out, hipStream_t st, 
         PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
         attr_done = true;
     }
-    int grid = force_grid ? force_grid : ceil_div(n_out, OUT_PER_TRIP * 4);
-    if (grid > 1024) grid = 1024;
+    const int grid = gemv_grid(R, EPI == EPI_SWIGLU, n_out, force_grid);   // engine_state.hip.h
     const float* x = (PRO == PRO_PLAIN) ? a.xin : a.h;
     const float* aux = (PRO == PRO_NORM_SUM) ? a.part : a.res;
     const int naux = (PRO == PRO_NORM_SUM) ? a.nsplit : a.ld_out;
@@ -417,46 +416,37 @@ static pgk_status launch_fused_c(const FusedArgs& a, int n_out, hipStream_t st, 
     return PGK_OK;
 }
 
-// Pick the preload depth C = K / (64 * NW) when the row is short enough to sit in registers.
+// The preload depth C (gemv_preload, engine_state.hip.h): the row's chunks sit in registers when it is short enough.
 template <class WT, class XT, int M, int R, int PRO, int EPI>
 static pgk_status launch_fused(const FusedArgs& a, int n_out, hipStream_t st, int force_grid = 0) {
-    constexpr int NW = WTraits<WT>::NW;
     constexpr bool NV4 = std::is_same<WT, nvf4x2>::value;   // NVF4: C in 1024-k units, (C + 1) / 2 chunks per lane
-    constexpr int UNIT = NV4 ? 1024 : 64 * NW;
-    const int c = (a.K % UNIT == 0) ? a.K / UNIT : 0;
-    constexpr int BUDGET = 12 / R;  // R*C*4 preload VGPRs <= 48
+    const int c = gemv_preload(WTraits<WT>::NW, R, a.K);
+    constexpr int BUDGET = 12 / R;  // R*C*4 preload VGPRs <= 48: the depths gemv_preload can return for this R are the ones instantiated
     if constexpr (1 <= BUDGET) { if (c == 1) return launch_fused_c<WT, XT, M, R, PRO, EPI, 1>(a, n_out, st, force_grid); }
     if constexpr ((NV4 ? 1 : 2) <= BUDGET) { if (c == 2) return launch_fused_c<WT, XT, M, R, PRO, EPI, 2>(a, n_out, st, force_grid); }
     if constexpr ((NV4 ? 2 : 3) <= BUDGET) { if (c == 3) return launch_fused_c<WT, XT, M, R, PRO, EPI, 3>(a, n_out, st, force_grid); }
     if constexpr ((NV4 ? 2 : 4) <= BUDGET) { if (c == 4) return launch_fused_c<WT, XT, M, R, PRO, EPI, 4>(a, n_out, st, force_grid); }
     if constexpr ((NV4 ? 3 : 6) <= BUDGET) { if (c == 6) return launch_fused_c<WT, XT, M, R, PRO, EPI, 6>(a, n_out, st, force_grid); }
+    PGK_REQUIRE(c == 0, "engine: preload depth %d at %d rows per wave is not instantiated", c, R);
     return launch_fused_c<WT, XT, M, R, PRO, EPI, 0>(a, n_out, st, force_grid);
 }
 
-// rows-per-wave heuristic: enough workgroups to cover 256 CUs even for the N = hidden projections
+// The rows per wave R (gemv_rows, engine_state.hip.h); only the R a (weight kind, M, epilogue) can be given are instantiated.
 template <class WT, class XT, int M, int PRO, int EPI>
 static pgk_status launch_fused_auto(const FusedArgs& a, int n_out, hipStream_t st) {
+    const int r = gemv_rows(WTraits<WT>::NW, M, EPI == EPI_SWIGLU, n_out, a.K);
     if constexpr (std::is_same<WT, nvf4x2>::value && M >= 4) {
-        // NVF4, 4 / 8 sequences: 4 rows per wave hold 2 x R x M partial sums besides the activation fragments - 190 to 256
-        // VGPRs, one wave per SIMD; 2 rows per wave stay near the bf16 kernels' ~120
-        return launch_fused<WT, XT, M, 2, PRO, EPI>(a, n_out, st);
-    }
-    if constexpr (EPI == EPI_SWIGLU) {
-        // One sequence, mid-sized gate/up (Qwen3-0.6B: 3072 pairs): 3 pairs per wave = 256 workgroups, one per CU.  Every
-        // workgroup's prologue re-reads h and the 8 o_proj partial vectors (36 KB from L2); with 768 two-pair workgroups that
-        // was 108 KB per CU through the texture addresser against 49 KB of weights (gate/up span 4.32 -> 3.69 us, step 0.607
-        // -> 0.592 ms; 4 pairs per wave = 384 workgroups: 4.28 us).  Needs the 6 rows x C chunks to fit the preload budget.
-        if constexpr (M == 1) {
-            constexpr int NW = WTraits<WT>::NW;
-            if (n_out >= 2048 && n_out < 4096 && a.K % (64 * NW) == 0 && a.K / (64 * NW) <= 2) return launch_fused<WT, XT, M, 6, PRO, EPI>(a, n_out, st);
-        }
-        if (n_out >= 4096) return launch_fused<WT, XT, M, 4, PRO, EPI>(a, n_out, st);
-        return launch_fused<WT, XT, M, 2, PRO, EPI>(a, n_out, st);
+        if (r == 2) return launch_fused<WT, XT, M, 2, PRO, EPI>(a, n_out, st);
+    } else if constexpr (EPI == EPI_SWIGLU) {
+        if constexpr (M == 1) { if (r == 6) return launch_fused<WT, XT, M, 6, PRO, EPI>(a, n_out, st); }
+        if (r == 4) return launch_fused<WT, XT, M, 4, PRO, EPI>(a, n_out, st);
+        if (r == 2) return launch_fused<WT, XT, M, 2, PRO, EPI>(a, n_out, st);
     } else {
-        if (n_out >= 4096) return launch_fused<WT, XT, M, 4, PRO, EPI>(a, n_out, st);
-        if (n_out >= 2048) return launch_fused<WT, XT, M, 2, PRO, EPI>(a, n_out, st);
-        return launch_fused<WT, XT, M, 1, PRO, EPI>(a, n_out, st);
+        if (r == 4) return launch_fused<WT, XT, M, 4, PRO, EPI>(a, n_out, st);
+        if (r == 2) return launch_fused<WT, XT, M, 2, PRO, EPI>(a, n_out, st);
+        if (r == 1) return launch_fused<WT, XT, M, 1, PRO, EPI>(a, n_out, st);
     }
+    return set_error(PGK_ERR_UNSUPPORTED, "engine: %d rows per wave are not instantiated for this projection", r);
 }
 
 }  // namespace pgk

@@ -275,6 +275,47 @@ pgk_status packed_mlp_carried(Engine* e, int layer, int rows, const bf16* attn16
     return counted(launches, pkgemm_resid_nt(act16, I, P.down, h, rows, H, I, gnext, x16, e->pk_ss, ss_n, st));
 }
 
+// pgk_engine_prefill's choices for a chunk of n tokens, as a pure function of the engine's host state (and the
+// PGK_FUSED_EPILOGUES switch, read per call as before): pgk_engine_prefill executes them, pgk_engine_linear_plan prints them.
+PrefillChoice prefill_choice(const Engine* e, int n) {
+    const auto& c = e->cfg;
+    const int H = c.hidden_size, I = c.intermediate_size, D = c.head_dim, QD = c.num_heads * D, NQKV = e->qkv_dim();
+    PrefillChoice p{};
+    // split-K slabs of the N = hidden projections on the weight-streaming path (n <= 128)
+    const bool ws = p.ws = n <= 128;
+    p.s_o = ws ? wsgemm_pick_splits(H, QD, true) : 1; p.s_d = ws ? wsgemm_pick_splits(H, I, true) : 1;
+    p.s_qkv = ws ? wsgemm_pick_splits(NQKV, H, true) : 1; p.s_gu = ws ? wsgemm_pick_splits(2 * I, H, true) : 1;
+    // packed-weight path (ops_pkgemm.hip): bf16 layers, n <= 128; its own split counts for the N = hidden projections
+    const bool pk = p.pk = ws && e->packed_ok;
+    p.pk_so = pk ? pkgemm_pick_splits(n, H, QD) : 1; p.pk_sd = pk ? pkgemm_pick_splits(n, H, I) : 1;
+    p.pk_heads = pk && D == 128;       // QKV epilogue: per-head norm + RoPE + cache write inside the projection
+    p.carried = pk && e->packed_resid; // o_proj / down_proj carry the next RMSNorm
+    // long prompts, bf16 weights: the N = hidden projections as split-K slabs when their 128-tiles do not cover the chip
+    // (QKV / gate_up were tried too - their consumers can sum slabs - and measured slightly slower: 3.06 vs 2.99 ms at S = 512)
+    // w8a16 engines, long prompts: the staged bf16 GEMMs read the DEQUANTISED fragment-major copy the engine already holds
+    // (pack_weights_fp8: bf16(code x scale), the value the reference's w8a16 GEMM multiplies) - same kernels, epilogues and
+    // times as a bf16 engine (S = 512: 4.23 -> 2.44 ms) instead of the in-staging-dequant 128-tile kernel / a per-call
+    // dequantisation pass in front of the 256-tile kernel
+    const bool pkd = p.pkd = !ws && c.weight_format == 1 && e->packed_have && engine_gemm_packed_ok(n, NQKV, H) && engine_gemm_packed_ok(n, H, QD) &&
+                             engine_gemm_packed_ok(n, 2 * I, H) && engine_gemm_packed_ok(n, H, I);
+    p.nv4 = c.weight_format == 3;                 // NVF4: each layer's linears dequantised to bf16 (e->nv_deq), then the bf16 engine's path
+    const bool w16 = p.w16 = c.weight_format == 0 || p.nv4;   // the projections read bf16 row-major weights
+    const bool gsplit = p.gsplit = !ws && (w16 || pkd);
+    p.g_so = gsplit ? engine_gemm_pick_splits(n, H, QD) : 1; p.g_sd = gsplit ? engine_gemm_pick_splits(n, H, I) : 1;
+    const bool fp8 = p.fp8 = c.weight_format == 1 || c.weight_format == 2;
+    const bool fp8act = p.fp8act = c.weight_format == 2 && n > 128;   // fp8 x fp8 MFMA projections, activations quantised on the fly
+    // (PGK_FUSED_EPILOGUES=0 keeps the separate passes - quantise, SwiGLU: the A/B switch of the bit-identity tests)
+    const bool fuse_epi = p.fuse_epi = env_on("PGK_FUSED_EPILOGUES");
+    const bool fuse_q = p.fuse_q = fp8act && H % 128 == 0 && I % 128 == 0 && H <= 4096 && fuse_epi;
+    // SwiGLU in the gate / up GEMM's epilogue (256-tile kernels; fp8 x fp8: with the quantisation of its result)
+    p.fuse_sw8 = fuse_q && gemm_fp8_swiglu_ok(n, I, H);
+    p.fuse_sw16 = !fp8act && !ws && fuse_epi && engine_gemm_swiglu_ok(n, I, H, fp8 && !pkd);
+    // per-head norm + RoPE + cache write in the QKV GEMM's epilogue (bf16 weights, head_dim 128, 128-tile kernel: tile column = head)
+    p.fuse_heads8 = fuse_q && D == 128 && gemm_fp8_qkv_heads_ok(n, NQKV, H);      // fp8 x fp8: x's codes are already in q8
+    p.fuse_heads = p.fuse_heads8 || (!ws && !pk && fuse_epi && (w16 || pkd) && D == 128 && engine_gemm_qkv_heads_ok(n, NQKV, H));
+    return p;
+}
+
 // the per-head norm + RoPE + cache write arguments of a QKV projection's epilogue (PkArgs, QkvHeadArgs)
 template <class HeadArgs>
 static void fill_head_args(HeadArgs& hd, const Engine* e, const pgk_layer_weights_t& L, bf16* kc, bf16* vc, int start_pos) {
@@ -304,27 +345,12 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
     // GEMM and the epilogue fusions of round 3 the long-prompt path is faster at every such length: 144 tokens 1.94 vs 2.38 ms,
     // 256 tokens 2.27 vs 2.62)
     const int H = c.hidden_size, I = c.intermediate_size, D = c.head_dim, QD = c.num_heads * D, NQKV = e->qkv_dim();
-    // split-K slabs of the N = hidden projections on the weight-streaming path (n <= 128)
-    const bool ws = n <= 128;
-    const int s_o = ws ? wsgemm_pick_splits(H, QD, true) : 1, s_d = ws ? wsgemm_pick_splits(H, I, true) : 1;
-    const int s_qkv_ws = ws ? wsgemm_pick_splits(NQKV, H, true) : 1, s_qkv = s_qkv_ws, s_gu = ws ? wsgemm_pick_splits(2 * I, H, true) : 1;
+    // which kernels the projections run on, their split-K slabs and epilogues: prefill_choice, above (also what
+    // pgk_engine_linear_plan prints)
+    const PrefillChoice pc = prefill_choice(e, n);
+    const bool ws = pc.ws, pk = pc.pk, pk_heads = pc.pk_heads, pkd = pc.pkd, nv4 = pc.nv4, w16 = pc.w16, gsplit = pc.gsplit;
+    const int s_o = pc.s_o, s_d = pc.s_d, s_qkv_ws = pc.s_qkv, s_qkv = pc.s_qkv, s_gu = pc.s_gu, pk_so = pc.pk_so, pk_sd = pc.pk_sd, g_so = pc.g_so, g_sd = pc.g_sd;
     const int maxk = I > QD ? (I > H ? I : H) : (QD > H ? QD : H);
-    // packed-weight path (ops_pkgemm.hip): bf16 layers, n <= 128; its own split counts for the N = hidden projections
-    const bool pk = ws && e->packed_ok;
-    const int pk_so = pk ? pkgemm_pick_splits(n, H, QD) : 1, pk_sd = pk ? pkgemm_pick_splits(n, H, I) : 1;
-    const bool pk_heads = pk && D == 128;       // QKV epilogue: per-head norm + RoPE + cache write inside the projection
-    // long prompts, bf16 weights: the N = hidden projections as split-K slabs when their 128-tiles do not cover the chip
-    // (QKV / gate_up were tried too - their consumers can sum slabs - and measured slightly slower: 3.06 vs 2.99 ms at S = 512)
-    // w8a16 engines, long prompts: the staged bf16 GEMMs read the DEQUANTISED fragment-major copy the engine already holds
-    // (pack_weights_fp8: bf16(code x scale), the value the reference's w8a16 GEMM multiplies) - same kernels, epilogues and
-    // times as a bf16 engine (S = 512: 4.23 -> 2.44 ms) instead of the in-staging-dequant 128-tile kernel / a per-call
-    // dequantisation pass in front of the 256-tile kernel
-    const bool pkd = !ws && c.weight_format == 1 && e->packed_have && engine_gemm_packed_ok(n, NQKV, H) && engine_gemm_packed_ok(n, H, QD) &&
-                     engine_gemm_packed_ok(n, 2 * I, H) && engine_gemm_packed_ok(n, H, I);
-    const bool nv4 = c.weight_format == 3;       // NVF4: each layer's linears dequantised to bf16 (e->nv_deq), then the bf16 engine's path
-    const bool w16 = c.weight_format == 0 || nv4; // the projections read bf16 row-major weights
-    const bool gsplit = !ws && (w16 || pkd);
-    const int g_so = gsplit ? engine_gemm_pick_splits(n, H, QD) : 1, g_sd = gsplit ? engine_gemm_pick_splits(n, H, I) : 1;
     const bool use_slabs = ws || g_so > 1 || g_sd > 1;
     const size_t slab_elems = std::max({(size_t)std::max({s_o, s_d, g_so, g_sd, pk_so, pk_sd}) * n * H, s_qkv > 1 ? (size_t)s_qkv * n * NQKV : 0,
                                         s_gu > 1 ? (size_t)s_gu * n * 2 * I : 0});
@@ -367,21 +393,12 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
         PGK_CHECK_HIP(hipMemcpyAsync(e->pf_tokens, h_tokens, (size_t)n * 4, hipMemcpyHostToDevice, st));
         PGK_CHECK_HIP(hipStreamSynchronize(st));  // h_tokens may be pageable: make the copy complete before returning control
     }
-    const bool fp8 = c.weight_format == 1 || c.weight_format == 2;
-    const bool fp8act = c.weight_format == 2 && n > 128;   // fp8 x fp8 MFMA projections, activations quantised on the fly
+    const bool fp8 = pc.fp8, fp8act = pc.fp8act;
     layout(e->pf);
     int pending = 0;   // split-K slabs of the previous projection still to be added into h32 by the next norm
     // fp8act: RMSNorm and SwiGLU leave their result in q8/q8s themselves (x_in == nullptr); attention output is
     // quantised here (its rows span all heads, a flash workgroup only sees one)
-    // (PGK_FUSED_EPILOGUES=0 keeps the separate passes - quantise, SwiGLU: the A/B switch of the bit-identity tests)
-    const bool fuse_epi = env_on("PGK_FUSED_EPILOGUES");
-    const bool fuse_q = fp8act && H % 128 == 0 && I % 128 == 0 && H <= 4096 && fuse_epi;
-    // SwiGLU in the gate / up GEMM's epilogue (256-tile kernels; fp8 x fp8: with the quantisation of its result)
-    const bool fuse_sw8 = fuse_q && gemm_fp8_swiglu_ok(n, I, H);
-    const bool fuse_sw16 = !fp8act && !ws && fuse_epi && engine_gemm_swiglu_ok(n, I, H, fp8 && !pkd);
-    // per-head norm + RoPE + cache write in the QKV GEMM's epilogue (bf16 weights, head_dim 128, 128-tile kernel: tile column = head)
-    const bool fuse_heads8 = fuse_q && D == 128 && gemm_fp8_qkv_heads_ok(n, NQKV, H);      // fp8 x fp8: x's codes are already in q8
-    const bool fuse_heads = fuse_heads8 || (!ws && !pk && fuse_epi && (w16 || pkd) && D == 128 && engine_gemm_qkv_heads_ok(n, NQKV, H));
+    const bool fuse_q = pc.fuse_q, fuse_sw8 = pc.fuse_sw8, fuse_sw16 = pc.fuse_sw16, fuse_heads8 = pc.fuse_heads8, fuse_heads = pc.fuse_heads;
     // one projection: accum = h32 += x W^T (fp32), else dst = x W^T (bf16).  With splits > 1 the result is left as fp32
     // split-K slabs - accum: for the next norm to add into h32 (pending), else for the consumer kernel to sum
     auto proj = [&](const bf16* x_in, const void* w, const void* sc, void* dst, bool accum, int N_, int K_, int splits, const bf16* wp = nullptr) -> pgk_status {
@@ -434,7 +451,7 @@ pgk_status pgk_engine_prefill(pgk_engine eh, int seq, const int32_t* h_tokens, i
         bf16* vc = e->vcache + (size_t)l * e->kv_layer_elems() + (size_t)seq * c.num_kv_heads * c.max_seq_len * D;
         // packed path with carried norms: layer 0 normalises with a launch; afterwards x holds bf16(h * gamma) and pk_ss the
         // row statistics, both left by the previous layer's down_proj
-        const bool carried = pk && e->packed_resid;
+        const bool carried = pc.carried;
         PkArgs nrm{};                                   // how the consumer of x scales its rows (all null: x is normalised)
         if (carried && l > 0) { nrm.ss_in = e->pk_ss; nrm.ss_n = ss_n; nrm.ss_eps = c.norm_eps; }
         else if (pgk_status r = norm((const bf16*)L.attn_norm, fuse_q)) return r;

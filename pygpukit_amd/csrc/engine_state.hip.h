@@ -55,9 +55,9 @@ struct Engine {
     bool packed_ok = false;     // the skinny-GEMM kernels of ops_pkgemm.hip can use the copy (their shape limits)
     bool packed_have = false;   // the copy exists (w8a16 engines: also for shapes beyond those kernels - the long-prompt GEMMs read it)
     size_t packed_bytes = 0;
-    bool packed_resid = false;      // o_proj / down_proj without K split, carrying the next RMSNorm (pkgemm_resid_nt); PGK_PACKED_RESID=0: split-K slabs + norm launches
+    bool packed_resid = false;      // o_proj / down_proj without K split, carrying the next RMSNorm (pkgemm_resid_nt) where pkgemm_resid_ok takes both shapes; otherwise split-K slabs + norm launches
     float* pk_ss = nullptr;         // its sum-of-squares table [128][PK_SS_LD]
-    bf16* packed_lm = nullptr;      // fragment-major lm_head for the batched (3..64 sequences) lm_head kernels; PGK_PACKED_LMHEAD=0: none
+    bf16* packed_lm = nullptr;      // fragment-major lm_head for the batched (3..64 sequences) lm_head kernels (vocabularies of whole 16-row groups, max_batch >= 3)
     float* dec_slabs = nullptr;     // 17..64 sequences on the packed kernels: split-K slabs of o_proj / down_proj [splits][M][H] (PGK_PACKED_DECODE=0: engine_batched kernels)
     bool packed_decode = false;
     // NVF4 engines (weight_format 3): ONE layer's linears dequantised to row-major bf16 [qkv | o | gate_up | down], refilled
@@ -173,6 +173,77 @@ inline AttnFlags attn_flags(const Engine* e, ChunkForm form, int M, bool short_c
 // 4, 2 and 1 heads: the size of the chunk that starts at head `off` of a group of G.
 inline bool group_instantiated(int G) { return G == 1 || G == 2 || G == 4; }
 inline int head_chunk(int G, int off) { return group_instantiated(G) ? G : ((G - off >= 4) ? 4 : ((G - off >= 2) ? 2 : 1)); }
+
+// ---- the projections' decisions, shared by their launchers and the read-only plan query (pgk_engine_linear_plan) ----------
+
+// fused_gemv_kernel (engine_gemv.hip.h).  Weight kinds: the k elements one lane loads per trip (WTraits<WT>::NW).
+enum { GEMV_NW_BF16 = 8, GEMV_NW_FP8 = 16, GEMV_NW_NVF4 = 32 };
+// Rows per wave R of a projection with n_out outputs (SwiGLU: pairs): enough workgroups to cover 256 CUs even for the
+// N = hidden projections.
+inline int gemv_rows(int nw, int M, bool swiglu, int n_out, int K) {
+    // NVF4, 4 / 8 sequences: 4 rows per wave hold 2 x R x M partial sums besides the activation fragments - 190 to 256
+    // VGPRs, one wave per SIMD; 2 rows per wave stay near the bf16 kernels' ~120
+    if (nw == GEMV_NW_NVF4 && M >= 4) return 2;
+    if (swiglu) {
+        // One sequence, mid-sized gate/up (Qwen3-0.6B: 3072 pairs): 3 pairs per wave = 256 workgroups, one per CU.  Every
+        // workgroup's prologue re-reads h and the 8 o_proj partial vectors (36 KB from L2); with 768 two-pair workgroups that
+        // was 108 KB per CU through the texture addresser against 49 KB of weights (gate/up span 4.32 -> 3.69 us, step 0.607
+        // -> 0.592 ms; 4 pairs per wave = 384 workgroups: 4.28 us).  Needs the 6 rows x C chunks to fit the preload budget.
+        if (M == 1 && n_out >= 2048 && n_out < 4096 && K % (64 * nw) == 0 && K / (64 * nw) <= 2) return 6;
+        return n_out >= 4096 ? 4 : 2;
+    }
+    return n_out >= 4096 ? 4 : (n_out >= 2048 ? 2 : 1);
+}
+// Preload depth C of a row of K elements at R rows per wave: K / (64 * NW) chunks (NVF4: K / 1024, (C + 1) / 2 chunks per lane)
+// when the row is short enough to sit in registers (R * C * 4 preload VGPRs <= 48) and the depth is instantiated; 0: the generic loop.
+inline int gemv_preload(int nw, int R, int K) {
+    const bool nv4 = nw == GEMV_NW_NVF4;
+    const int unit = nv4 ? 1024 : 64 * nw;
+    const int c = (K % unit == 0) ? K / unit : 0;
+    const bool inst = c == 1 || c == 2 || c == 3 || c == 4 || c == 6;
+    return inst && (nv4 ? (c + 1) / 2 : c) <= 12 / R ? c : 0;
+}
+// workgroups of a GEMV projection: 4 waves of R rows (SwiGLU: R / 2 pairs), at most 1024 (the lm_head forces its own count)
+inline int gemv_grid(int R, bool swiglu, int n_out, int force_grid) {
+    const int grid = force_grid ? force_grid : (n_out + (swiglu ? R / 2 : R) * 4 - 1) / ((swiglu ? R / 2 : R) * 4);
+    return grid > 1024 ? 1024 : grid;
+}
+
+// engine_batched.hip.h, 3..16 sequences: register-resident activation fragments at the instantiated widths K = 128 x
+// {8, 16, 24, 32} (batched_reg_kernel), the LDS-image kernel (batched_mfma_kernel) for every other K
+inline bool batched_is_reg(int K) { const int s = K / 128; return s == 8 || s == 16 || s == 24 || s == 32; }
+// ... weight rows per workgroup of batched_reg_kernel: enough workgroups to pull HBM bandwidth - fewer weight rows per
+// workgroup when N / 16 would leave CUs idle (the LDS-image kernel: always 16)
+inline int batched_reg_rows(int N, bool logits) { return (logits || (N + 15) / 16 >= 192) ? 16 : ((N + 7) / 8 >= 192 ? 8 : 4); }
+// ... 17..64 sequences (batched_mt_kernel): rows per workgroup and M tiles of 16 per workgroup
+// (Tried for the N = hidden projections at batch 64: 16 rows per workgroup - 64 workgroups, a quarter of the activation
+// traffic: 17.2 / 12.1 us against 15.5 / 11.1; and the weights of 16 rows parked in LDS with one wave per 16-row batch tile,
+// no cross-wave reduction: 16.4 us average.  A workgroup keeps at most ~64 KB of loads in flight, so 64 workgroups cannot
+// pull the 6 MB of weights plus their activation rows faster than 256 four-row workgroups that each re-read the rows.)
+inline int mt_rows_per_group(int N, bool logits) { return (logits || (N + 15) / 16 >= 192) ? 16 : 4; }
+inline int mt_tiles(int M) { return M <= 32 ? 2 : 4; }
+// ... both read the fragment-major copy only with bf16 weights and 16-row workgroups (whole 16-row groups; a ragged last group reads row-major)
+inline bool batched_reads_copy(bool fp8, int rows_per_group, bool have_copy) { return !fp8 && rows_per_group == 16 && have_copy; }
+// ... of the layer's QKV and gate / up matrices where the engine holds one (o_proj / down_proj: none); the lm_head: packed_lm
+inline bool batched_layer_copy(const Engine* e, bool fp8) { return !fp8 && e->packed_ok; }
+// argmax partial blocks per sequence of the batched lm_head
+inline int batched_lm_blocks(int vocab) { const int g = (vocab + 15) / 16; return g < 2048 ? g : 2048; }
+
+// pgk_engine_prefill's choices for a chunk of n tokens (engine_prefill.hip): which GEMM family each projection runs on, its
+// split-K slabs and the fused epilogues.
+struct PrefillChoice {
+    bool ws;            // n <= 128: weight-streaming kernels (wsgemm_nt, or pkgemm_nt with `pk`)
+    bool pk;            // ... on the fragment-major copy (ops_pkgemm.hip)
+    bool pk_heads;      // ... with the QKV epilogue (head_dim 128)
+    bool carried;       // ... o_proj / down_proj carry the next RMSNorm (pkgemm_resid_nt)
+    bool pkd;           // n > 128, w8a16: the staged bf16 GEMMs read the dequantised fragment-major copy
+    bool nv4, w16, gsplit, fp8, fp8act;
+    bool fuse_epi, fuse_q, fuse_sw8, fuse_sw16, fuse_heads8, fuse_heads;
+    int s_o, s_d, s_qkv, s_gu;   // wsgemm_nt split-K slabs
+    int pk_so, pk_sd;            // pkgemm_nt split-K slabs of the N = hidden projections
+    int g_so, g_sd;              // engine_gemm_nt_slabs split-K slabs of the N = hidden projections
+};
+PrefillChoice prefill_choice(const Engine* e, int n);
 
 // Host entries the prefill and the decode step's packed path (one row per SEQUENCE) share; defined in engine_prefill.hip.
 // h[r] += the *pending split-K slabs of the projection in front of this norm (then *pending = 0), x[r] = bf16(rmsnorm(h[r]) * gamma)

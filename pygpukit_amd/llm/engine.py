@@ -247,6 +247,36 @@ class Engine:
             out.append({k: int(v) if k in ("b0", "m", "nsplit", "span") else v for k, v in d.items()})
         return out
 
+    @staticmethod
+    def _plan_fields(line: str) -> dict:
+        d = dict(kv.split("=", 1) for kv in line.split()[1:])
+        return {k: int(v) if v.lstrip("-").isdigit() else v for k, v in d.items()}
+
+    def linear_plan(self, batch: int = 1, max_position: int = 0) -> list[dict]:
+        """What the projections of one decode step of `batch` sequences with largest position `max_position` launch, per
+        chunk of the step: {"b0", "m", "form", "act", "oproj", "carried", "normrows", "attn16", "proj": {name: {...}}} with
+        one entry of "proj" per launch among qkv / o / gate_up / down / lm_head (pgk_engine_linear_plan: the launchers'
+        own decision functions, read-only - it neither runs nor changes anything)."""
+        buf = C.create_string_buffer(16384)
+        _hip.call("pgk_engine_linear_plan", self.handle, batch, max_position, 0, buf, len(buf))
+        out: list[dict] = []
+        for line in buf.value.decode().splitlines():
+            d = self._plan_fields(line)
+            if line.startswith("chunk"):
+                d["proj"] = {}
+                out.append(d)
+            else:
+                out[-1]["proj"][d.pop("name")] = d
+        return out
+
+    def prefill_plan(self, n: int) -> dict:
+        """Which kernels one prefill call of n tokens runs its projections on: {"path": "ws" | "pk" | "gemm" | "fp8act",
+        the flags ws / pk / pk_heads / carried / pkd / nvf4 / fp8act / fuse_heads / fuse_heads8 / fuse_sw16 / fuse_sw8 and
+        the split-K slab counts s_qkv / s_o / s_gu / s_d} (pgk_engine_linear_plan, read-only)."""
+        buf = C.create_string_buffer(1024)
+        _hip.call("pgk_engine_linear_plan", self.handle, 1, 0, int(n), buf, len(buf))
+        return self._plan_fields(buf.value.decode().splitlines()[0])
+
     # ------------------------------------------------------------------ convenience
     def generate_greedy(self, prompt, max_new_tokens: int, *, use_graph: bool = True) -> list[int]:
         """Prompt + max_new_tokens greedy tokens for one sequence (slot 0): prefill, argmax of the last
