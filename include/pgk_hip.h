@@ -137,7 +137,8 @@ pgk_status pgk_binary(const void* a, const void* b, void* c, size_t n, int op, p
 pgk_status pgk_binary_inplace(void* a, const void* b, size_t n, int op, pgk_dtype dt, pgk_stream s);
 /* ops.cuh:139 bias_add_inplace: out[rows,features] += bias[features] */
 pgk_status pgk_bias_add_inplace(void* out, const void* bias, int rows, int features, pgk_dtype dt, pgk_stream s);
-/* ops.cuh:136 gelu (tanh form 0.7978845608/0.044715), :176-179 silu; act: 0 silu, 1 gelu, 2 sigmoid, 3 tanh, 4 relu2 */
+/* ops.cuh:136 gelu (tanh form 0.7978845608/0.044715), :176-179 silu; act: 0 silu, 1 gelu, 2 sigmoid, 3 tanh, 4 relu2,
+ * 14 quick_gelu = x * sigmoid(1.702 x) [build-defined: CLIP's hidden_act] */
 pgk_status pgk_activation(const void* x, void* y, size_t n, int act, pgk_dtype dt, pgk_stream s);
 /* ... and the unary family of ops.cuh:60-101 (src/pygpukit/ops/unary.py:16-260) through the same entry:
  * act 5 exp, 6 log, 7 relu, 8 sin, 9 cos, 10 sqrt, 11 rsqrt, 12 abs, 13 neg */
@@ -494,6 +495,21 @@ pgk_status pgk_sdpa_alibi(const void* q, const void* k, const void* v, const voi
 pgk_status pgk_sdpa_alibi_fixed_cache(const void* q, const void* k_cache, const void* v_cache, const void* slopes, void* out, int hq,
                                       int hkv, int q_len, int max_seq, int d, float scale, int h_context_len, const int32_t* ctx_buf,
                                       void* workspace, pgk_dtype dt, pgk_stream s);
+/* [build-defined: the reference's T5 encoder adds a dense [1, H, S, S] bias to materialised scores on the host]  sdpa_relbias:
+ *   out[h][i] = softmax_j(q[h][i] . k[h / rep][j] * scale + table[h][clamp(j - i, -radius, radius) + radius], ALL j < kv_len) . v[h / rep]
+ * - no mask, any q_len, kv_len >= 1; delta is KEY position minus QUERY position.  table: fp32 [hq][2 * radius + 1] on the device,
+ * one row per QUERY head, finite entries, radius >= 0; scale <= 0 means 1 / sqrt(d).  Strides in elements as in pgk_sdpa_noncausal.
+ * f16 / bf16 with d 64 or 128, radius <= 1024, 16-byte aligned q / k / v, 8-byte aligned out, q / kv strides multiples of 8 and
+ * out strides multiples of 4 elements run the MFMA flash kernel (FlashRelBias policy: the head's row staged in LDS, the score
+ * accumulators start from it; workspaces from the pool); anything else with d <= 256 - float32 included - and
+ * PYGPUKIT_FLASH_ATTENTION=0 run one wave per (head, query row) in fp32 (hq <= 65535).  d > 256 there: PGK_ERR_UNSUPPORTED. */
+pgk_status pgk_sdpa_relbias(const void* q, const void* k, const void* v, const void* table, void* out, int hq, int hkv, int q_len,
+                            int kv_len, int d, int radius, float scale, int64_t q_stride_h, int64_t q_stride_s, int64_t kv_stride_h,
+                            int64_t kv_stride_s, int64_t o_stride_h, int64_t o_stride_s, pgk_dtype dt, pgk_stream s);
+/* Host-only: "relbias_flash" or "relbias_rows", the kernel pgk_sdpa_relbias takes for this head_dim, radius and dtype; aligned:
+ * pointers and strides as the flash path needs them (a contiguous [H, S, D] call is).  NULL + pgk_last_error for head_dim outside
+ * 1..256, a negative radius or a non-float dtype. */
+const char* pgk_relbias_plan(int head_dim, int radius, pgk_dtype dt, int aligned);
 /* ops.cuh:294-300 sdpa_causal_fixed_cache / _ptr: Q[Hq,q_len,D] over the first context_len rows of
  * cache[Hc,max_seq,D].  ctx_buf (device int32) overrides h_context_len when non-NULL.  q_len == 1
  * uses split-KV flash-decoding (replaces native/ops/nn/flash_decoding.cuh:75-377, fp16-only there);

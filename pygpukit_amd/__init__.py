@@ -25,3 +25,5 @@ from pygpukit_amd.ops.nn.attention import (fa3_fp8_available, get_sm_version, sd
 from pygpukit_amd.ops.nn.linear import embed_token_position_ptr, ln_linear, ln_linear_plan, ln_linear_qkv_cache_ptr  # noqa: F401,E402
 from pygpukit_amd.ops.conv import conv1d, conv2d  # noqa: F401,E402
 from pygpukit_amd.ops.nn.norm import group_norm, group_norm_silu  # noqa: F401,E402
+from pygpukit_amd.ops.nn.relpos import (relbias_plan, relpos_bias_table, relpos_bucket, relpos_compute_bias, sdpa_relbias,  # noqa: F401,E402
+                                        sdpa_relbias_strided)

@@ -128,6 +128,7 @@ _PROTOS = {
     "pgk_alibi_add_bias": [_V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V],
     "pgk_sdpa_alibi": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
     "pgk_sdpa_alibi_fixed_cache": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _V, _V, _I, _V],
+    "pgk_sdpa_relbias": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
     "pgk_lstm": [_V, C.POINTER(LstmDir), C.POINTER(LstmDir), _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _V],
     "pgk_engine_create": [C.POINTER(ModelConfig), _V, _V, _V, C.POINTER(LayerWeights), c_void_pp],
     "pgk_engine_destroy": [_V], "pgk_engine_bytes": [_V, C.POINTER(_Z), C.POINTER(_Z)],
@@ -176,6 +177,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_audio_log_mel_plan": ([_I, _I, _I], C.c_int),
                "pgk_adaln_plan": ([_I, _I, _I], C.c_char_p),
                "pgk_flux_qk_norm_rope_plan": ([_I, _I, _I], C.c_char_p),
+               "pgk_relbias_plan": ([_I, _I, _I, _I], C.c_char_p),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}

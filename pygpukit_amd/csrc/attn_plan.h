@@ -75,6 +75,24 @@ inline SdpaKernel sdpa_full_pick(bool half, int d, bool in_aligned, bool out_ali
     return half && flash_on && flash2_ok(d, in_aligned, out_aligned8, sd) ? SDPA_FLASH2 : SDPA_NAIVE;
 }
 
+// ---- pgk_sdpa_relbias: the flash kernel with the FlashRelBias policy, or the one-wave-per-row fp32 kernel (ops_relbias.hip) ----
+// The staged table row is padded on both sides by the reach of a (wave, KV tile) pair - 64 keys + 32 query rows - so a tile that
+// is not entirely saturated reads table entries with no per-element clamp.  The radius bound keeps the row within 9 KiB of LDS
+// (64 KiB of K / V images at D = 128, two workgroups per CU in 160 KiB).
+constexpr int FL_RELBIAS_PAD = FL_BKV + 32, FL_RELBIAS_MAX_RADIUS = 1024, RELBIAS_ROWS_MAX_D = 256;
+inline size_t relbias_lds_bytes(int radius) { return (size_t)(2 * radius + 1 + 2 * FL_RELBIAS_PAD) * sizeof(float); }
+inline SdpaKernel relbias_pick(bool half, int d, int radius, bool in_aligned, bool out_aligned8, const FlashStrides& sd, bool flash_on) {
+    return half && flash_on && radius <= FL_RELBIAS_MAX_RADIUS && flash2_ok(d, in_aligned, out_aligned8, sd) ? SDPA_FLASH2 : SDPA_NAIVE;
+}
+// One wave's 32 query rows [qw0, qw0 + 32) against the 64 keys [kv0, kv0 + 64): delta = key - row spans
+// [kv0 - qw0 - 31, kv0 - qw0 + 63].  Entirely at or below -radius (far left) or at or above +radius (far right) the bias is one
+// value for the whole wave; anything else gathers from the padded row.
+enum RelbiasTile { RELBIAS_FAR_LEFT = 0, RELBIAS_NEAR = 1, RELBIAS_FAR_RIGHT = 2 };
+__host__ __device__ inline RelbiasTile relbias_tile_class(int kv0, int qw0, int radius) {
+    const int rel = kv0 - qw0;
+    return rel + FL_BKV - 1 <= -radius ? RELBIAS_FAR_LEFT : (rel - 31 >= radius ? RELBIAS_FAR_RIGHT : RELBIAS_NEAR);
+}
+
 // KV runs per query tile of the second-generation kernels: enough workgroups for two per CU (the kernels' occupancy), never more
 // runs than the shortest useful run of two KV tiles allows for the heaviest query tile.  cus: device_cu_count()
 inline int flash_nsplit(int nqt, int hq, int kv_len, int cus) {
@@ -99,5 +117,8 @@ pgk_status flash_prefill_alibi(const void* q, const void* k, const void* v, cons
                                int kv_len, int d, float scale, const FlashStrides& sd, int dt16, hipStream_t st);
 pgk_status flash_prefill_q8(const void* q, const void* k, const void* v, uint8_t* q8, float* q8s, int hq, int hkv, int q_len, int kv_len,
                             float scale, long long qh, long long qs, long long kh, long long ks, hipStream_t st);
+// table: [hq][2 * radius + 1] fp32 on the device, 0 <= radius <= FL_RELBIAS_MAX_RADIUS; scale > 0; any q_len, kv_len >= 1
+pgk_status flash_prefill_relbias(const void* q, const void* k, const void* v, const float* table, void* out, int hq, int hkv, int q_len,
+                                 int kv_len, int d, int radius, float scale, const FlashStrides& sd, int dt16, hipStream_t st);
 
 }  // namespace pgk

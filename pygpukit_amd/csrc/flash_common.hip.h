@@ -42,6 +42,14 @@ struct FlashIrope {
 struct FlashAlibi {
     const float* slopes;     // [Hq] fp32, one per QUERY head
 };
+// sdpa_relbias (ops_relbias.hip): no mask, as FlashFull; the score of (row i, key j) of query head h gets
+// table[h][clamp(j - i, -radius, radius) + radius] (T5's bucketed relative-position bias, folded to one entry per delta).  The
+// head's row is staged into LDS once per workgroup - in the exp2 domain, padded on both sides by FL_RELBIAS_PAD copies of the
+// saturated entries - and the accumulators of Q.K^T start from it (attn_plan.h: relbias_tile_class).
+struct FlashRelBias {
+    const float* table;      // [Hq][2 * radius + 1] fp32, one row per QUERY head
+    int radius;              // 0 .. FL_RELBIAS_MAX_RADIUS
+};
 
 // V^T image: [D][64 kv] 16-bit = 128-byte rows, 8-byte chunk c8 (0..15) of row d at d*128 + ((c8 ^ ((d>>1) & 15)) << 3):
 // the 32 rows a half-wave reads at one c8 then fall on 32 different bank pairs

@@ -35,6 +35,7 @@ __device__ __forceinline__ float act_fn(float x, int act) {
         case 10: return sqrtf(x);
         case 11: return 1.0f / sqrtf(x);
         case 12: return fabsf(x);
+        case 14: return x / (1.0f + expf(-1.702f * x));                                    // quick_gelu: x * sigmoid(1.702 x) (CLIP)
         default: return -x;
     }
 }
@@ -228,7 +229,7 @@ pgk_status pgk_bias_add_inplace(void* out, const void* bias, int rows, int featu
 
 pgk_status pgk_activation(const void* x, void* y, size_t n, int act, pgk_dtype dt, pgk_stream s) {
     PGK_REQUIRE(x && y, "pgk_activation: null pointer");
-    PGK_REQUIRE(act >= 0 && act <= 13, "pgk_activation: bad activation %d", act);
+    PGK_REQUIRE(act >= 0 && act <= 14, "pgk_activation: bad activation %d", act);
     if (!n) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     const bool al = aligned16(x) && aligned16(y);

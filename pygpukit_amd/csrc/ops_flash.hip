@@ -23,6 +23,8 @@
 // -slope[head] * (mask_off + q_pos - kv_pos), in the exp2 domain, instead of at zero - no extra pass over the scores.
 // With a FlashFull it is sdpa_noncausal (pgk_sdpa_noncausal, ops_attention.hip): the mask offset is kv_len, so no key is
 // ever above a diagonal; q_len may be smaller or larger than kv_len and any q_len >= 1 takes this kernel.
+// With a FlashRelBias it is sdpa_relbias (pgk_sdpa_relbias, ops_relbias.hip): FlashFull's mask, and the accumulators of S^T start
+// at table[head][clamp(kv_pos - q_pos, -R, R) + R] - the head's row staged once into LDS behind the K / V images.
 
 #include "flash_common.hip.h"
 
@@ -33,13 +35,15 @@ template <int D> __device__ __forceinline__ int fl_k_off(int r, int c) { return 
 
 // X = FlashPlain: sdpa_causal.  X = FlashIrope: sdpa_irope - the two differences are `if constexpr (IROPE)` below.
 // X = FlashAlibi: sdpa_alibi - the head's slope and the start value of the score accumulators, `if constexpr (ALIBI)`.
+// X = FlashRelBias: sdpa_relbias - FlashFull's mask offset, the staged table row and the start value, `if constexpr (RELBIAS)`.
 template <class T, int D, class X = FlashPlain>
 __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, const T* k, const T* vt, T* out, int hq, int hkv,
                                                               int q_len, int kv_len, int kv_pad, float scale_log2e, FlashStrides sd,
                                                               FlashSplit sp, X ex) {
     constexpr bool IROPE = std::is_same<X, FlashIrope>::value;
     constexpr bool ALIBI = std::is_same<X, FlashAlibi>::value;
-    constexpr bool FULL = std::is_same<X, FlashFull>::value;
+    constexpr bool RELBIAS = std::is_same<X, FlashRelBias>::value;
+    constexpr bool FULL = std::is_same<X, FlashFull>::value || RELBIAS;
     constexpr int NC = D / 8;            // 16-byte chunks per K row
     constexpr int KS = D / 16;           // k-steps of Q.K^T
     constexpr int DT = D / 32;           // 32-row tiles of O^T
@@ -109,6 +113,22 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
     // the origin is the same for every tile and KV run of a row, so m_run and the split records need no correction.
     float slope2 = 0.f;
     if constexpr (ALIBI) slope2 = ex.slopes[head] * 1.4426950408889634f;
+    // Relative-position bias: entry e of the LDS row is table[head][clamp(e - PAD, 0, 2R)] * log2(e), e in [0, 2R + 1 + 2 PAD).
+    // A (wave, tile) pair that is not saturated has kv0 - qw0 in (-R - 64, R + 31), so every index
+    // (kv0 + kv_local) - (qw0 + ql) + R + PAD it forms lies in [2, 2R + 2 PAD - 2]: inside the row with no clamp, for rows past
+    // q_len and keys past kv_len as well.  rb_lo / rb_hi: the two saturated values (wave-uniform).
+    float rb_lo = 0.f, rb_hi = 0.f;
+    float* const rb = reinterpret_cast<float*>(fl_smem + 2 * K_BYTES + 2 * V_BYTES);
+    int rb_idx = 0;     // + kv0 + local kv row: this lane's entry (negative on its own for late query rows, never once kv0 is added)
+    if constexpr (RELBIAS) {
+        const int w = 2 * ex.radius + 1;
+        const float* trow = ex.table + (size_t)head * w;
+        for (int e = tid; e < w + 2 * FL_RELBIAS_PAD; e += FL_THREADS)
+            rb[e] = trow[min(max(e - FL_RELBIAS_PAD, 0), w - 1)] * 1.4426950408889634f;    // visible after the barrier below
+        rb_lo = trow[0] * 1.4426950408889634f;
+        rb_hi = trow[w - 1] * 1.4426950408889634f;
+        rb_idx = ex.radius + FL_RELBIAS_PAD + 4 * h - (qw0 + ql);
+    }
 
     const int q_last = min(qt * FL_BQ + FL_BQ - 1, q_len - 1);
     const int kv_end = min(kv_len, causal_off + q_last + 1);
@@ -189,6 +209,20 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
             for (int r = 0; r < 16; ++r) {
                 s0[r] = fmaf(slope2, (float)((r & 3) + 8 * (r >> 2)), base);
                 s1[r] = fmaf(slope2, (float)(32 + (r & 3) + 8 * (r >> 2)), base);
+            }
+        } else if constexpr (RELBIAS) {
+            const RelbiasTile cls = relbias_tile_class(kv0, qw0, ex.radius);    // wave-uniform
+            if (cls == RELBIAS_NEAR) {
+                const float* e = rb + (rb_idx + kv0);      // 32 LDS reads at literal offsets from one address
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    s0[r] = e[(r & 3) + 8 * (r >> 2)];
+                    s1[r] = e[32 + (r & 3) + 8 * (r >> 2)];
+                }
+            } else {
+                const float b = cls == RELBIAS_FAR_LEFT ? rb_lo : rb_hi;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { s0[r] = b; s1[r] = b; }
             }
         } else {
 #pragma unroll
@@ -356,6 +390,12 @@ template <class T, int D, class X = FlashPlain>
 static pgk_status flash_launch(const T* q, const T* k, const T* v, T* out, int hq, int hkv, int q_len, int kv_len, float scale,
                                const FlashStrides& sd, hipStream_t st, uint8_t* q8 = nullptr, float* q8s = nullptr, X ex = X{},
                                int kv_seen = 0) {
+    // FlashRelBias: the table row sits behind the K / V images; the attribute is set once for the largest row
+    size_t lds_extra = 0, lds_extra_max = 0;
+    if constexpr (std::is_same<X, FlashRelBias>::value) {
+        lds_extra = relbias_lds_bytes(ex.radius);
+        lds_extra_max = relbias_lds_bytes(FL_RELBIAS_MAX_RADIUS);
+    }
     const int kv_pad = ceil_div(kv_len, 64) * 64;
     const int nqt = ceil_div(q_len, FL_BQ);
     const int nsplit = flash_nsplit(nqt, hq, kv_seen > 0 ? kv_seen : kv_len, device_cu_count());
@@ -374,12 +414,12 @@ static pgk_status flash_launch(const T* q, const T* k, const T* v, T* out, int h
     transpose_v_kernel<T, D><<<dim3(kv_pad / 64, hkv), 256, 0, st>>>(v, vt, kv_len, kv_pad, sd.kh, sd.ks);
     constexpr size_t LDS = 2 * (size_t)(64 * D * 2) + 2 * (size_t)(D * 128);
     static bool attr_done = false;
-    if (LDS > 48 * 1024 && !attr_done) {
+    if (LDS + lds_extra_max > 48 * 1024 && !attr_done) {
         PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd_kernel<T, D, X>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS + lds_extra_max)));
         attr_done = true;
     }
-    flash_fwd_kernel<T, D, X><<<nqt * hq * nsplit, FL_THREADS, LDS, st>>>(q, k, (const T*)vt, out, hq, hkv, q_len, kv_len, kv_pad,
+    flash_fwd_kernel<T, D, X><<<nqt * hq * nsplit, FL_THREADS, LDS + lds_extra, st>>>(q, k, (const T*)vt, out, hq, hkv, q_len, kv_len, kv_pad,
                                                                          scale * 1.4426950408889634f, sd, sp, ex);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && nsplit > 1) {
@@ -433,6 +473,12 @@ pgk_status flash_prefill_irope(const void* q, const void* k, const void* v, cons
 pgk_status flash_prefill_alibi(const void* q, const void* k, const void* v, const float* slopes, void* out, int hq, int hkv, int q_len,
                                int kv_len, int d, float scale, const FlashStrides& sd, int dt16, hipStream_t st) {
     return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, scale, sd, st, FlashAlibi{slopes}, 0);
+}
+
+// every KV run of every query tile is live, as in flash_prefill_full; the callers have checked 0 <= radius <= FL_RELBIAS_MAX_RADIUS
+pgk_status flash_prefill_relbias(const void* q, const void* k, const void* v, const float* table, void* out, int hq, int hkv, int q_len,
+                                 int kv_len, int d, int radius, float scale, const FlashStrides& sd, int dt16, hipStream_t st) {
+    return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, scale, sd, st, FlashRelBias{table, radius}, kv_len);
 }
 
 // engine entry (fp8 x fp8 prefill, bf16, head_dim 128, q_len > 128): causal attention whose result leaves as the o_proj's fp8

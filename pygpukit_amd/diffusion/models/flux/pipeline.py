@@ -1,6 +1,7 @@
 """FLUX generation loop (reference: src/pygpukit/diffusion/models/flux/pipeline.py) on precomputed text embeddings: noise is drawn
-once on the host, then transformer -> scheduler step -> unpack -> VAE.decode all stay on the device.  The text encoders (T5,
-CLIP) and their tokenisers are not built, so a string prompt, encode_prompt and from_pretrained raise and point at prompt_embeds."""
+once on the host, then transformer -> scheduler step -> unpack -> VAE.decode all stay on the device.  Given text_encoder= (a
+CLIPTextEncoder) and text_encoder_2= (a T5Encoder), encode_prompt and a string prompt work; without them they raise and point at
+prompt_embeds, as from_pretrained always does (hub layouts and downloads are out of scope)."""
 
 from __future__ import annotations
 
@@ -15,15 +16,18 @@ from pygpukit_amd.diffusion.models.flux.scheduler import FlowMatchEulerScheduler
 from pygpukit_amd.diffusion.ops.flux import flux_unpack_latents
 from pygpukit_amd.diffusion.ops.patch import patchify
 
-_NO_ENCODERS = ("the T5 / CLIP text encoders are not built: pass prompt_embeds [B, tokens, joint_attention_dim] and "
+_NO_ENCODERS = ("no T5 / CLIP text encoders were given (text_encoder=, text_encoder_2=): pass prompt_embeds [B, tokens, joint_attention_dim] and "
                 "pooled_prompt_embeds [B, pooled_projection_dim] computed elsewhere")
 
 
 class FluxPipeline:
     """pipe(prompt_embeds, pooled_prompt_embeds, height, width) -> image GPUArray [B, 3, height, width] in [-1, 1]."""
 
-    def __init__(self, transformer: FluxTransformer, vae, scheduler: "FlowMatchEulerScheduler | None" = None):
+    def __init__(self, transformer: FluxTransformer, vae, scheduler: "FlowMatchEulerScheduler | None" = None, *, text_encoder=None,
+                 text_encoder_2=None):
         self.transformer = transformer
+        self.text_encoder = text_encoder            # CLIP: pooled_prompt_embeds
+        self.text_encoder_2 = text_encoder_2        # T5: prompt_embeds
         self.vae = vae
         self.scheduler = scheduler or FlowMatchEulerScheduler(FlowMatchEulerSchedulerConfig())
         self.vae_scale_factor = 16                                  # 8x VAE and 2x2 packing
@@ -36,8 +40,19 @@ class FluxPipeline:
         raise NotImplementedError(f"FluxPipeline.from_pretrained: {_NO_ENCODERS}; build the pipeline from FluxTransformer.from_safetensors "
                                   "and VAE.from_safetensors")
 
-    def encode_prompt(self, prompt, max_sequence_length: int = 512):
-        raise NotImplementedError(f"FluxPipeline.encode_prompt: {_NO_ENCODERS}")
+    def _has_encoders(self) -> bool:
+        return getattr(self, "text_encoder", None) is not None and getattr(self, "text_encoder_2", None) is not None
+
+    def encode_prompt(self, prompt, max_sequence_length: int = 512, *, mask_padding: bool = True):
+        """-> (pooled [B, pooled_projection_dim], t5_embeds [B, max_sequence_length, joint_attention_dim]), the reference's order.
+        CLIP is padded / truncated to 77 tokens, T5 to max_sequence_length.  mask_padding=True keeps T5's padding out of its
+        attention (the reference's mask); False attends it, as diffusers' FluxPipeline does."""
+        if not self._has_encoders():
+            raise NotImplementedError(f"FluxPipeline.encode_prompt: {_NO_ENCODERS}")
+        clip_ids, clip_mask = self.text_encoder.tokenize(prompt, max_length=77)
+        _, pooled = self.text_encoder.forward(clip_ids, clip_mask)
+        t5_ids, t5_mask = self.text_encoder_2.tokenize(prompt, max_length=max_sequence_length)
+        return pooled, self.text_encoder_2.forward(t5_ids, t5_mask if mask_padding else None)
 
     # ------------------------------------------------------------------ latent packing
     @staticmethod
@@ -65,8 +80,14 @@ class FluxPipeline:
     # ------------------------------------------------------------------ generation
     def __call__(self, prompt_embeds=None, pooled_prompt_embeds=None, height: int = 512, width: int = 512, num_inference_steps: int = 4,
                  guidance_scale: float = 0.0, seed: "int | None" = None, latents=None, prompt=None) -> GPUArray:
-        if isinstance(prompt_embeds, str) or prompt is not None:
-            raise NotImplementedError(f"FluxPipeline: {_NO_ENCODERS}")
+        is_text = isinstance(prompt_embeds, str) or (isinstance(prompt_embeds, (list, tuple)) and len(prompt_embeds) > 0
+                                                     and all(isinstance(p, str) for p in prompt_embeds))
+        if is_text and prompt is None:              # the reference's first positional argument is the prompt
+            prompt, prompt_embeds = prompt_embeds, None
+        if prompt is not None:
+            if not self._has_encoders():
+                raise NotImplementedError(f"FluxPipeline: {_NO_ENCODERS}")
+            pooled_prompt_embeds, prompt_embeds = self.encode_prompt(prompt)
         if prompt_embeds is None or pooled_prompt_embeds is None:
             raise ValueError("FluxPipeline: prompt_embeds and pooled_prompt_embeds are required")
         if height % 16 or width % 16:

@@ -5,7 +5,7 @@ from __future__ import annotations
 from pygpukit_amd.core.array import GPUArray
 from pygpukit_amd.ops._common import call, check_out, validate_float
 
-_ACT = {"silu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "relu2": 4}
+_ACT = {"silu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "relu2": 4, "quick_gelu": 14}
 
 
 def _act(a: GPUArray, name: str, out: GPUArray | None) -> GPUArray:
@@ -35,3 +35,8 @@ def tanh(a: GPUArray, *, out: GPUArray | None = None) -> GPUArray:
 
 def relu2(a: GPUArray, *, out: GPUArray | None = None) -> GPUArray:
     return _act(a, "relu2", out)
+
+
+def quick_gelu(a: GPUArray, *, out: GPUArray | None = None) -> GPUArray:
+    """[build-defined] x * sigmoid(1.702 x), CLIP's `hidden_act="quick_gelu"`, in one pass; `out` may alias the input."""
+    return _act(a, "quick_gelu", out)
