@@ -102,6 +102,26 @@ inline int flash_nsplit(int nqt, int hq, int kv_len, int cus) {
     return nsplit;
 }
 
+// One launch of a second-generation kernel (16-bit tensors): its grid factors and its workspace, one stream-ordered allocation of
+// `bytes` carved into V^T [Hkv][D][kv_pad] at 0 | partial O | (m, l) (both only when nsplit > 1) | extra_bytes of the caller's own,
+// every region a multiple of 256 bytes.  kv_seen: the keys the heaviest query tile walks, which is what the split is sized by.
+struct FlashPlan {
+    int kv_pad, nqt, nsplit;
+    size_t po_off, ml_off, extra_off, bytes;
+};
+inline FlashPlan flash_plan(int hq, int hkv, int q_len, int kv_len, int kv_seen, int d, int cus, size_t extra_bytes = 0) {
+    auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    FlashPlan p;
+    p.kv_pad = ceil_div(kv_len, 64) * 64;
+    p.nqt = ceil_div(q_len, FL_BQ);
+    p.nsplit = flash_nsplit(p.nqt, hq, kv_seen, cus);
+    p.po_off = up256((size_t)hkv * d * p.kv_pad * 2);
+    p.ml_off = p.po_off + (p.nsplit > 1 ? up256((size_t)p.nsplit * q_len * hq * d * 2) : 0);
+    p.extra_off = p.ml_off + (p.nsplit > 1 ? up256((size_t)p.nsplit * hq * q_len * 2 * sizeof(float)) : 0);
+    p.bytes = p.extra_off + up256(extra_bytes);
+    return p;
+}
+
 // ---- entry points across the family's translation units -----------------------------------------------------------------------
 bool sdpa_flash_enabled();   // ops_attention.hip: PYGPUKIT_FLASH_ATTENTION, for the engine's direct use of flash_prefill_q8
 

@@ -1,5 +1,6 @@
-// Pieces shared by the flash-attention prefill kernels (ops_flash.hip: bf16 / f16 products; ops_flash_fp8.hip: e4m3 first
-// product): MFMA / packing wrappers, the V^T image and its transposing pre-pass, the KV split and its merge kernel.
+// Types and kernels around the flash-attention prefill kernels (ops_flash.hip: bf16 / f16 products; ops_flash_fp8.hip: e4m3
+// first product): MFMA / packing wrappers (also used by the conv and audio kernels), the policies, the V^T image and its
+// transposing pre-pass, the KV split and its merge kernel.  The kernels' shared tile walk is flash_core.hip.h.
 #pragma once
 
 #include <type_traits>
@@ -31,6 +32,7 @@ template <> __device__ __forceinline__ uint32_t pack16x2<f16>(float lo, float hi
 // a free mask offset.  FlashAlibi: sdpa_alibi (ops_posenc.hip), mask as FlashPlain, the score of (row i, key j) of query head h
 // gets -slopes[h] * (kv_len - q_len + i - j): the MFMA accumulators of Q.K^T start at that bias instead of at zero.
 // FlashFull: sdpa_noncausal (ops_attention.hip), every key visible to every query row, kv_len and q_len unrelated.
+// FlashRelBias: sdpa_relbias (ops_relbias.hip), FlashFull's mask and a per-head table of biases by key - query distance (below).
 struct FlashPlain {};
 struct FlashFull {};        // sdpa_noncausal: no mask but the end of the keys (mask offset kv_len)
 struct FlashIrope {

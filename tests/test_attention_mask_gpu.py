@@ -194,7 +194,8 @@ def test_sdpa_causal_fp8(case):
     """Exact on every row whose last visible key lies below 704; ONE bf16 ulp on the rows beyond (only (2,1,130,1030,128) has
     any: its first run, bit-exact comparison on all rows, had 49 of 260 rows off by one ulp in 5.4 % of their elements).
 
-    The reason is in flash_fwd_fp8_kernel (csrc/ops_flash_fp8.hip).  The MFMA leaves RAW fp8 sums; the running maximum is
+    The reason is in flash_softmax_pv<.., SCALED = true> (csrc/flash_core.hip.h), the step flash_fwd_fp8_kernel
+    (csrc/ops_flash_fp8.hip) runs on each tile.  The MFMA leaves RAW fp8 sums; the running maximum is
     `mx = max(raw) * cf`, one fp32 rounding of the product, and the probabilities are `exp2(fmaf(raw, cf, -m_use))`, the
     product NOT rounded before the subtraction.  For the key that holds the maximum the exponent is therefore the rounding
     error of raw * cf instead of 0 (flash_fwd_kernel, whose MFMA returns the scaled scores themselves, subtracts a score
