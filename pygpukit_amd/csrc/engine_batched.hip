@@ -6,11 +6,10 @@
 
 #include "engine_common.hip.h"
 #include "engine_state.hip.h"
+#include "mfma_common.hip.h"
 
 namespace pgk {
 
-typedef __bf16 bf16x8_b __attribute__((ext_vector_type(8)));
-typedef float f32x4_b __attribute__((ext_vector_type(4)));
 #include "engine_batched.hip.h"
 
 // x16[m][:] = bf16(h[m][:] * rsqrt(mean(h[m]^2) + eps) * gamma)   (gamma == nullptr: plain fp32 -> bf16 rows)

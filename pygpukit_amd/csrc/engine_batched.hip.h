@@ -129,11 +129,7 @@ __global__ __launch_bounds__(256) void batched_mfma_kernel(unsigned long long* t
     const int am = l15 & (MP - 1);
     auto bfrag = [&](int t, int s) -> uint4 {
         if constexpr (FP8) {
-            const f32x2 c0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].x, false), c1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].x, true);
-            const f32x2 c2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].y, false), c3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].y, true);
-            const float sc = wsc[t][s];
-            return make_uint4(pack_bf16x2(c0.x * sc, c0.y * sc), pack_bf16x2(c1.x * sc, c1.y * sc), pack_bf16x2(c2.x * sc, c2.y * sc),
-                              pack_bf16x2(c3.x * sc, c3.y * sc));
+            return fp8x8_to_bf16x8(make_uint2(wv[t][s].x, wv[t][s].y), wsc[t][s]);
         } else {
             return wv[t][s];
         }
@@ -145,16 +141,16 @@ __global__ __launch_bounds__(256) void batched_mfma_kernel(unsigned long long* t
         if (g != (int)blockIdx.x) load_w(n0);
         float resv = 0.f;
         if constexpr (EPI == EPI_RESID) resv = a.res[(size_t)min(em, M - 1) * a.ld_out + min(n0 + en, N - 1)];
-        f32x4_b acc[NT];
+        f32x4_t acc[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = f32x4_b{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const int kc = (kw0 >> 3) + s * 4 + q;
             const uint4 af = *reinterpret_cast<const uint4*>(smem + ((size_t)kc * MP + am) * 16);
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b, af), __builtin_bit_cast(bf16x8_b, bfrag(t, s)), acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af), __builtin_bit_cast(bf16x8_t, bfrag(t, s)), acc[t], 0, 0, 0);
         }
         for (int s = S; s < steps; ++s) {          // steps beyond the preloaded ones stream through a plain loop
             const int k = kw0 + s * 32 + 8 * q;
@@ -167,14 +163,11 @@ __global__ __launch_bounds__(256) void batched_mfma_kernel(unsigned long long* t
                 if constexpr (FP8) {
                     const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(a.w) + row * K + k);
                     const float sc = to_f(a.wscale[(row >> 7) * (size_t)(K >> 7) + (k >> 7)]);
-                    const f32x2 c0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), c1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
-                    const f32x2 c2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), c3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
-                    b = make_uint4(pack_bf16x2(c0.x * sc, c0.y * sc), pack_bf16x2(c1.x * sc, c1.y * sc), pack_bf16x2(c2.x * sc, c2.y * sc),
-                                   pack_bf16x2(c3.x * sc, c3.y * sc));
+                    b = fp8x8_to_bf16x8(v, sc);
                 } else {
                     b = load_nt16(reinterpret_cast<const bf16*>(a.w) + row * K + k);
                 }
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b, af), __builtin_bit_cast(bf16x8_b, b), acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af), __builtin_bit_cast(bf16x8_t, b), acc[t], 0, 0, 0);
             }
         }
         // sum the four K quarters: C tile element (m = 4 q + r, n = l15)
@@ -362,11 +355,7 @@ __global__ __launch_bounds__(256) void batched_reg_kernel(unsigned long long* tl
 
     auto bfrag = [&](int t, int s) -> uint4 {
         if constexpr (FP8) {
-            const f32x2 c0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].x, false), c1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].x, true);
-            const f32x2 c2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].y, false), c3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].y, true);
-            const float sc = wsc[t][s];
-            return make_uint4(pack_bf16x2(c0.x * sc, c0.y * sc), pack_bf16x2(c1.x * sc, c1.y * sc), pack_bf16x2(c2.x * sc, c2.y * sc),
-                              pack_bf16x2(c3.x * sc, c3.y * sc));
+            return fp8x8_to_bf16x8(make_uint2(wv[t][s].x, wv[t][s].y), wsc[t][s]);
         } else {
             return wv[t][s];
         }
@@ -377,14 +366,14 @@ __global__ __launch_bounds__(256) void batched_reg_kernel(unsigned long long* tl
         const int n0 = g * RPG;
         float resv = 0.f;
         if constexpr (EPI == EPI_RESID) resv = a.res[(size_t)min(em, M - 1) * a.ld_out + min(n0 + en, N - 1)];
-        f32x4_b acc[NT];
+        f32x4_t acc[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = f32x4_b{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < S; ++s)
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b, af[s]), __builtin_bit_cast(bf16x8_b, bfrag(t, s)), acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[s]), __builtin_bit_cast(bf16x8_t, bfrag(t, s)), acc[t], 0, 0, 0);
         // the next group's weights (lm_head: a workgroup walks several groups) travel while this one is reduced and stored
         if (g + (int)gridDim.x < ngroups) load_w((g + (int)gridDim.x) * RPG);
         __syncthreads();                                    // the previous trip's partial tiles have been read
@@ -513,11 +502,7 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
     if constexpr (NCH == 1) load_a(0, 0);
     auto bfrag = [&](int t, int s) -> uint4 {
         if constexpr (FP8) {
-            const f32x2 c0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].x, false), c1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].x, true);
-            const f32x2 c2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].y, false), c3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wv[t][s].y, true);
-            const float sc = wsc[t][s];
-            return make_uint4(pack_bf16x2(c0.x * sc, c0.y * sc), pack_bf16x2(c1.x * sc, c1.y * sc), pack_bf16x2(c2.x * sc, c2.y * sc),
-                              pack_bf16x2(c3.x * sc, c3.y * sc));
+            return fp8x8_to_bf16x8(make_uint2(wv[t][s].x, wv[t][s].y), wsc[t][s]);
         } else {
             return wv[t][s];
         }
@@ -533,11 +518,11 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
 #pragma unroll
             for (int t = 0; t < MT; ++t) resv[t] = a.res[(size_t)min(t * 16 + em, M - 1) * a.ld_out + min(n0 + en, N - 1)];
         }
-        f32x4_b acc[MT][NT];
+        f32x4_t acc[MT][NT];
 #pragma unroll
         for (int t = 0; t < MT; ++t)
 #pragma unroll
-            for (int u = 0; u < NT; ++u) acc[t][u] = f32x4_b{0.f, 0.f, 0.f, 0.f};
+            for (int u = 0; u < NT; ++u) acc[t][u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if constexpr (NCH > 1) load_a(0, 0);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -549,8 +534,8 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
                     const uint4 b = bfrag(u, c * CH + j);
 #pragma unroll
                     for (int t = 0; t < MT; ++t)
-                        acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b, af[c & 1][j][t]),
-                                                                             __builtin_bit_cast(bf16x8_b, b), acc[t][u], 0, 0, 0);
+                        acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[c & 1][j][t]),
+                                                                             __builtin_bit_cast(bf16x8_t, b), acc[t][u], 0, 0, 0);
                 }
             }
         }

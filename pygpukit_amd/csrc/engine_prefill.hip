@@ -5,6 +5,7 @@
 #include "engine_gemv.hip.h"
 #include "engine_state.hip.h"
 #include "gemm_epilogues.hip.h"
+#include "gemm_plan.h"      // wsgemm_pick_splits
 #include "pkgemm.hip.h"
 
 namespace pgk {
@@ -12,7 +13,6 @@ namespace pgk {
 pgk_status engine_gemm_nt(const bf16* A, const void* W, const bf16* wscale, bool fp8, void* C, bool accum_f32, int M,
                           int N, int K, hipStream_t st, bool packed = false);      // packed: W = the fragment-major bf16 copy
 bool engine_gemm_packed_ok(int M, int N, int K);
-int wsgemm_pick_splits(int N, int K, bool allow_split);
 int engine_gemm_pick_splits(int M, int N, int K);
 pgk_status engine_gemm_nt_slabs(const bf16* A, const void* W, float* slabs, int splits, int M, int N, int K, hipStream_t st, bool packed = false);
 pgk_status gemm_fp8_nt(const uint8_t* a, const float* sa, const uint8_t* w, const bf16* sw, void* c, bool accum_f32, int M,

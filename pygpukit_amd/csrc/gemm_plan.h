@@ -1,5 +1,6 @@
 // Host-side kernel choice of the dense GEMM family: pgk_gemm_nt, pgk_gemm_nn, pgk_w8a16_gemm_nk / _kn, pgk_gemv_fp8_bf16 and
-// pgk_gemm_fp8_nt.  Every `if` ladder of those dispatchers lives here as a pure function of the shape (plus PGK_GEMM256 /
+// pgk_gemm_fp8_nt, and of the grouped expert GEMM pgk_grouped_gemm_sorted (regime, K splits, row tiles: pgk_grouped_gemm_sorted_splits
+// is its query).  Every `if` ladder of those dispatchers lives here as a pure function of the shape (plus PGK_GEMM256 /
 // PGK_GEMM256S, read per call); the launchers switch on what these functions return and pgk_gemm_plan (ops_gemm.hip) prints
 // the same return values, so the plan query cannot drift from the dispatch.  No device, stream or pointer is touched here.
 #pragma once
@@ -29,18 +30,64 @@ inline int wsgemm_pick_mt(int M) {
     return mt <= 1 ? 1 : mt <= 2 ? 2 : mt <= 4 ? 4 : mt <= 8 ? 8 : 0;
 }
 
-// ---- gemm256_bf16_nt (ops_gemm256.hip) ---------------------------------------------------------------------------------------
+// K splits (fp32 slabs for the consumer to sum) so that ~256+ workgroups stream; normalised to a count that tiles K in whole
+// LDS tiles, which is what wsgemm_nt launches.
+constexpr int WS_KT = 256;        // K elements per LDS tile of the weight-streaming walk (wsgemm_core.hip.h)
+inline int ws_whole_tile_splits(int K, int s) {
+    const int kps = ceil_div(ceil_div(K, s), WS_KT) * WS_KT;
+    return ceil_div(K, kps);
+}
+inline int wsgemm_pick_splits(int N, int K, bool allow_split) {
+    const int nblk = ceil_div(N, 64);
+    if (!allow_split || nblk >= 192) return 1;
+    int s = ceil_div(256, nblk);
+    const int max_s = K / WS_KT;
+    if (s > max_s) s = max_s;
+    if (s > 16) s = 16;
+    if (s < 1) s = 1;
+    return ws_whole_tile_splits(K, s);
+}
+
+// ---- pgk_grouped_gemm_sorted (ops_moe.hip) -----------------------------------------------------------------------------------
+constexpr int MOE_TILE_ROWS = 128;      // rows per tile-table entry (both grouped-GEMM regimes)
+constexpr int MOE_WS_ROWS_MAX = 64;     // T*k/E at or below this: weight-streaming regime, above: 128 x 128 tiles
+inline int moe_max_tiles(int T, int k, int E) { return ceil_div((long long)T * k, MOE_TILE_ROWS) + E; }
+inline bool moe_ws_regime(int T, int k, int E) { return (long long)T * k <= (long long)MOE_WS_ROWS_MAX * E; }
+// K splits of the weight-streaming regime: enough (expected active expert, 64-column slab, split) workgroups to stream on
+// every CU.  1 in the tiled regime.
+inline int moe_sorted_splits(int T, int k, int E, int N, int K) {
+    if (!moe_ws_regime(T, k, E)) return 1;
+    const long long active = E < (long long)T * k ? E : (long long)T * k;
+    const long long wgs = active * ceil_div(N, 64);
+    int s = wgs >= 512 ? 1 : ceil_div(512, wgs);
+    const int max_s = K / WS_KT < 1 ? 1 : K / WS_KT;
+    if (s > max_s) s = max_s;
+    if (s > 16) s = 16;
+    return ws_whole_tile_splits(K, s);
+}
+// row tiles of 16 the weight-streaming kernel holds: no expert can have more rows than there are, or than a table entry
+inline int moe_ws_pick_mt(int T, int k) {
+    const long long rows = (long long)T * k;
+    return wsgemm_pick_mt((int)(rows < MOE_TILE_ROWS ? rows : MOE_TILE_ROWS));
+}
+
+// ---- gemm256_bf16_nt / gemm256_bf16_swiglu_nt (ops_gemm256.hip) --------------------------------------------------------------
+// Narrower tiles (three quarters of the columns: `ntn_narrow` of them where there were `ntn`) when they fill the rounds of the
+// chip better (cost = rounds x work per tile): Qwen3-0.6B's gate / up at S = 2048 is 8 x 24 = 192 tiles of 128 act columns
+// (three quarters of the CUs, one round) or 8 x 32 = 256 tiles of 96 (all of them).
+inline bool gemm256_narrow_fills_better(int ntm, int ntn, int ntn_narrow) {
+    return 0.75 * ceil_div(ntm * ntn_narrow, 256) < (double)ceil_div(ntm * ntn, 256) - 0.01;
+}
 enum Gemm256Kernel { G256_STAGGERED = 0, G256_STAGGERED_N192 = 1, G256_LOCKSTEP = 2 };
 inline Gemm256Kernel gemm256_pick(int M, int N, bool accum_f32, bool packed) {
     const int ntm = ceil_div(M, 256), ntn = ceil_div(N, 256);
     const char* e = getenv("PGK_GEMM256S");          // 0: two full stages, waves in lockstep; default: staggered phases
     if (!(packed || !e || atoi(e) != 0)) return G256_LOCKSTEP;
-    // 192-column tiles when they fill the rounds of the chip better (cost = rounds x work per tile)
-    const int ntn3 = N / 192;
-    const bool narrow = !accum_f32 && N % 192 == 0 &&
-                        0.75 * ceil_div(ntm * ntn3, 256) < (double)ceil_div(ntm * ntn, 256) - 0.01;
+    const bool narrow = !accum_f32 && N % 192 == 0 && gemm256_narrow_fills_better(ntm, ntn, N / 192);      // 192-column tiles
     return narrow ? G256_STAGGERED_N192 : G256_STAGGERED;
 }
+// the SwiGLU epilogue: 128 act columns per tile, or 96 (192-column B tiles)
+inline bool gemm256_swiglu_narrow(int M, int I) { return I % 96 == 0 && gemm256_narrow_fills_better(ceil_div(M, 256), I / 128, I / 96); }
 
 // ---- dispatch_mfma (ops_gemm.hip): smallest BM covering M (<= 128); BN as large as keeps >= ~256 workgroups in flight --------
 struct MfmaTile { int bm, bn; };

@@ -18,20 +18,15 @@
 // checkout: parity for this op is pinned on the oracle's restatement of the formula above).
 
 #include "gemv_core.hip.h"
+#include "mfma_common.hip.h"
 #include "gemm_epilogues.hip.h"
 #include "gemm_plan.h"
 #include "pgk_internal.h"
 
 namespace pgk {
 
-typedef int i32x8_q __attribute__((ext_vector_type(8)));
-typedef float f32x4_q __attribute__((ext_vector_type(4)));
-
 constexpr int F8_BM = 128, F8_BN = 128, F8_THREADS = 256;
 constexpr int F8_TILE = 128 * 128;   // bytes of one operand tile: 128 rows x 128 fp8
-
-// byte offset of 16-byte chunk kc (0..7) of row `row` in a [128][128 B] tile
-__device__ __forceinline__ int f8_off(int row, int kc) { return row * 128 + ((kc ^ (row & 7)) << 4); }
 
 template <int EPI>   // 0: bf16 C store; 1: fp32 C += (the engine's residual stream)
 __global__ __launch_bounds__(F8_THREADS) void gemm_fp8_kernel(const uint8_t* A, const float* sa, const uint8_t* W,
@@ -62,7 +57,7 @@ __global__ __launch_bounds__(F8_THREADS) void gemm_fp8_kernel(const uint8_t* A, 
     const uint8_t* b_p3 = W + (size_t)min(n0 + 96 + srow, N - 1) * K + skc * 16;
     const float* sa_p = sa + (size_t)min(m0 + (tid & 127), M - 1) * KB;
     const bf16* sw_row = sw + (size_t)blockIdx.x * KB;
-    const int st_off = f8_off(srow, skc);   // rows srow + 32 i share the swizzle (32 % 8 == 0)
+    const int st_off = swz128_off(srow, skc);   // rows srow + 32 i share the swizzle (32 % 8 == 0)
     auto load_tiles = [&](int kt) {
         const size_t kb = (size_t)kt * 128;
         ra0 = *reinterpret_cast<const uint4*>(a_p0 + kb); ra1 = *reinterpret_cast<const uint4*>(a_p1 + kb);
@@ -82,11 +77,11 @@ __global__ __launch_bounds__(F8_THREADS) void gemm_fp8_kernel(const uint8_t* A, 
         if (tid < F8_BM) Ss(buf)[tid] = rs_a * to_f(rs_w);
     };
 
-    f32x4_q acc[4][4];
+    f32x4_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_q{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     load_tiles(0);
     store_tiles(0);
@@ -94,25 +89,25 @@ __global__ __launch_bounds__(F8_THREADS) void gemm_fp8_kernel(const uint8_t* A, 
     for (int kt = 0; kt < KB; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < KB) load_tiles(kt + 1);
-        i32x8_q fa[4], fb[4];
-        f32x4_q sc[4];
+        i32x8_t fa[4], fb[4];
+        f32x4_t sc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int ar = wm * 64 + i * 16 + (lane & 15), br = wn * 64 + i * 16 + (lane & 15);
-            const uint4 a0 = *reinterpret_cast<const uint4*>(As(buf) + f8_off(ar, 2 * q));
-            const uint4 a1 = *reinterpret_cast<const uint4*>(As(buf) + f8_off(ar, 2 * q + 1));
-            const uint4 b0 = *reinterpret_cast<const uint4*>(Bs(buf) + f8_off(br, 2 * q));
-            const uint4 b1 = *reinterpret_cast<const uint4*>(Bs(buf) + f8_off(br, 2 * q + 1));
-            fa[i] = i32x8_q{(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-            fb[i] = i32x8_q{(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
+            const uint4 a0 = *reinterpret_cast<const uint4*>(As(buf) + swz128_off(ar, 2 * q));
+            const uint4 a1 = *reinterpret_cast<const uint4*>(As(buf) + swz128_off(ar, 2 * q + 1));
+            const uint4 b0 = *reinterpret_cast<const uint4*>(Bs(buf) + swz128_off(br, 2 * q));
+            const uint4 b1 = *reinterpret_cast<const uint4*>(Bs(buf) + swz128_off(br, 2 * q + 1));
+            fa[i] = i32x8_t{(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
+            fb[i] = i32x8_t{(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
             // C rows of tile i held by this lane: q*4 .. q*4+3
-            sc[i] = *reinterpret_cast<const f32x4_q*>(Ss(buf) + wm * 64 + i * 16 + q * 4);
+            sc[i] = *reinterpret_cast<const f32x4_t*>(Ss(buf) + wm * 64 + i * 16 + q * 4);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const f32x4_q t = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[i], fb[j], f32x4_q{0.f, 0.f, 0.f, 0.f},
+                const f32x4_t t = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[i], fb[j], f32x4_t{0.f, 0.f, 0.f, 0.f},
                                                                                   0, 0, 0, 0, 0, 0);
                 acc[i][j] += t * sc[i];
             }

@@ -24,13 +24,11 @@
 // Output: fp32 -> e4m3 round-to-nearest-even with satfinite (|x| > 448 -> +-448, 0x7E / 0xFE), NaN kept as a NaN
 // code, -0 -> 0x80; the 128x128 byte tile goes through LDS so that D is written with 16-byte stores.
 
+#include "mfma_common.hip.h"
 #include "pgk_device.hip.h"
 #include "pgk_internal.h"
 
 namespace pgk {
-
-typedef int i32x8_nn __attribute__((ext_vector_type(8)));
-typedef float f32x4_nn __attribute__((ext_vector_type(4)));
 
 constexpr int NN_BM = 128, NN_BN = 128, NN_BK = 128, NN_THREADS = 256;
 constexpr int NN_TILE = 128 * 128;   // bytes of one staged operand tile
@@ -127,11 +125,11 @@ __global__ __launch_bounds__(NN_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
             *reinterpret_cast<uint2*>(b + nn_off_b(ng * 8 + j, kg >> 1) + 8 * (kg & 1)) = make_uint2(lo[j], hi[j]);
     };
 
-    f32x4_nn acc[4][4];
+    f32x4_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_nn{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     load_tiles(0);
     store_tiles(0);
@@ -140,16 +138,16 @@ __global__ __launch_bounds__(NN_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     for (int kt = 0; kt < KT; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < KT) load_tiles(kt + 1);
-        auto frag = [&](const char* tile, int row, bool b_image) -> i32x8_nn {   // 32 k of one row: k = 32 q .. 32 q + 31
+        auto frag = [&](const char* tile, int row, bool b_image) -> i32x8_t {   // 32 k of one row: k = 32 q .. 32 q + 31
             const uint4 x0 = *reinterpret_cast<const uint4*>(tile + (b_image ? nn_off_b(row, 2 * q) : nn_off_a(row, 2 * q)));
             const uint4 x1 = *reinterpret_cast<const uint4*>(tile + (b_image ? nn_off_b(row, 2 * q + 1) : nn_off_a(row, 2 * q + 1)));
-            return i32x8_nn{(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, (int)x1.x, (int)x1.y, (int)x1.z, (int)x1.w};
+            return i32x8_t{(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, (int)x1.x, (int)x1.y, (int)x1.z, (int)x1.w};
         };
-        i32x8_nn fb[4];
+        i32x8_t fb[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) fb[j] = frag(Bs(buf), wn * 64 + j * 16 + (lane & 15), true);
         if constexpr (UNIT) {
-            i32x8_nn fa[4];
+            i32x8_t fa[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) fa[i] = frag(As(buf), wm * 64 + i * 16 + (lane & 15), false);
 #pragma unroll
@@ -160,13 +158,13 @@ __global__ __launch_bounds__(NN_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
         } else {
             // per row i of tiles: its A fragment, 4 zero-C MFMAs, then the fold of row i - 1 behind them.  Two rows of
             // products and one A fragment live at a time; all 16 products in flight would cost the second wave per SIMD.
-            f32x4_nn tp[4], tc[4];
+            f32x4_t tp[4], tc[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const i32x8_nn fa = frag(As(buf), wm * 64 + i * 16 + (lane & 15), false);
+                const i32x8_t fa = frag(As(buf), wm * 64 + i * 16 + (lane & 15), false);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    tc[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa, fb[j], f32x4_nn{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0);
+                    tc[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa, fb[j], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0);
                 if (i > 0) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc[i - 1][j] += tp[j] * s_cur;
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(NN_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const f32x4_nn v = acc[i][j];
+            const f32x4_t v = acc[i][j];
             const uint32_t w = pack_fp8x4(nn_satfinite(v[0]), nn_satfinite(v[1]), nn_satfinite(v[2]), nn_satfinite(v[3]));
             const int col = wn * 64 + j * 16 + (lane & 15);
 #pragma unroll

@@ -4,16 +4,15 @@
 //   pgk_w8a16_gemm_kn : bf16 A, fp8-e4m3 B[K,N] with 128x128 block scales (reference K4 layout)
 //   (internal) nt with fp8 W[N,K] + block scales, used by the engine's fp8 prefill
 //
-// Structure (v1): BM x BN x 64 block tile, 256 threads = 2x2 waves, v_mfma_f32_16x16x32_{bf16,f16},
-// fp32 accumulate; A/B tiles staged global -> VGPR -> LDS (16-byte chunks, XOR-swizzled so the
-// ds_read_b128 fragment reads are bank-conflict free), two LDS buffers: the global loads of tile t+1
-// are issued before the MFMAs of tile t and written to LDS after them (one barrier per K tile).
+// Structure (v1): BM x BN x 64 block tile, 256 threads = 2x2 waves, register-staged into two swizzled LDS
+// buffers - the tile types and the loop are gemm_tile_core.hip.h (shared with the grouped expert GEMM);
+// this file has the kernel's operand modes, its epilogues and the dispatchers.
 // The reference reaches for CUTLASS / cuBLASLt here (native/ops/matmul/matmul.cu:43-354); neither
 // exists on this target and nothing is linked in their place.
 
 #include "gemm_epilogues.hip.h"
 #include "gemm_plan.h"
-#include "gemv_core.hip.h"
+#include "gemm_tile_core.hip.h"
 #include "pgk_internal.h"
 
 #include <string>
@@ -42,162 +41,7 @@ bool want_gemm256(int M, int N) {
     return (long long)ceil_div(M, 256) * ceil_div(N, 256) >= 192;
 }
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-template <class T> __device__ __forceinline__ f32x4_t mfma16(const uint4& a, const uint4& b, f32x4_t c);
-template <> __device__ __forceinline__ f32x4_t mfma16<bf16>(const uint4& a, const uint4& b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ f32x4_t mfma16<f16>(const uint4& a, const uint4& b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-
-constexpr int GEMM_BK = 64;       // K elements per tile (128 bytes per LDS row)
-constexpr int GEMM_THREADS = 256;
-
-// byte offset of 16-byte chunk `kc` (0..7) of row `row` in a [rows][64 x 16-bit] swizzled LDS tile
-__device__ __forceinline__ int lds_off(int row, int kc) { return row * 128 + ((kc ^ (row & 7)) << 4); }
-
 enum BMode { B_NT = 0, B_NN = 1, B_NT_FP8 = 2, B_KN_FP8 = 3 };
-
-// ---- A-side (and NT B-side) tile: rows x 64 elements, k contiguous in memory -----------------
-template <int ROWS>
-struct TileRegsK {
-    static constexpr int CH = ROWS * 8 / GEMM_THREADS;  // 16-byte chunks per thread
-    uint4 v[CH > 0 ? CH : 1];
-    template <class T>
-    __device__ __forceinline__ void load(const T* base, int row0, int nrows, int k0, int K, int ld) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            const int r = c >> 3, kc = c & 7;
-            const int gr = row0 + r, gk = k0 + kc * 8;
-            if (gr < nrows && gk < K) v[i] = *reinterpret_cast<const uint4*>(base + (size_t)gr * ld + gk);
-            else v[i] = make_uint4(0, 0, 0, 0);
-        }
-    }
-    __device__ __forceinline__ void store(char* lds) const {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            *reinterpret_cast<uint4*>(lds + lds_off(c >> 3, c & 7)) = v[i];
-        }
-    }
-};
-
-// ---- NN B-side tile: B[K,N] row-major; tile is 64 k-rows x BN columns, transposed into LDS ----
-template <int BN>
-struct TileRegsN {
-    static constexpr int CH = 64 * (BN / 8) / GEMM_THREADS;
-    uint4 v[CH];
-    template <class T>
-    __device__ __forceinline__ void load(const T* base, int n0, int N, int k0, int K) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            const int k = c / (BN / 8), nc = c % (BN / 8);
-            const int gk = k0 + k, gn = n0 + nc * 8;
-            if (gk < K && gn < N) v[i] = *reinterpret_cast<const uint4*>(base + (size_t)gk * N + gn);  // N % 8 == 0
-            else v[i] = make_uint4(0, 0, 0, 0);
-        }
-    }
-    __device__ __forceinline__ void store(char* lds) const {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            const int k = c / (BN / 8), nc = c % (BN / 8);
-            const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int n = nc * 8 + j;
-                const uint16_t e = (uint16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
-                *reinterpret_cast<uint16_t*>(lds + lds_off(n, k >> 3) + (k & 7) * 2) = e;
-            }
-        }
-    }
-};
-
-// ---- fp8 B tiles, dequantised to bf16 on the way into LDS -----------------------------------
-// NT: W[N,K] u8, scale[N/128, K/128] bf16.  One 16-byte load = 16 k-values of one row.
-template <int BN>
-struct TileRegsFp8NT {
-    static constexpr int CH = (BN * 4 + GEMM_THREADS - 1) / GEMM_THREADS;  // 4 x 16-code chunks per row
-    uint4 v[CH];
-    float sc[CH];
-    __device__ __forceinline__ void load(const uint8_t* w, const bf16* scale, int n0, int N, int k0, int K) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            const int r = c >> 2, q = c & 3;
-            const int gn = n0 + r, gk = k0 + q * 16;
-            if (c < BN * 4 && gn < N && gk < K) {
-                v[i] = *reinterpret_cast<const uint4*>(w + (size_t)gn * K + gk);
-                sc[i] = to_f(scale[(size_t)(gn >> 7) * (K >> 7) + (gk >> 7)]);
-            } else {
-                v[i] = make_uint4(0, 0, 0, 0);
-                sc[i] = 0.f;
-            }
-        }
-    }
-    __device__ __forceinline__ void store(char* lds) const {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            if (c >= BN * 4) continue;
-            const int r = c >> 2, q = c & 3;
-            float f[16];
-            WTraits<fp8e4m3>::decode(v[i], f);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint4 o = make_uint4(pack_bf16x2(f[8 * h] * sc[i], f[8 * h + 1] * sc[i]),
-                                           pack_bf16x2(f[8 * h + 2] * sc[i], f[8 * h + 3] * sc[i]),
-                                           pack_bf16x2(f[8 * h + 4] * sc[i], f[8 * h + 5] * sc[i]),
-                                           pack_bf16x2(f[8 * h + 6] * sc[i], f[8 * h + 7] * sc[i]));
-                *reinterpret_cast<uint4*>(lds + lds_off(r, q * 2 + h)) = o;
-            }
-        }
-    }
-};
-// KN: B[K,N] u8, scale[K/128, N/128].  One 16-byte load = 16 n-values of one k.
-template <int BN>
-struct TileRegsFp8KN {
-    static constexpr int PER_ROW = BN / 16;
-    static constexpr int CH = (64 * PER_ROW + GEMM_THREADS - 1) / GEMM_THREADS;
-    uint4 v[CH];
-    float sc[CH];
-    __device__ __forceinline__ void load(const uint8_t* b, const bf16* scale, int n0, int N, int k0, int K) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            const int k = c / PER_ROW, nc = c % PER_ROW;
-            const int gk = k0 + k, gn = n0 + nc * 16;
-            if (c < 64 * PER_ROW && gk < K && gn < N) {
-                v[i] = *reinterpret_cast<const uint4*>(b + (size_t)gk * N + gn);  // N % 16 == 0
-                sc[i] = to_f(scale[(size_t)(gk >> 7) * (N >> 7) + (gn >> 7)]);
-            } else {
-                v[i] = make_uint4(0, 0, 0, 0);
-                sc[i] = 0.f;
-            }
-        }
-    }
-    __device__ __forceinline__ void store(char* lds) const {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = threadIdx.x + i * GEMM_THREADS;
-            if (c >= 64 * PER_ROW) continue;
-            const int k = c / PER_ROW, nc = c % PER_ROW;
-            float f[16];
-            WTraits<fp8e4m3>::decode(v[i], f);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int n = nc * 16 + j;
-                *reinterpret_cast<uint16_t*>(lds + lds_off(n, k >> 3) + (k & 7) * 2) = f_to_bf16_bits(f[j] * sc[i]);
-            }
-        }
-    }
-};
 
 template <class T, int BM, int BN, int MODE, int EPI>
 // kps > 0 (B_NT only, EPI 2): split-K - workgroup z multiplies k in [z * kps, (z + 1) * kps) and stores its fp32 partial tile into
@@ -205,10 +49,7 @@ template <class T, int BM, int BN, int MODE, int EPI>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_mfma_kernel(const T* A, const void* Bv, const bf16* bscale,
                                                                 const T* bias, void* Cv, int M, int N, int K, int kps) {
     constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 16, TN = WN / 16;
-    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    auto As = [&](int buf) -> char* { return smem + buf * A_BYTES; };
-    auto Bs = [&](int buf) -> char* { return smem + 2 * A_BYTES + buf * B_BYTES; };
 
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int wm = wid >> 1, wn = wid & 1;
@@ -229,11 +70,13 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_mfma_kernel(const T* A, con
         else rb_f8kn.load((const uint8_t*)Bv, bscale, n0, N, k0, K);
     };
     auto store_tiles = [&](int buf) {
-        ra.store(As(buf));
-        if constexpr (MODE == B_NT) rb_nt.store(Bs(buf));
-        else if constexpr (MODE == B_NN) rb_nn.store(Bs(buf));
-        else if constexpr (MODE == B_NT_FP8) rb_f8nt.store(Bs(buf));
-        else rb_f8kn.store(Bs(buf));
+        char* as = gemm_tile_a<BM, BN>(smem, buf);
+        char* bs = gemm_tile_b<BM, BN>(smem, buf);
+        ra.store(as);
+        if constexpr (MODE == B_NT) rb_nt.store(bs);
+        else if constexpr (MODE == B_NN) rb_nn.store(bs);
+        else if constexpr (MODE == B_NT_FP8) rb_f8nt.store(bs);
+        else rb_f8kn.store(bs);
     };
 
     f32x4_t acc[TM][TN];
@@ -241,32 +84,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_mfma_kernel(const T* A, con
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = (kend - kbeg + GEMM_BK - 1) / GEMM_BK;
-    load_tiles(kbeg);
-    store_tiles(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) load_tiles(kbeg + (kt + 1) * GEMM_BK);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            uint4 fa[TM], fb[TN];
-            const int kc = ks * 4 + (lane >> 4);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                fa[i] = *reinterpret_cast<const uint4*>(As(buf) + lds_off(wm * WM + i * 16 + (lane & 15), kc));
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                fb[j] = *reinterpret_cast<const uint4*>(Bs(buf) + lds_off(wn * WN + j * 16 + (lane & 15), kc));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = mfma16<T>(fa[i], fb[j], acc[i][j]);
-        }
-        if (kt + 1 < nk) store_tiles(buf ^ 1);
-        __syncthreads();
-    }
+#include "gemm_tile_loop.hip.h"      // the main loop: acc += A . B^T over [kbeg, kend)
 
     // C/D map of v_mfma_f32_16x16x32: col = lane & 15, row = (lane >> 4) * 4 + reg
 #pragma unroll
@@ -334,18 +152,10 @@ __global__ __launch_bounds__(256) void gemm_simple_kernel(const T* A, const T* B
 template <class T, int BM, int BN, int MODE, int EPI>
 static pgk_status launch_mfma(const T* A, const void* B, const bf16* bscale, const T* bias, void* C, int M, int N, int K,
                               hipStream_t st, int splits = 1) {
-    constexpr size_t LDS = 2 * (size_t)(BM + BN) * 128;
-    static bool attr_done = false;
-    if (LDS > 48 * 1024 && !attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_kernel<T, BM, BN, MODE, EPI>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
+    constexpr size_t LDS = gemm_tile_lds_bytes(BM, BN);
     dim3 grid(ceil_div(N, BN), ceil_div(M, BM), splits);
     const int kps = splits > 1 ? ceil_div(ceil_div(K, splits), GEMM_BK) * GEMM_BK : 0;
-    gemm_mfma_kernel<T, BM, BN, MODE, EPI><<<grid, GEMM_THREADS, LDS, st>>>(A, B, bscale, bias, C, M, N, K, kps);
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
+    return launch_dyn_lds<&gemm_mfma_kernel<T, BM, BN, MODE, EPI>>(grid, GEMM_THREADS, LDS, LDS > 48 * 1024, st, A, B, bscale, bias, C, M, N, K, kps);
 }
 
 // Tile choice: mfma_pick_tile (gemm_plan.h).
@@ -370,16 +180,9 @@ __global__ __launch_bounds__(256) void dequant_fp8_blocks_kernel(const uint8_t* 
         const int n = (int)(t / cpr), c = (int)(t % cpr);
         const uint4 raw = *reinterpret_cast<const uint4*>(w8 + (size_t)n * K + (size_t)c * 16);
         const float sc = to_f(sw[(size_t)(n >> 7) * KB + (c >> 3)]);
-        float f[16];
-        WTraits<fp8e4m3>::decode(raw, f);
-        uint4 lo, hi;
-        lo.x = pack_bf16x2(f[0] * sc, f[1] * sc); lo.y = pack_bf16x2(f[2] * sc, f[3] * sc);
-        lo.z = pack_bf16x2(f[4] * sc, f[5] * sc); lo.w = pack_bf16x2(f[6] * sc, f[7] * sc);
-        hi.x = pack_bf16x2(f[8] * sc, f[9] * sc); hi.y = pack_bf16x2(f[10] * sc, f[11] * sc);
-        hi.z = pack_bf16x2(f[12] * sc, f[13] * sc); hi.w = pack_bf16x2(f[14] * sc, f[15] * sc);
         uint4* o = reinterpret_cast<uint4*>(out + (size_t)n * K + (size_t)c * 16);
-        o[0] = lo;
-        o[1] = hi;
+        o[0] = fp8x8_to_bf16x8(make_uint2(raw.x, raw.y), sc);
+        o[1] = fp8x8_to_bf16x8(make_uint2(raw.z, raw.w), sc);
     }
 }
 

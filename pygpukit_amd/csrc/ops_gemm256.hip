@@ -19,19 +19,13 @@
 #include "gemm_epilogues.hip.h"
 #include "gemm_plan.h"
 #include "gemv_core.hip.h"
+#include "mfma_common.hip.h"
 #include "pgk_internal.h"
 
 namespace pgk {
 
-typedef __bf16 bf16x8_g __attribute__((ext_vector_type(8)));
-typedef float f32x4_g __attribute__((ext_vector_type(4)));
-typedef int i32x8_g __attribute__((ext_vector_type(8)));
-
 constexpr int G2_BM = 256, G2_BN = 256, G2_THREADS = 512;
 constexpr int G2_TILE = 256 * 128;   // bytes of one operand tile
-
-// byte offset of 16-byte chunk c (0..7) of row r in a [rows][128 B] tile
-__device__ __forceinline__ int g2_off(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
 // fp8 image swizzle (see gemm256_fp8_kernel): (r & 7) ^ (5 for rows 8-15 of every 16)
 __device__ __forceinline__ int g2_sw8(int r) { return (r & 7) ^ ((r & 8) ? 5 : 0); }
@@ -75,7 +69,7 @@ __device__ __forceinline__ void g2_tile_of(int id, int nwg, int ntm, int ntn, in
 // lanes, quantize_fp8_rows' contract): exactly the fp8 x fp8 down projection's A operand.  Saves the [M][2 I] bf16 round
 // trip through HBM (Llama-3-8B shape, S = 4096: 235 MB written + read back = ~75 us of a 1.4 ms layer) and a launch.
 template <bool QOUT, int TN = 4>   // TN = n-fragments per wave column: 4 = 128 act columns per tile; 3 = 96 (bf16 output only)
-__device__ __forceinline__ void g2_swiglu_epilogue(char* smem, const f32x4_g (&acc)[8][TN], int tid, int m0, int tn, int M, int I,
+__device__ __forceinline__ void g2_swiglu_epilogue(char* smem, const f32x4_t (&acc)[8][TN], int tid, int m0, int tn, int M, int I,
                                                    void* outv, float* out_scales) {
     static_assert(TN == 4 || !QOUT, "the e4m3 epilogue needs whole 128-column scale blocks");
     constexpr int WN = TN * 16, ACT = 2 * WN, ROWB = 4 * WN * 2, CH = ACT / 8;       // act columns per tile, bytes per LDS row, 8-column chunks per row
@@ -130,7 +124,7 @@ __device__ __forceinline__ void g2_swiglu_epilogue(char* smem, const f32x4_g (&a
 // it exposed: a one-wave grid has no second tile to hide an epilogue behind.  Here, per 64-column quarter of the tile: the
 // residual words are requested first (8 float4 per lane), the owning wave column puts its accumulators into LDS ([256][64]
 // fp32 over the operand stages, lane quarters XOR-ed apart), and every lane adds and stores 8 float4 (256-byte row segments).
-__device__ __forceinline__ void g2_accum_epilogue(char* smem, const f32x4_g (&acc)[8][4], int tid, int m0, int n0, int M, int N, float* C) {
+__device__ __forceinline__ void g2_accum_epilogue(char* smem, const f32x4_t (&acc)[8][4], int tid, int m0, int n0, int M, int N, float* C) {
     const int lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3, q = lane >> 4, l15 = lane & 15;
     // one pass per 64-column quarter (= one wave column): 8 float4 per lane in flight (16 - halves - spilled in these kernels)
 #pragma unroll 1
@@ -169,7 +163,7 @@ __device__ __forceinline__ void g2_accum_epilogue(char* smem, const f32x4_g (&ac
 // ---- QKV-heads epilogue (EPI 3): the accumulators go to LDS as the bf16 tile the plain kernel would have stored (the layout of
 // g2_swiglu_epilogue), a tile = 256 token rows x two head slots, 16 consecutive lanes take one (row, head) and finish it
 // (qkv_head_finish: per-head RMSNorm, RoPE, q -> qkv buffer, k / v -> cache): bit-identical to GEMM + qknorm_rope_kvwrite_kernel.
-__device__ __forceinline__ void g2_qkv_heads_epilogue(char* smem, const f32x4_g (&acc)[8][4], int tid, int m0, int tn, int M, int N, bf16* qkv,
+__device__ __forceinline__ void g2_qkv_heads_epilogue(char* smem, const f32x4_t (&acc)[8][4], int tid, int m0, int tn, int M, int N, bf16* qkv,
                                                       const QkvHeadArgs& hd) {
     const int lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3, q = lane >> 4, l15 = lane & 15;
     __builtin_amdgcn_s_barrier();
@@ -225,11 +219,11 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256_bf16_kernel(const bf16* A,
         }
     };
 
-    f32x4_g acc[8][4];
+    f32x4_t acc[8][4];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     // fragment read offsets: row = base + l15 (base a multiple of 16), chunk = ks*4 + q
     const int f_off0 = l15 * 128 + (((0 + q) ^ (l15 & 7)) << 4);
@@ -264,15 +258,15 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256_bf16_kernel(const bf16* A,
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_g, fa0[i]),
-                                                                    __builtin_bit_cast(bf16x8_g, fb0[j]), acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fa0[i]),
+                                                                    __builtin_bit_cast(bf16x8_t, fb0[j]), acc[i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_g, fa1[i]),
-                                                                    __builtin_bit_cast(bf16x8_g, fb1[j]), acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fa1[i]),
+                                                                    __builtin_bit_cast(bf16x8_t, fb1[j]), acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -378,11 +372,11 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256s_bf16_kernel(const bf16* A
         else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     };
 
-    f32x4_g acc[8][TN];
+    f32x4_t acc[8][TN];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const int f_off = l15 * 64 + ((q ^ ((l15 >> 2) & 2)) << 4);
     const int a_base = wr * 128 * 64, w_base = HALF + wc * WN * 64;
     uint4 fa[8], fb[TN];
@@ -409,8 +403,8 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256s_bf16_kernel(const bf16* A
         __builtin_amdgcn_s_setprio(1);                                                                       \
         _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                        \
             _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                   \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_g, fa[i]),     \
-                                                                    __builtin_bit_cast(bf16x8_g, fb[j]), acc[i][j], 0, 0, 0); \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fa[i]),     \
+                                                                    __builtin_bit_cast(bf16x8_t, fb[j]), acc[i][j], 0, 0, 0); \
         __builtin_amdgcn_s_setprio(0);                                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         if (!late) wait_two_younger();                                                                       \
@@ -509,11 +503,11 @@ __global__ __launch_bounds__(G1_THREADS, 2) void gemm128s_bf16_kernel(const bf16
         g2_dma16(w_src1 + kw, a_dst + G1_HALF + 1024);
     };
 
-    f32x4_g acc[4][4];
+    f32x4_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const int f_off = l15 * 64 + ((q ^ ((l15 >> 2) & 2)) << 4);
     const int a_base = wr * 64 * 64, w_base = G1_HALF + wc * 64 * 64;
     uint4 fa[4], fb[4];
@@ -538,8 +532,8 @@ __global__ __launch_bounds__(G1_THREADS, 2) void gemm128s_bf16_kernel(const bf16
         __builtin_amdgcn_s_setprio(1);                                                                        \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                         \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                     \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_g, fa[i]),      \
-                                                                    __builtin_bit_cast(bf16x8_g, fb[j]), acc[i][j], 0, 0, 0); \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fa[i]),      \
+                                                                    __builtin_bit_cast(bf16x8_t, fb[j]), acc[i][j], 0, 0, 0); \
         __builtin_amdgcn_s_setprio(0);                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
     }
@@ -730,11 +724,11 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256_fp8_kernel(const uint8_t* 
         else if (wid == 4) g2_dma2_so(sw_tile + kt, ((uint32_t)lane & 1u) * sw_step, s_dst);
     };
 
-    f32x4_g acc[8][4];
+    f32x4_t acc[8][4];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     // fragment reads: row = base + l15, the lane's 32 bytes are chunks 2q and 2q+1
     const int f_lo = l15 * 128 + (((2 * q) ^ g2_sw8(l15)) << 4);
@@ -760,14 +754,14 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256_fp8_kernel(const uint8_t* 
     stage(min(1, KB - 1), 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    i32x8_g fb[4], fa[2][2];
-    f32x4_g t[3];
-    f32x4_g sc[2][2];        // [slot][row-tile of the group]: raw row scales as they come from LDS, multiplied by the block scale in place
+    i32x8_t fb[4], fa[2][2];
+    f32x4_t t[3];
+    f32x4_t sc[2][2];        // [slot][row-tile of the group]: raw row scales as they come from LDS, multiplied by the block scale in place
     float swv;
     uint32_t off_e = 0, off_o = 0;
-    auto ldfrag = [&](const char* base) -> i32x8_g {
+    auto ldfrag = [&](const char* base) -> i32x8_t {
         const uint4 lo = *reinterpret_cast<const uint4*>(base + f_lo), hi = *reinterpret_cast<const uint4*>(base + f_hi);
-        return i32x8_g{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+        return i32x8_t{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
     };
     auto load_frags = [&](int buf, int g, int slot) {
         const char* As = g2_smem + buf * G2_TILE + a_base;
@@ -779,7 +773,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256_fp8_kernel(const uint8_t* 
     auto load_scales = [&](int buf, int g, int slot) {
         const char* Ss = g2_smem + 4 * G2_TILE + buf * G2_SCALE_BYTES;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) sc[slot][u] = *reinterpret_cast<const f32x4_g*>(Ss + (wr * 128 + (2 * g + u) * 16 + q * 4) * 4);
+        for (int u = 0; u < 2; ++u) sc[slot][u] = *reinterpret_cast<const f32x4_t*>(Ss + (wr * 128 + (2 * g + u) * 16 + q * 4) * 4);
     };
     // (a sub-dword LDS-DMA still strides the lanes by 4 bytes: lane l's 16 bits land at +4l, zero-extended)
     auto load_swv = [&](int buf) -> float { return to_f(*reinterpret_cast<const bf16*>(g2_smem + 4 * G2_TILE + buf * G2_SCALE_BYTES + 1024 + (wc >> 1) * 4)); };
@@ -821,7 +815,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm256_fp8_kernel(const uint8_t* 
             else load_scales(buf ^ 1, 0, 0);                                                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                      \
         }                                                                                                           \
-        t[(N) % 3] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[g_ & 1][u_], fb[j_], f32x4_g{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0); \
+        t[(N) % 3] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[g_ & 1][u_], fb[j_], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0); \
         asm volatile("" : "+v"(t[(N) % 3]));          /* pins this MFMA here */                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                          \
         if constexpr ((N) >= 24) {                    /* one DMA piece of tile kt + 2 behind each MFMA of the last group (past the end: re-reads the last tile into a stage nobody reads any more) */ \
@@ -883,17 +877,9 @@ pgk_status gemm256_fp8_nt(const uint8_t* a, const float* sa, const uint8_t* w, c
                           int K, hipStream_t st) {
     PGK_REQUIRE(K % 128 == 0 && K >= 128 && M % G2_BM == 0 && N % G2_BN == 0, "gemm256 fp8: M=%d N=%d must be multiples of 256 and K=%d of 128", M, N, K);
     constexpr size_t LDS = 4 * (size_t)G2_TILE + 2 * G2_SCALE_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_fp8_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_fp8_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
     const int ntm = ceil_div(M, G2_BM), ntn = ceil_div(N, G2_BN);
-    if (accum_f32) gemm256_fp8_kernel<1><<<ntm * ntn, G2_THREADS, LDS, st>>>(a, sa, w, sw, c, nullptr, M, N, K, ntm, ntn, QkvHeadArgs{});
-    else gemm256_fp8_kernel<0><<<ntm * ntn, G2_THREADS, LDS, st>>>(a, sa, w, sw, c, nullptr, M, N, K, ntm, ntn, QkvHeadArgs{});
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
+    if (accum_f32) return launch_dyn_lds<&gemm256_fp8_kernel<1>>(ntm * ntn, G2_THREADS, LDS, true, st, a, sa, w, sw, c, nullptr, M, N, K, ntm, ntn, QkvHeadArgs{});
+    else return launch_dyn_lds<&gemm256_fp8_kernel<0>>(ntm * ntn, G2_THREADS, LDS, true, st, a, sa, w, sw, c, nullptr, M, N, K, ntm, ntn, QkvHeadArgs{});
 }
 
 // QKV projection finished per head in the epilogue (QkvHeadArgs): N = (Hq + 2 Hkv) x 128, two head slots per tile
@@ -902,15 +888,8 @@ pgk_status gemm256_fp8_qkv_heads_nt(const uint8_t* a, const float* sa, const uin
     PGK_REQUIRE(K % 128 == 0 && K >= 128 && M % G2_BM == 0 && N % G2_BN == 0 && N == (hd.hq + 2 * hd.hkv) * 128,
                 "gemm256 fp8 qkv heads: M=%d, N=%d must be multiples of 256, K=%d of 128, N = (Hq + 2 Hkv) x 128", M, N, K);
     constexpr size_t LDS = 4 * (size_t)G2_TILE + 2 * G2_SCALE_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_fp8_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
     const int ntm = M / G2_BM, ntn = N / G2_BN;
-    gemm256_fp8_kernel<3><<<ntm * ntn, G2_THREADS, LDS, st>>>(a, sa, w, sw, qkv, nullptr, M, N, K, ntm, ntn, hd);
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
+    return launch_dyn_lds<&gemm256_fp8_kernel<3>>(ntm * ntn, G2_THREADS, LDS, true, st, a, sa, w, sw, qkv, nullptr, M, N, K, ntm, ntn, hd);
 }
 
 // act codes / scales = quantise(silu(a . Wg^T) * (a . Wu^T)), w = fused [2 I, K] gate / up codes with [2 I / 128][K / 128] block scales
@@ -919,15 +898,8 @@ pgk_status gemm256_fp8_swiglu_nt(const uint8_t* a, const float* sa, const uint8_
     PGK_REQUIRE(K % 128 == 0 && K >= 128 && M % G2_BM == 0 && I % 128 == 0, "gemm256 fp8 swiglu: M=%d must be a multiple of 256, I=%d and K=%d of 128", M, I, K);
     PGK_REQUIRE((const void*)a != (const void*)q_out, "gemm256 fp8 swiglu: output aliases the activation operand");
     constexpr size_t LDS = 4 * (size_t)G2_TILE + 2 * G2_SCALE_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_fp8_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
     const int ntm = M / G2_BM, ntn = I / 128;
-    gemm256_fp8_kernel<2><<<ntm * ntn, G2_THREADS, LDS, st>>>(a, sa, w, sw, q_out, s_out, M, I, K, ntm, ntn, QkvHeadArgs{});
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
+    return launch_dyn_lds<&gemm256_fp8_kernel<2>>(ntm * ntn, G2_THREADS, LDS, true, st, a, sa, w, sw, q_out, s_out, M, I, K, ntm, ntn, QkvHeadArgs{});
 }
 
 // bf16 NT on the 256^2 structure; caller guarantees K % 64 == 0 and 16-byte aligned rows
@@ -936,61 +908,31 @@ pgk_status gemm256_bf16_nt(const bf16* A, const bf16* W, const bf16* bias, void*
     PGK_REQUIRE(K % 64 == 0 && K >= 64, "gemm256: K=%d must be a multiple of 64", K);
     PGK_REQUIRE(!packed || N % 16 == 0, "gemm256: the fragment-major weight copy has whole 16-row tiles (N=%d)", N);
     constexpr size_t LDS = 4 * (size_t)G2_TILE;
-    static bool attr_done = false;
-    if (!attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_bf16_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_bf16_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
     const int ntm = ceil_div(M, G2_BM), ntn = ceil_div(N, G2_BN);
     static_assert(G2_BM == 256 && G2_BN == 256, "gemm256_pick counts 256 x 256 tiles");
     const Gemm256Kernel kern = gemm256_pick(M, N, accum_f32, packed);      // gemm_plan.h (reads PGK_GEMM256S)
     if (kern != G256_LOCKSTEP) {
-        static bool attr_s = false;
-        if (!attr_s) {
-            PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-            PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-            attr_s = true;
-        }
         const int ntn3 = N / 192;
         if (kern == G256_STAGGERED_N192) {      // 192-column tiles
-            static bool attr_n = false;
-            if (!attr_n) {
-                PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-                attr_n = true;
-            }
-            gemm256s_bf16_kernel<0, 3><<<ntm * ntn3, G2_THREADS, LDS, st>>>(A, W, bias, C, M, N, K, ntm, ntn3, packed ? 1 : 0);
-        } else if (accum_f32) gemm256s_bf16_kernel<1><<<ntm * ntn, G2_THREADS, LDS, st>>>(A, W, nullptr, C, M, N, K, ntm, ntn, packed ? 1 : 0);
-        else gemm256s_bf16_kernel<0><<<ntm * ntn, G2_THREADS, LDS, st>>>(A, W, bias, C, M, N, K, ntm, ntn, packed ? 1 : 0);
-        PGK_CHECK_HIP(hipGetLastError());
-        return PGK_OK;
+            return launch_dyn_lds<&gemm256s_bf16_kernel<0, 3>>(ntm * ntn3, G2_THREADS, LDS, true, st, A, W, bias, C, M, N, K, ntm, ntn3, packed ? 1 : 0);
+        } else if (accum_f32) return launch_dyn_lds<&gemm256s_bf16_kernel<1>>(ntm * ntn, G2_THREADS, LDS, true, st, A, W, nullptr, C, M, N, K, ntm, ntn, packed ? 1 : 0);
+        else return launch_dyn_lds<&gemm256s_bf16_kernel<0>>(ntm * ntn, G2_THREADS, LDS, true, st, A, W, bias, C, M, N, K, ntm, ntn, packed ? 1 : 0);
     }
-    if (accum_f32) gemm256_bf16_kernel<1><<<ntm * ntn, G2_THREADS, LDS, st>>>(A, W, nullptr, C, M, N, K, ntm, ntn);
-    else gemm256_bf16_kernel<0><<<ntm * ntn, G2_THREADS, LDS, st>>>(A, W, bias, C, M, N, K, ntm, ntn);
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
+    if (accum_f32) return launch_dyn_lds<&gemm256_bf16_kernel<1>>(ntm * ntn, G2_THREADS, LDS, true, st, A, W, nullptr, C, M, N, K, ntm, ntn);
+    else return launch_dyn_lds<&gemm256_bf16_kernel<0>>(ntm * ntn, G2_THREADS, LDS, true, st, A, W, bias, C, M, N, K, ntm, ntn);
 }
 
 // act[M][I] = bf16(silu(A . Wg^T) * (A . Wu^T)), W = fused [2 I, K] gate / up weight (staggered kernel, SwiGLU epilogue)
 pgk_status gemm256_bf16_swiglu_nt(const bf16* A, const bf16* W, bf16* act, int M, int I, int K, hipStream_t st, bool packed) {
     PGK_REQUIRE(K % 64 == 0 && K >= 64 && I % 128 == 0, "gemm256 swiglu: K=%d must be a multiple of 64 and I=%d of 128", K, I);
     constexpr size_t LDS = 4 * (size_t)G2_TILE;
-    static bool attr_done = false;
-    if (!attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_bf16_kernel<2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
     const int ntm = ceil_div(M, G2_BM), ntn = I / 128;
-    // 96 act columns per tile (192-column B tiles) when that fills the rounds of the chip better: Qwen3-0.6B at S = 2048 is
-    // 8 x 24 = 192 tiles of 128 (three quarters of the CUs, one round) or 8 x 32 = 256 tiles of 96 (all of them)
-    if (I % 96 == 0 && 0.75 * ceil_div(ntm * (I / 96), 256) < (double)ceil_div(ntm * ntn, 256) - 0.01) {
-        gemm256s_bf16_kernel<2, 3><<<ntm * (I / 96), G2_THREADS, LDS, st>>>(A, W, nullptr, act, M, I, K, ntm, I / 96, packed ? 1 : 0);
+    static_assert(G2_BM == 256, "gemm256_swiglu_narrow counts 256-row tiles");
+    if (gemm256_swiglu_narrow(M, I)) {      // gemm_plan.h: 96 act columns per tile (192-column B tiles)
+        return launch_dyn_lds<&gemm256s_bf16_kernel<2, 3>>(ntm * (I / 96), G2_THREADS, LDS, true, st, A, W, nullptr, act, M, I, K, ntm, I / 96, packed ? 1 : 0);
     } else {
-        gemm256s_bf16_kernel<2><<<ntm * ntn, G2_THREADS, LDS, st>>>(A, W, nullptr, act, M, I, K, ntm, ntn, packed ? 1 : 0);
+        return launch_dyn_lds<&gemm256s_bf16_kernel<2>>(ntm * ntn, G2_THREADS, LDS, true, st, A, W, nullptr, act, M, I, K, ntm, ntn, packed ? 1 : 0);
     }
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
 }
 
 // 128 x 128 tiles; mode 0: bf16 C (+bias), 1: fp32 C +=, 2: fp32 slabs [splits][M][N] (K split into `splits` runs of whole 64-k steps)
@@ -1004,26 +946,15 @@ pgk_status gemm128s_bf16_nt(const bf16* A, const bf16* W, const bf16* bias, void
     PGK_REQUIRE(mode != 3 || (heads && N == (heads->hq + 2 * heads->hkv) * 128), "gemm128s: the QKV-heads epilogue needs N=%d = (Hq + 2 Hkv) x 128", N);
     const QkvHeadArgs hd = heads ? *heads : QkvHeadArgs{};
     constexpr size_t LDS = 8 * (size_t)G1_HALF;
-    static bool attr_done = false;
-    if (!attr_done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm128s_bf16_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm128s_bf16_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm128s_bf16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm128s_bf16_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm128s_bf16_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
     const int ntm = ceil_div(M, 128), ntn = mode == 4 ? N / 64 : ceil_div(N, 128);      // SwiGLU: N = I act columns, 64 per tile
     const int kps = ceil_div(ceil_div(K, splits), 64) * 64;
     const dim3 grid(ntm * ntn, ceil_div(K, kps));
     PGK_REQUIRE((int)grid.y == splits, "gemm128s: K=%d does not split into %d runs of whole 64-k steps", K, splits);
-    if (mode == 0) gemm128s_bf16_kernel<0><<<grid, G1_THREADS, LDS, st>>>(A, W, bias, C, M, N, K, ntm, ntn, kps, hd, pk);
-    else if (mode == 1) gemm128s_bf16_kernel<1><<<grid, G1_THREADS, LDS, st>>>(A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
-    else if (mode == 2) gemm128s_bf16_kernel<2><<<grid, G1_THREADS, LDS, st>>>(A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
-    else if (mode == 3) gemm128s_bf16_kernel<3><<<grid, G1_THREADS, LDS, st>>>(A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
-    else gemm128s_bf16_kernel<4><<<grid, G1_THREADS, LDS, st>>>(A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
-    PGK_CHECK_HIP(hipGetLastError());
-    return PGK_OK;
+    if (mode == 0) return launch_dyn_lds<&gemm128s_bf16_kernel<0>>(grid, G1_THREADS, LDS, true, st, A, W, bias, C, M, N, K, ntm, ntn, kps, hd, pk);
+    else if (mode == 1) return launch_dyn_lds<&gemm128s_bf16_kernel<1>>(grid, G1_THREADS, LDS, true, st, A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
+    else if (mode == 2) return launch_dyn_lds<&gemm128s_bf16_kernel<2>>(grid, G1_THREADS, LDS, true, st, A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
+    else if (mode == 3) return launch_dyn_lds<&gemm128s_bf16_kernel<3>>(grid, G1_THREADS, LDS, true, st, A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
+    else return launch_dyn_lds<&gemm128s_bf16_kernel<4>>(grid, G1_THREADS, LDS, true, st, A, W, nullptr, C, M, N, K, ntm, ntn, kps, hd, pk);
 }
 
 }  // namespace pgk

@@ -6,32 +6,26 @@
 //   pgk_moe_gather / _scatter   rows into sorted order / weighted sum back per token (fp32, slot order, one rounding)
 //   pgk_grouped_gemm_rows       C[r] = A[r] . W[e_r]^T for rows in any order (a plain fp32 kernel: not the hot path)
 //   pgk_grouped_gemm_sorted     the same on rows grouped by expert, driven by the tile table:
-//     few rows per expert (decode) - the ops_wsgemm.hip structure per (tile, 64-column slab, K split): the expert's rows sit
-//       in LDS, its weight streams from HBM straight into MFMA B fragments, once per tile; split K writes fp32 slabs that
-//       the consumer (pgk_moe_scatter) sums in order;
-//     many rows (prefill) - 128 x 128 x 64 MFMA tiles staged through registers into XOR-swizzled LDS (the ops_gemm.hip
-//       structure), each row tile inside one expert's segment and masked past its end.
+//     few rows per expert (decode) - wsgemm_core.hip.h's walk (the one pgk_gemm_nt's skinny kernel runs) per (tile,
+//       64-column slab, K split): the expert's rows sit in LDS, its weight streams from HBM straight into MFMA B
+//       fragments, once per tile; split K writes fp32 slabs that the consumer (pgk_moe_scatter) sums in order;
+//     many rows (prefill) - gemm_tile_core.hip.h's tile types and gemm_tile_loop.hip.h's 128 x 128 x 64 register-staged
+//       loop (the ones gemm_mfma_kernel runs), each row tile inside one expert's segment and zero past its end.
+//   Both kernels here add only the tile-table prologue, the a_map row gather and the r0-offset epilogue.
 // No kernel here reads a device value back to the host: every grid is sized from T, k, E, N and K; workgroups whose tile
 // table entry is empty exit at once.  No atomic decides an order, so two runs give identical bytes.
 
-#include "gemv_core.hip.h"
+#include "gemm_plan.h"
+#include "gemm_tile_core.hip.h"
 #include "pgk_internal.h"
-
-#include <algorithm>
+#include "wsgemm_core.hip.h"
 
 namespace pgk {
 
-typedef __bf16 bf16x8_m __attribute__((ext_vector_type(8)));
-typedef float f32x4_m __attribute__((ext_vector_type(4)));
-
 constexpr int MOE_MAX_E = 256;
 constexpr int MOE_MAX_K = 8;
-constexpr int MOE_TILE_ROWS = 128;      // rows per tile-table entry (both grouped-GEMM regimes)
 constexpr int MOE_PERM_CHUNK = 4096;    // (token, slot) entries per permutation workgroup: 4 waves x 1024
-constexpr int MOE_WS_KT = 256;          // K elements per LDS tile of the weight-streaming kernel
-constexpr int MOE_WS_ROWS_MAX = 64;     // T*k/E at or below this: weight-streaming regime
-
-int moe_max_tiles(int T, int k, int E) { return ceil_div((long long)T * k, MOE_TILE_ROWS) + E; }
+// MOE_TILE_ROWS (rows per tile-table entry) and the regime / split / row-tile choices: gemm_plan.h
 
 // softmax_topk_*_kernel (topk_kernels.cuh:192-260): max, exp(x - max) summed in order in fp32, times 1/sum
 __device__ __forceinline__ void moe_softmax_k(float (&x)[MOE_MAX_K], int k) {
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(256) void grouped_rows_kernel(const bf16* A, const 
             float fa[8];
             WTraits<bf16>::decode(av, fa);
             float fw[8];
-            if constexpr (FP8) {
+            if constexpr (FP8) {      // not fp8x8_to_bf16x8: the product stays fp32, it is never rounded to bf16
                 const uint8_t* w = reinterpret_cast<const uint8_t*>(W) + ((size_t)e * N + n) * K + k0;
                 const uint2 v = *reinterpret_cast<const uint2*>(w);
                 const float sc = to_f(ws[((size_t)e * (N >> 7) + (n >> 7)) * (K >> 7) + (k0 >> 7)]);
@@ -328,107 +322,39 @@ struct MoeGemmArgs {
 
 __device__ __forceinline__ int moe_src_row(const MoeGemmArgs& g, int r) { return g.a_map ? g.a_map[r] / g.k : r; }
 
-// byte offset of 16-byte chunk c (0..31) of row r in a [rows][256 x bf16] tile (ops_wsgemm.hip)
-__device__ __forceinline__ int mws_off(int r, int c) { return r * (MOE_WS_KT * 2) + (((c & ~15) | ((c ^ r) & 15)) << 4); }
+// Weight-streaming regime: wsgemm_walk on one tile-table entry.  grid (N/64, splits, max_tiles); 4 waves x 16 weight rows;
+// MT*16 >= the rows any tile can hold.
+struct MoeWsProblem {
+    const MoeGemmArgs& g;
+    int r0;                 // first sorted row of the tile
+    const void* w;          // the expert's weight and scales
+    const bf16* wscale;
+    int M, N, K, kbeg, kend;
+    __device__ __forceinline__ const bf16* a_row(int r) const { return g.a + (size_t)moe_src_row(g, r0 + min(r, M - 1)) * K; }
+};
 
-// Weight-streaming regime.  grid (N/64, splits, max_tiles); 4 waves x 16 weight rows; MT*16 >= the rows any tile can hold.
 template <int MT, bool FP8, bool SLAB>
-__global__ __launch_bounds__(256) void moe_ws_kernel(MoeGemmArgs g) {
+__global__ __launch_bounds__(WS_THREADS) void moe_ws_kernel(MoeGemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char a_lds[];
     const int e = load_uniform_i32(g.tiles + 2 * blockIdx.z);
     if (e < 0) return;
     const int r0 = load_uniform_i32(g.tiles + 2 * blockIdx.z + 1);
     const int M = min(min(load_uniform_i32(g.offsets + e + 1) - r0, MOE_TILE_ROWS), MT * 16);
-    const int mt_on = (M + 15) >> 4;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int n0 = (blockIdx.x * 4 + wid) * 16;
-    const int K = g.K;
     const int kbeg = blockIdx.y * g.k_per_split;
-    const int kend = min(kbeg + g.k_per_split, K);
-    const int nrow = min(n0 + (lane & 15), g.N - 1);
-    const int kl = 8 * (lane >> 4);
-    const char* wbase = reinterpret_cast<const char*>(g.w) + (size_t)e * g.N * K * (FP8 ? 1 : 2);
-    const bf16* sbase = FP8 ? g.wscale + (size_t)e * (g.N >> 7) * (K >> 7) : nullptr;
+    const MoeWsProblem p{g, r0, reinterpret_cast<const char*>(g.w) + (size_t)e * g.N * g.K * (FP8 ? 1 : 2),
+                         FP8 ? g.wscale + (size_t)e * (g.N >> 7) * (g.K >> 7) : nullptr,
+                         M, g.N, g.K, kbeg, min(kbeg + g.k_per_split, g.K)};
 
-    f32x4_m acc[MT];
+    f32x4_t acc[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) acc[i] = f32x4_m{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < MT; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // row tiles past M are neither read nor multiplied; each A fragment is read right before its MFMA, not one k-step ahead:
+    // reading ahead takes MT*8 more registers, which in this kernel (it holds r0 and the expert's bases besides) costs a wave
+    // of occupancy at MT = 2 (4 -> 3) and at MT = 4 fp8 (3 -> 2)
+    wsgemm_walk<MT, FP8, true, false>(p, a_lds, n0, acc);
 
-    uint4 wreg[8];
-    float wsc[8];
-    auto load_w = [&](int kt) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int k = min(kt + s * 32 + kl, K - 8);
-            if constexpr (FP8) {
-                const uint2 v = *reinterpret_cast<const uint2*>(wbase + (size_t)nrow * K + k);
-                wreg[s] = make_uint4(v.x, v.y, 0, 0);
-                wsc[s] = to_f(sbase[(size_t)(nrow >> 7) * (K >> 7) + (k >> 7)]);
-            } else {
-                wreg[s] = load_nt16(reinterpret_cast<const bf16*>(wbase) + (size_t)nrow * K + k);
-            }
-        }
-    };
-    constexpr int ACH = MT * 16 * 32 / 256;
-    const bf16* arow[ACH];
-#pragma unroll
-    for (int i = 0; i < ACH; ++i) {
-        const int r = (threadIdx.x + i * 256) >> 5;
-        arow[i] = g.a + (size_t)moe_src_row(g, r0 + min(r, M - 1)) * K;
-    }
-    uint4 areg[ACH];
-    auto load_a = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < ACH; ++i) {
-            const int c = (threadIdx.x + i * 256) & 31;
-            areg[i] = *reinterpret_cast<const uint4*>(arow[i] + min(kt + c * 8, K - 8));
-        }
-    };
-    auto store_a = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < ACH; ++i) {
-            const int ch = threadIdx.x + i * 256;
-            const int r = ch >> 5, c = ch & 31;
-            const bool ok = r < M && kt + c * 8 < kend;
-            const uint4 v = areg[i];
-            *reinterpret_cast<uint4*>(a_lds + mws_off(r, c)) = make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
-        }
-    };
-
-    load_w(kbeg);
-    __builtin_amdgcn_sched_barrier(0);
-    load_a(kbeg);
-    for (int kt = kbeg; kt < kend; kt += MOE_WS_KT) {
-        __syncthreads();
-        store_a(kt);
-        __syncthreads();
-        uint4 wcur[8];
-        float scur[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) { wcur[s] = wreg[s]; scur[s] = wsc[s]; }
-        if (kt + MOE_WS_KT < kend) { load_w(kt + MOE_WS_KT); load_a(kt + MOE_WS_KT); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            uint4 bfrag;
-            if constexpr (FP8) {
-                const float sc = scur[s];
-                const f32x2 a0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wcur[s].x, false), a1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wcur[s].x, true);
-                const f32x2 a2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wcur[s].y, false), a3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wcur[s].y, true);
-                bfrag = make_uint4(pack_bf16x2(a0.x * sc, a0.y * sc), pack_bf16x2(a1.x * sc, a1.y * sc),
-                                   pack_bf16x2(a2.x * sc, a2.y * sc), pack_bf16x2(a3.x * sc, a3.y * sc));
-            } else {
-                bfrag = wcur[s];
-            }
-            const bf16x8_m b = __builtin_bit_cast(bf16x8_m, bfrag);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                if (mt >= mt_on) break;   // wave-uniform: rows past the tile are not multiplied
-                const uint4 af = *reinterpret_cast<const uint4*>(a_lds + mws_off(mt * 16 + (lane & 15), s * 4 + (lane >> 4)));
-                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_m, af), b, acc[mt], 0, 0, 0);
-            }
-        }
-    }
     const int n = n0 + (lane & 15);
     if (n >= g.N) return;
 #pragma unroll
@@ -443,15 +369,12 @@ __global__ __launch_bounds__(256) void moe_ws_kernel(MoeGemmArgs g) {
         }
 }
 
-// Tiled regime: 128 x 128 output tile per workgroup, K steps of 64, 2 x 2 waves of 64 x 64; A and B staged through
-// registers into two LDS buffers (ops_gemm.hip: lds_off swizzle, one barrier per K step).  grid (max_tiles, N/128).
-constexpr int MOE_BK = 64;
-__device__ __forceinline__ int mt_off(int row, int kc) { return row * 128 + ((kc ^ (row & 7)) << 4); }
-
+// Tiled regime: the gemm_tile_loop.hip.h loop on one tile-table entry and 128 columns: A rows gathered through a_map (rows past the
+// expert's segment are zero), B the expert's weight.  grid (max_tiles, N/128).
 template <bool FP8, bool SLAB>
-__global__ __launch_bounds__(256) void moe_tile_kernel(MoeGemmArgs g) {
-    constexpr int BM = 128, BN = 128, A_BYTES = BM * 128, B_BYTES = BN * 128;
-    __shared__ __attribute__((aligned(16))) char smem[2 * A_BYTES + 2 * B_BYTES];
+__global__ __launch_bounds__(GEMM_THREADS) void moe_tile_kernel(MoeGemmArgs g) {
+    constexpr int BM = 128, BN = 128;
+    __shared__ __attribute__((aligned(16))) char smem[gemm_tile_lds_bytes(BM, BN)];
     const int e = load_uniform_i32(g.tiles + 2 * blockIdx.x);
     if (e < 0) return;
     const int r0 = load_uniform_i32(g.tiles + 2 * blockIdx.x + 1);
@@ -463,99 +386,39 @@ __global__ __launch_bounds__(256) void moe_tile_kernel(MoeGemmArgs g) {
     const char* wbase = reinterpret_cast<const char*>(g.w) + (size_t)e * N * K * (FP8 ? 1 : 2);
     const bf16* sbase = FP8 ? g.wscale + (size_t)e * (N >> 7) * (K >> 7) : nullptr;
 
-    // A: 128 rows x 8 chunks, 4 per thread; rows past M read a clamped row and are stored as zero
-    const bf16* arow[4];
-    bool aok[4];
+    TileRegsK<BM> ra;
+    TileRegsK<BN> rb;
+    TileRegsFp8NT<BN> rb_f8;
+    const bf16* arow[TileRegsK<BM>::CH];      // rows past M read a clamped row and are stored as zeros
+    bool aok[TileRegsK<BM>::CH];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (threadIdx.x + i * 256) >> 3;
+    for (int i = 0; i < TileRegsK<BM>::CH; ++i) {
+        const int r = (threadIdx.x + i * GEMM_THREADS) >> 3;
         aok[i] = r < M;
         arow[i] = g.a + (size_t)moe_src_row(g, r0 + min(r, M - 1)) * K;
     }
-    constexpr int BCH = FP8 ? 2 : 4;   // bf16: 128 rows x 8 chunks of 8; fp8: 128 rows x 4 chunks of 16 codes
-    uint4 ra[4], rb[BCH];
-    float rs[BCH];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int kc = (threadIdx.x + i * 256) & 7;
-            const int gk = k0 + kc * 8;
-            ra[i] = gk < K ? *reinterpret_cast<const uint4*>(arow[i] + gk) : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < BCH; ++i) {
-            const int c = threadIdx.x + i * 256;
-            if constexpr (FP8) {
-                const int rr = c >> 2, q = c & 3;
-                const int gn = min(n0 + rr, N - 1), gk = k0 + q * 16;
-                rb[i] = gk < K ? *reinterpret_cast<const uint4*>(wbase + (size_t)gn * K + gk) : make_uint4(0, 0, 0, 0);
-                rs[i] = gk < K ? to_f(sbase[(size_t)(gn >> 7) * (K >> 7) + (gk >> 7)]) : 0.f;
-            } else {
-                const int rr = c >> 3, kc = c & 7;
-                const int gn = min(n0 + rr, N - 1), gk = k0 + kc * 8;
-                rb[i] = gk < K ? *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(wbase) + (size_t)gn * K + gk) : make_uint4(0, 0, 0, 0);
-            }
-        }
+    auto load_tiles = [&](int k0) {
+        ra.load_rows(arow, k0, K);
+        if constexpr (FP8) rb_f8.load(reinterpret_cast<const uint8_t*>(wbase), sbase, n0, N, k0, K);
+        else rb.load(reinterpret_cast<const bf16*>(wbase), n0, N, k0, K, K);
     };
-    auto store = [&](int buf) {
-        char* As = smem + buf * A_BYTES;
-        char* Bs = smem + 2 * A_BYTES + buf * B_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = threadIdx.x + i * 256;
-            *reinterpret_cast<uint4*>(As + mt_off(c >> 3, c & 7)) = aok[i] ? ra[i] : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < BCH; ++i) {
-            const int c = threadIdx.x + i * 256;
-            if constexpr (FP8) {
-                const int rr = c >> 2, q = c & 3;
-                float f[16];
-                WTraits<fp8e4m3>::decode(rb[i], f);
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    *reinterpret_cast<uint4*>(Bs + mt_off(rr, q * 2 + h)) =
-                        make_uint4(pack_bf16x2(f[8 * h] * rs[i], f[8 * h + 1] * rs[i]), pack_bf16x2(f[8 * h + 2] * rs[i], f[8 * h + 3] * rs[i]),
-                                   pack_bf16x2(f[8 * h + 4] * rs[i], f[8 * h + 5] * rs[i]), pack_bf16x2(f[8 * h + 6] * rs[i], f[8 * h + 7] * rs[i]));
-            } else {
-                *reinterpret_cast<uint4*>(Bs + mt_off(c >> 3, c & 7)) = rb[i];
-            }
-        }
+    auto store_tiles = [&](int buf) {
+        char* as = gemm_tile_a<BM, BN>(smem, buf);
+        char* bs = gemm_tile_b<BM, BN>(smem, buf);
+        ra.store_rows(as, aok);
+        if constexpr (FP8) rb_f8.store(bs);
+        else rb.store(bs);
     };
 
-    f32x4_m acc[4][4];
+    f32x4_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_m{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    using T = bf16;
+    const int kbeg = 0, kend = K;
+#include "gemm_tile_loop.hip.h"      // the main loop: acc += A . B^T over [kbeg, kend)
 
-    const int nk = (K + MOE_BK - 1) / MOE_BK;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) load((kt + 1) * MOE_BK);
-        const char* As = smem + buf * A_BYTES;
-        const char* Bs = smem + 2 * A_BYTES + buf * B_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            uint4 fa[4], fb[4];
-            const int kc = ks * 4 + (lane >> 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const uint4*>(As + mt_off(wm * 64 + i * 16 + (lane & 15), kc));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const uint4*>(Bs + mt_off(wn * 64 + j * 16 + (lane & 15), kc));
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_m, fa[i]), __builtin_bit_cast(bf16x8_m, fb[j]),
-                                                                        acc[i][j], 0, 0, 0);
-        }
-        if (kt + 1 < nk) store(buf ^ 1);
-        __syncthreads();
-    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -573,19 +436,17 @@ __global__ __launch_bounds__(256) void moe_tile_kernel(MoeGemmArgs g) {
         }
 }
 
-static bool moe_ws_regime(int T, int k, int E) { return (long long)T * k <= (long long)MOE_WS_ROWS_MAX * E; }
-
-// K splits of the weight-streaming regime: enough (expected active expert, 64-column slab, split) workgroups to stream on
-// every CU.  1 in the tiled regime.
-int moe_sorted_splits(int T, int k, int E, int N, int K) {
-    if (!moe_ws_regime(T, k, E)) return 1;
-    const long long active = std::min<long long>(E, (long long)T * k);
-    const long long wgs = active * ceil_div(N, 64);
-    int s = wgs >= 512 ? 1 : ceil_div(512, wgs);
-    s = std::min(s, std::max(1, K / MOE_WS_KT));
-    s = std::min(s, 16);
-    const int kps = ceil_div(ceil_div(K, s), MOE_WS_KT) * MOE_WS_KT;
-    return ceil_div(K, kps);
+// MT x FP8 x SLAB -> the instantiation (its LDS limit raised once where MT*16 rows of 512 bytes pass 48 KiB)
+template <int MT, bool FP8>
+static pgk_status moe_ws_launch_slab(const MoeGemmArgs& g, bool slab, dim3 grid, hipStream_t st) {
+    constexpr size_t lds = ws_lds_bytes(MT);
+    constexpr bool raise = lds > 48 * 1024;
+    if (slab) return launch_dyn_lds<&moe_ws_kernel<MT, FP8, true>>(grid, WS_THREADS, lds, raise, st, g);
+    return launch_dyn_lds<&moe_ws_kernel<MT, FP8, false>>(grid, WS_THREADS, lds, raise, st, g);
+}
+template <int MT>
+static pgk_status moe_ws_launch(const MoeGemmArgs& g, bool fp8, bool slab, dim3 grid, hipStream_t st) {
+    return fp8 ? moe_ws_launch_slab<MT, true>(g, slab, grid, st) : moe_ws_launch_slab<MT, false>(g, slab, grid, st);
 }
 
 }  // namespace pgk
@@ -731,32 +592,15 @@ pgk_status pgk_grouped_gemm_sorted(const void* a, const int32_t* a_map, const vo
         return PGK_OK;
     }
     const int nsplit = slab ? splits : 1;
-    g.k_per_split = ceil_div(ceil_div(K, nsplit), MOE_WS_KT) * MOE_WS_KT;
-    const int rows_bound = std::min(T * k, MOE_TILE_ROWS);
-    const int mt = ceil_div(rows_bound, 16);
+    g.k_per_split = ceil_div(ceil_div(K, nsplit), WS_KT) * WS_KT;
     dim3 grid(ceil_div(N, 64), nsplit, tiles_n);
-#define PGK_MOE_WS_LAUNCH(MTV, F8, SL)                                                                             \
-    {                                                                                                              \
-        static bool done = false;                                                                                  \
-        if (lds > 48 * 1024 && !done) {                                                                            \
-            PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&moe_ws_kernel<MTV, F8, SL>),           \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
-            done = true;                                                                                           \
-        }                                                                                                          \
-        moe_ws_kernel<MTV, F8, SL><<<grid, 256, lds, st>>>(g);                                                     \
+    switch (moe_ws_pick_mt(T, k)) {      // gemm_plan.h: 1, 2, 4 or 8 tiles of 16 rows
+        case 1: return moe_ws_launch<1>(g, fp8 != 0, slab, grid, st);
+        case 2: return moe_ws_launch<2>(g, fp8 != 0, slab, grid, st);
+        case 4: return moe_ws_launch<4>(g, fp8 != 0, slab, grid, st);
+        case 8: return moe_ws_launch<8>(g, fp8 != 0, slab, grid, st);
     }
-#define PGK_MOE_WS(MTV)                                                                                            \
-    if (mt <= MTV) {                                                                                               \
-        const size_t lds = (size_t)MTV * 16 * MOE_WS_KT * 2;                                                       \
-        if (fp8) { if (slab) PGK_MOE_WS_LAUNCH(MTV, true, true) else PGK_MOE_WS_LAUNCH(MTV, true, false) }         \
-        else { if (slab) PGK_MOE_WS_LAUNCH(MTV, false, true) else PGK_MOE_WS_LAUNCH(MTV, false, false) }           \
-        PGK_LAUNCH_CHECK();                                                                                        \
-        return PGK_OK;                                                                                             \
-    }
-    PGK_MOE_WS(1) PGK_MOE_WS(2) PGK_MOE_WS(4) PGK_MOE_WS(8)
-#undef PGK_MOE_WS
-#undef PGK_MOE_WS_LAUNCH
-    return set_error(PGK_ERR_INVALID, "pgk_grouped_gemm_sorted: no tile for %d rows", rows_bound);
+    return set_error(PGK_ERR_INVALID, "pgk_grouped_gemm_sorted: no tile for T*k=%d rows", T * k);
 }
 
 }  // extern "C"

@@ -19,12 +19,11 @@
 // where the reference's threshold chains round them away from zero, and bf16 inputs hit those ties exactly.
 
 #include "gemv_core.hip.h"
+#include "mfma_common.hip.h"
 #include "pgk_internal.h"
 
 namespace pgk {
 
-typedef int i32x8_n __attribute__((ext_vector_type(8)));
-typedef float f32x4_n __attribute__((ext_vector_type(4)));
 typedef float f32x2_n __attribute__((ext_vector_type(2)));
 
 // nvf4_scale_value (the exact decode of a scale byte) lives in gemv_core.hip.h, shared with the engine's decode kernels.
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(NV_THREADS) void gemv_nvf4_kernel(const bf16* a, co
     }
 #pragma unroll
     for (int j = 0; j < 16; j += 4)
-        *reinterpret_cast<f32x4_n*>(red + kl * NV_TN + cl * 16 + j) = f32x4_n{acc[j], acc[j + 1], acc[j + 2], acc[j + 3]};
+        *reinterpret_cast<f32x4_t*>(red + kl * NV_TN + cl * 16 + j) = f32x4_t{acc[j], acc[j + 1], acc[j + 2], acc[j + 3]};
     __syncthreads();
     if (tid < NV_TN && n0 + tid < N) {
         float sum = 0.f;
@@ -306,8 +305,6 @@ __global__ __launch_bounds__(256) void quantize_e2m1_kernel(const bf16* x, uint8
 constexpr int F4_BM = 128, F4_BN = 128, F4_THREADS = 256;
 constexpr int F4_TILE = 128 * 128;   // bytes of one staged operand tile: 128 rows x 128 bytes (256 k)
 
-__device__ __forceinline__ int f4_off(int row, int kc) { return row * 128 + ((kc ^ (row & 7)) << 4); }
-
 __global__ __launch_bounds__(F4_THREADS) void gemm_fp4_kernel(const uint8_t* A, const uint8_t* B, bf16* D, int M, int N, int Kp) {
     extern __shared__ __attribute__((aligned(16))) char f4_smem[];   // A[2] | B[2]
     auto As = [&](int buf) -> char* { return f4_smem + buf * F4_TILE; };
@@ -329,7 +326,7 @@ __global__ __launch_bounds__(F4_THREADS) void gemm_fp4_kernel(const uint8_t* A, 
     const uint8_t* b_p1 = B + (size_t)min(n0 + 32 + srow, N - 1) * RB + skc * 16;
     const uint8_t* b_p2 = B + (size_t)min(n0 + 64 + srow, N - 1) * RB + skc * 16;
     const uint8_t* b_p3 = B + (size_t)min(n0 + 96 + srow, N - 1) * RB + skc * 16;
-    const int st_off = f4_off(srow, skc);
+    const int st_off = swz128_off(srow, skc);
     auto load_tiles = [&](int kt) {
         // past the packed row (the second half of the last step when Kp % 256 == 128): load chunk 0 again and
         // zero it.  A select, not a branch: a branch here makes hipcc keep the staging registers in scratch.
@@ -351,11 +348,11 @@ __global__ __launch_bounds__(F4_THREADS) void gemm_fp4_kernel(const uint8_t* A, 
         *reinterpret_cast<uint4*>(b + 64 * 128) = rb2; *reinterpret_cast<uint4*>(b + 96 * 128) = rb3;
     };
 
-    f32x4_n acc[4][4];
+    f32x4_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_n{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     load_tiles(0);
     store_tiles(0);
@@ -365,15 +362,15 @@ __global__ __launch_bounds__(F4_THREADS) void gemm_fp4_kernel(const uint8_t* A, 
         if (kt + 1 < KT) load_tiles(kt + 1);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {   // the two 128-k halves of the step
-            i32x8_n fa[4], fb[4];
+            i32x8_t fa[4], fb[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int ar = wm * 64 + i * 16 + (lane & 15), br = wn * 64 + i * 16 + (lane & 15);
-                const uint4 a0 = *reinterpret_cast<const uint4*>(As(buf) + f4_off(ar, 4 * h + q));
-                const uint4 b0 = *reinterpret_cast<const uint4*>(Bs(buf) + f4_off(br, 4 * h + q));
+                const uint4 a0 = *reinterpret_cast<const uint4*>(As(buf) + swz128_off(ar, 4 * h + q));
+                const uint4 b0 = *reinterpret_cast<const uint4*>(Bs(buf) + swz128_off(br, 4 * h + q));
                 // e2m1 operands occupy the low 4 registers of the 8-register operand
-                fa[i] = i32x8_n{(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, 0, 0, 0, 0};
-                fb[i] = i32x8_n{(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, 0, 0, 0, 0};
+                fa[i] = i32x8_t{(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, 0, 0, 0, 0};
+                fb[i] = i32x8_t{(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, 0, 0, 0, 0};
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)

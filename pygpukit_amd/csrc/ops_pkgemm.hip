@@ -23,13 +23,11 @@
 // mul launches (src/pygpukit/llm/layers/attention.py, mlp.py; native/ops/matmul/matmul.cu:142-235).
 
 #include "gemv_core.hip.h"
+#include "mfma_common.hip.h"
 #include "pgk_internal.h"
 #include "pkgemm.hip.h"
 
 namespace pgk {
-
-typedef __bf16 bf16x8_p __attribute__((ext_vector_type(8)));
-typedef float f32x4_p __attribute__((ext_vector_type(4)));
 
 constexpr int PK_THREADS = 256;
 constexpr int PK_MT = 2;           // m-tiles per workgroup
@@ -82,10 +80,7 @@ __global__ void pack_weights_fp8_kernel(const uint8_t* w, const bf16* scale, bf1
         const int row = nt * 16 + (l & 15), k = ks * 32 + 8 * (l >> 4);
         const uint2 v = *reinterpret_cast<const uint2*>(w + (size_t)row * K + k);
         const float sc = to_f(scale[(size_t)(row >> 7) * KB + (k >> 7)]);
-        const f32x2 c0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), c1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
-        const f32x2 c2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), c3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
-        *reinterpret_cast<uint4*>(wp + t * 8) = make_uint4(pack_bf16x2(c0.x * sc, c0.y * sc), pack_bf16x2(c1.x * sc, c1.y * sc),
-                                                          pack_bf16x2(c2.x * sc, c2.y * sc), pack_bf16x2(c3.x * sc, c3.y * sc));
+        *reinterpret_cast<uint4*>(wp + t * 8) = fp8x8_to_bf16x8(v, sc);
     }
 }
 
@@ -215,11 +210,11 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_kernel(PkArgs g) {
     __syncthreads();
     PK_STAMP(2);
 
-    f32x4_p acc[NTW][PK_MT];
+    f32x4_t acc[NTW][PK_MT];
 #pragma unroll
     for (int t = 0; t < NTW; ++t)
 #pragma unroll
-        for (int mt = 0; mt < PK_MT; ++mt) acc[t][mt] = f32x4_p{0.f, 0.f, 0.f, 0.f};
+        for (int mt = 0; mt < PK_MT; ++mt) acc[t][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     // A fragment of k-step ks: row mt * 16 + l15, chunk 4 ks + q at its swizzled position.  With ks = 4 a + j the byte
     // offset is rowbase + 256 a + 16 ((4 j + q) ^ (row & 15)): the four XOR terms are per-lane constants
@@ -236,10 +231,10 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_kernel(PkArgs g) {
     auto step = [&](int s, const uint4 (&a_cur)[PK_MT]) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
-            const bf16x8_p b = __builtin_bit_cast(bf16x8_p, wr[t][s]);
+            const bf16x8_t b = __builtin_bit_cast(bf16x8_t, wr[t][s]);
 #pragma unroll
             for (int mt = 0; mt < PK_MT; ++mt)
-                acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_p, a_cur[mt]), b, acc[t][mt], 0, 0, 0);
+                acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a_cur[mt]), b, acc[t][mt], 0, 0, 0);
         }
     };
     // fragments are read TWO k-steps ahead of the MFMAs that use them: with one wave per SIMD nothing else hides the LDS
@@ -486,11 +481,11 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_resid_kernel(PkResidArgs g)
     else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     __syncthreads();
 
-    f32x4_p acc[NTW][MT];
+    f32x4_t acc[NTW][MT];
 #pragma unroll
     for (int t = 0; t < NTW; ++t)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[t][mt] = f32x4_p{0.f, 0.f, 0.f, 0.f};
+        for (int mt = 0; mt < MT; ++mt) acc[t][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     uint4 af[4][MT];
     int aoff[MT][4];
 #pragma unroll
@@ -504,10 +499,10 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_resid_kernel(PkResidArgs g)
     auto step = [&](int s, const uint4 (&a_cur)[MT]) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
-            const bf16x8_p b = __builtin_bit_cast(bf16x8_p, wr[t][s]);
+            const bf16x8_t b = __builtin_bit_cast(bf16x8_t, wr[t][s]);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
-                acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_p, a_cur[mt]), b, acc[t][mt], 0, 0, 0);
+                acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a_cur[mt]), b, acc[t][mt], 0, 0, 0);
         }
     };
     auto ahead = [&](int ks, int s2) {                          // local k-step ks, s2 = ks mod 16; KSW and ksw0 are multiples of 4

@@ -52,6 +52,33 @@ inline int ceil_div(long long a, long long b) { return static_cast<int>((a + b -
 
 #define PGK_LAUNCH_CHECK() PGK_CHECK_HIP(hipGetLastError())
 
+namespace pgk {
+
+// Launch KERNEL with `lds` bytes of dynamic LDS.  raise: the kernel may need more than the 48 KiB a kernel gets unasked, so
+// its limit is raised to `lds` first - one hipFuncSetAttribute per kernel instantiation per process (the flag below is per
+// KERNEL), always before that kernel's first launch.  Each instantiation is raised at its own first launch and not with its
+// siblings (the five modes of a kernel, say): that is intended - setting the attribute is a host-side property of the function,
+// it enqueues nothing, so it may also first happen while a stream is being captured for a mode that warm-up did not touch.
+template <auto KERNEL>
+inline pgk_status raise_dyn_lds_once(size_t lds) {
+    static bool done = false;
+    if (!done) {
+        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    return PGK_OK;
+}
+template <auto KERNEL, class... Args>
+inline pgk_status launch_dyn_lds(dim3 grid, int threads, size_t lds, bool raise, hipStream_t st, Args... args) {
+    if (raise)
+        if (pgk_status r = raise_dyn_lds_once<KERNEL>(lds)) return r;
+    KERNEL<<<grid, threads, lds, st>>>(args...);
+    PGK_LAUNCH_CHECK();
+    return PGK_OK;
+}
+
+}  // namespace pgk
+
 // Dispatch a callable templated on the device element type for the three float dtypes.
 #define PGK_DISPATCH_FLOAT(dt, NAME, ...)                                             \
     switch (dt) {                                                                     \

@@ -166,8 +166,11 @@ def run_grouped(fp8, a_rows, wq, scale, **kw):
     return ops.grouped_gemm_bf16(a_rows, wq, kw.pop("ids", None), **kw)
 
 
-# (T, k, E, N, K): T*k/E about 1 (weight-streaming regime) and about 512 (tiled regime); segments not multiples of 128
-SHAPES = [(3, 2, 8, 256, 384), (40, 8, 16, 384, 512), (2048, 2, 8, 256, 256), (700, 4, 5, 384, 640)]
+# (T, k, E, N, K): T*k/E about 1 (weight-streaming regime) and about 512 (tiled regime); segments not multiples of 128.
+# The weight-streaming kernel holds 1, 2, 4 or 8 row tiles of 16 by T*k: 6 and 320 rows take 1 and 8; 24 rows take 2 (K = 1.5
+# LDS tiles of 256) and 50 rows take 4 (K = 2.5 tiles).
+SHAPES = [(3, 2, 8, 256, 384), (40, 8, 16, 384, 512), (2048, 2, 8, 256, 256), (700, 4, 5, 384, 640),
+          (12, 2, 8, 128, 384), (25, 2, 8, 128, 640)]
 
 
 @pytest.mark.parametrize("fp8", [False, True])
