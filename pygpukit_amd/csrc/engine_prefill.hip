@@ -53,7 +53,8 @@ __global__ void embed_rows_arg_kernel(const bf16* embed, float* h, int H, EmbedT
 // the slab loads are unconditional (clamped slab index, masked add) so they share one memory round trip.
 // With q8 != nullptr (fp8-activation prefill, H % 128 == 0) the row leaves as e4m3 codes + one fp32 scale per 128
 // columns instead of bf16: the values quantised are the bf16-rounded ones, so this is bit-identical to
-// rmsnorm -> quantize_rows_kernel without the second pass over the activations.
+// rmsnorm -> quantize_rows_kernel without the second pass over the activations.  (The caller asks for it only with
+// H <= 4096 - prefill_choice's fuse_q - so the e4m3 branch of the loop over the columns past 4096 has never run.)
 template <int NS>   // slab loads issued per trip (>= nslabs): 4 on the packed path, 16 covers every split count of wsgemm
 __global__ __launch_bounds__(256) void rmsnorm_f32_bf16_kernel(float* h, const bf16* gamma, bf16* out, int rows, int H,
                                                                float eps, const float* slabs, int nslabs,
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(256) void rmsnorm_f32_bf16_kernel(float* h, const b
     __shared__ float red[16];
     const int row = blockIdx.x;
     float* hr = h + (size_t)row * H;
-    constexpr int MAXT = 4;                     // H <= 4096 handled in registers
+    constexpr int MAXT = 4;                     // columns below 4096 stay in registers between the two passes
     float4 v[MAXT];
     uint2 gm[MAXT];                             // gamma requested with the row: not a second round trip after the reduction
     float ss = 0.f;
@@ -92,32 +93,46 @@ __global__ __launch_bounds__(256) void rmsnorm_f32_bf16_kernel(float* h, const b
             ss += acc.x * acc.x + acc.y * acc.y + acc.z * acc.z + acc.w * acc.w;
         }
     }
+    // columns past 4096 (as norm_rows_bf16_kernel): slabs added and the row written back here, summed, re-read below
+    for (int i = (threadIdx.x + MAXT * 256) * 4; i < H; i += 1024) {
+        float4 acc = *reinterpret_cast<const float4*>(hr + i);
+        if (nslabs > 0) {
+            for (int s = 0; s < nslabs; ++s) {
+                const float4 p = *reinterpret_cast<const float4*>(slabs + ((size_t)s * rows + row) * H + i);
+                acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
+            }
+            *reinterpret_cast<float4*>(hr + i) = acc;         // read back below by the thread that wrote it
+        }
+        ss += acc.x * acc.x + acc.y * acc.y + acc.z * acc.z + acc.w * acc.w;
+    }
     ss = block_sum(ss, red);
     const float inv = 1.0f / sqrtf(ss / H + eps);
+    auto emit = [&](int i, const float4& u, const uint2& g) {
+        const float g0 = __uint_as_float(g.x << 16), g1 = __uint_as_float(g.x & 0xFFFF0000u);
+        const float g2 = __uint_as_float(g.y << 16), g3 = __uint_as_float(g.y & 0xFFFF0000u);
+        uint2 o;
+        o.x = pack_bf16x2(u.x * inv * g0, u.y * inv * g1);
+        o.y = pack_bf16x2(u.z * inv * g2, u.w * inv * g3);
+        if (q8) {   // 32 lanes x 4 columns = one 128-column scale block
+            const float f0 = __uint_as_float(o.x << 16), f1 = __uint_as_float(o.x & 0xFFFF0000u);
+            const float f2 = __uint_as_float(o.y << 16), f3 = __uint_as_float(o.y & 0xFFFF0000u);
+            float amax = fmaxf(fmaxf(fabsf(f0), fabsf(f1)), fmaxf(fabsf(f2), fabsf(f3)));
+            amax = group16_max(amax);
+            amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+            const float sc = amax > 0.f ? amax / 448.0f : 1.0f;
+            *reinterpret_cast<uint32_t*>(q8 + (size_t)row * H + i) = pack_fp8x4(f0 / sc, f1 / sc, f2 / sc, f3 / sc);
+            if ((threadIdx.x & 31) == 0) q8s[(size_t)row * (H >> 7) + (i >> 7)] = sc;
+        } else {
+            *reinterpret_cast<uint2*>(out + (size_t)row * H + i) = o;
+        }
+    };
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) {
         const int i = (threadIdx.x + t * 256) * 4;
-        if (i < H) {
-            const uint2 g = gm[t];
-            const float g0 = __uint_as_float(g.x << 16), g1 = __uint_as_float(g.x & 0xFFFF0000u);
-            const float g2 = __uint_as_float(g.y << 16), g3 = __uint_as_float(g.y & 0xFFFF0000u);
-            uint2 o;
-            o.x = pack_bf16x2(v[t].x * inv * g0, v[t].y * inv * g1);
-            o.y = pack_bf16x2(v[t].z * inv * g2, v[t].w * inv * g3);
-            if (q8) {   // 32 lanes x 4 columns = one 128-column scale block
-                const float f0 = __uint_as_float(o.x << 16), f1 = __uint_as_float(o.x & 0xFFFF0000u);
-                const float f2 = __uint_as_float(o.y << 16), f3 = __uint_as_float(o.y & 0xFFFF0000u);
-                float amax = fmaxf(fmaxf(fabsf(f0), fabsf(f1)), fmaxf(fabsf(f2), fabsf(f3)));
-                amax = group16_max(amax);
-                amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-                const float sc = amax > 0.f ? amax / 448.0f : 1.0f;
-                *reinterpret_cast<uint32_t*>(q8 + (size_t)row * H + i) = pack_fp8x4(f0 / sc, f1 / sc, f2 / sc, f3 / sc);
-                if ((threadIdx.x & 31) == 0) q8s[(size_t)row * (H >> 7) + (i >> 7)] = sc;
-            } else {
-                *reinterpret_cast<uint2*>(out + (size_t)row * H + i) = o;
-            }
-        }
+        if (i < H) emit(i, v[t], gm[t]);
     }
+    for (int i = (threadIdx.x + MAXT * 256) * 4; i < H; i += 1024)
+        emit(i, *reinterpret_cast<const float4*>(hr + i), *reinterpret_cast<const uint2*>(gamma + i));
 }
 
 // Per (token s, head slot hh) of qkv[n][(Hq+2Hkv)*D] bf16: q heads -> norm+rope in place;
