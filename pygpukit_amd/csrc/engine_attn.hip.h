@@ -410,9 +410,20 @@ __device__ __forceinline__ int am_voff(int row, int ch) { return row * 256 + ((c
 
 // OPROJ = false: the whole-context BATCH attention (one workgroup per (sequence, kv head), grid (Hkv, 1, batch)): the same
 // kernel without the W_o slice - the normalised heads leave as bf16 (attn_direct16) or fp32 (attn_direct) rows.
+//
+// The 14 dwords the dispatcher preloads into SGPRs (Makefile) are the LEADING arguments: everything the new token's requests
+// and the K requests of chunk 0 need - the step's qkv rows, this layer's K cache, the RoPE rows, the two gammas, and the two
+// integers every offset is made of (hq = G * hkv; the qkv row is (hq + 2 hkv) * 128 floats; launch_attn_mfma checks both
+// against the struct).  The timeline pointer follows them (TLStamp's deferred form), then the struct, whose scalar fetch
+// through the cache the dispatch just invalidated completes under the 12 + NRAW requests that do not need it; its first
+// consumers are the position load, the V requests and the W_o preloads.
+// Grid: fused form (Hkv, H / rows_per_block, 1) - kv head in x, row slice in y: no division, and the linear workgroup id
+// (kv head fastest: XCD-aware, attn_oproj_kernel) is what it was; batch form (Hkv, 1, B).
 template <int G, bool OPROJ = true>
-__global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long* tl, AttnArgs a) {
-    const TLStamp tls(tl);
+__global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_, bf16* kcache_, const float* rope_cos_, const float* rope_sin_,
+                                                              const bf16* q_gamma_, const bf16* k_gamma_, int hkv_, int max_seq_,
+                                                              unsigned long long* tl, AttnArgs a) {
+    const TLStamp tls(tl, TLStamp::Deferred{});
     typedef __bf16 am_bf16x8 __attribute__((ext_vector_type(8)));
     typedef float am_f32x4 __attribute__((ext_vector_type(4)));
     typedef short am_v4s __attribute__((ext_vector_type(4)));
@@ -425,15 +436,11 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
     __shared__ __attribute__((aligned(16))) float attn[GD];
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l15 = lane & 15, q4 = lane >> 4;
-    const int kvh = blockIdx.x % a.hkv, rb = blockIdx.x / a.hkv, b = blockIdx.z;   // kv head fastest: XCD-aware (attn_oproj_kernel)
-    const int r0 = rb * a.rows_per_block;
+    const int kvh = blockIdx.x, rb = blockIdx.y, b = blockIdx.z;
+    const int hq = G * hkv_;
     const int lr = threadIdx.x % LPW, rip = threadIdx.x / LPW;
-    const int npass = a.rows_per_block / RPP;
-    const bf16* wbase = a.w_o + (size_t)kvh * GD + lr * 8;
-    const int ldw = a.hq * D;
-    const size_t head_off = (((size_t)b * a.hkv + kvh) * a.max_seq) * D;
-    const bf16* kc = a.kcache + head_off;
-    const bf16* vc = a.vcache + head_off;
+    const size_t head_off = (((size_t)b * hkv_ + kvh) * max_seq_) * D;
+    const bf16* kc = kcache_ + head_off;
 
     // Issue order = arrival order, and every wait on it is written out here: the new token's inputs, the cache chunk and
     // nothing else go through LDS-DMA issued as inline asm, so the compiler neither counts them nor - as it does for the
@@ -448,50 +455,102 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
     constexpr int HB = (G + 2) * 512;                     // bytes of the head slices in a wave's slot; then gq, gk, cos, sin (256 each)
     constexpr int NRAW = (HB + 1024 + 1023) / 1024;
     __shared__ __attribute__((aligned(16))) char raw_lds[NWV][NRAW * 1024];
+    // the same request from a SCALAR base and one 32-bit per-lane byte offset: no 64-bit address arithmetic per lane.  Every
+    // base here is made on the scalar unit from kernel arguments and workgroup ids (no VALU-written SGPR feeds it).
+    auto dma_s = [](const void* base, uint32_t voff, uint32_t lds_addr) {
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_addr) : "memory", "m0");
+    };
     {
-        const char* row = reinterpret_cast<const char*>(a.qkv + (size_t)b * a.qkv_ld);
-        const char* cosr = reinterpret_cast<const char*>(a.rope_cos + (size_t)b * 64);
-        const char* sinr = reinterpret_cast<const char*>(a.rope_sin + (size_t)b * 64);
-        const char* gqp = a.q_gamma ? reinterpret_cast<const char*>(a.q_gamma) : cosr;      // no QK-norm: any valid bytes
-        const char* gkp = a.k_gamma ? reinterpret_cast<const char*>(a.k_gamma) : cosr;
+        const char* row = reinterpret_cast<const char*>(qkv_ + (size_t)b * ((hq + 2 * hkv_) * D));
+        const char* cosr = reinterpret_cast<const char*>(rope_cos_ + (size_t)b * 64);
+        const char* sinr = reinterpret_cast<const char*>(rope_sin_ + (size_t)b * 64);
+        const char* gqp = q_gamma_ ? reinterpret_cast<const char*>(q_gamma_) : cosr;      // no QK-norm: any valid bytes
+        const char* gkp = k_gamma_ ? reinterpret_cast<const char*>(k_gamma_) : cosr;
+        auto head_byte = [&](int hs) { return (uint32_t)((hs < G) ? (kvh * G + hs) * D : (hs == G ? (hq + kvh) * D : (hq + hkv_ + kvh) * D)) * 4u; };
 #pragma unroll
         for (int i = 0; i < NRAW; ++i) {
             const int o = 1024 * i + 16 * lane;
-            const char* src;
-            if (o < HB) {
-                const int hs = o >> 9, within = o & 511;
-                const int elem = (hs < G) ? (kvh * a.g_total + a.g_off + hs) * D : (hs == G ? (a.hq + kvh) * D : (a.hq + a.hkv + kvh) * D);
-                src = row + (size_t)elem * 4 + within;
+            if (1024 * (i + 1) <= HB) {                   // two whole head slices: the qkv row is the scalar base
+                const uint32_t within = (uint32_t)(16 * lane) & 511u;
+                dma_s(row, (lane < 32 ? head_byte(2 * i) : head_byte(2 * i + 1)) + within, lds_u32(&raw_lds[wid][0]) + 1024 * i);
             } else {
-                const int o2 = min(o - HB, 1023), seg = o2 >> 8, within = o2 & 255;
-                src = (seg == 0 ? gqp : seg == 1 ? gkp : seg == 2 ? cosr : sinr) + within;
+                const char* src;
+                if (o < HB) {
+                    src = row + head_byte(o >> 9) + (o & 511);
+                } else {
+                    const int o2 = min(o - HB, 1023), seg = o2 >> 8, within = o2 & 255;
+                    src = (seg == 0 ? gqp : seg == 1 ? gkp : seg == 2 ? cosr : sinr) + within;
+                }
+                dma(src, lds_u32(&raw_lds[wid][0]) + 1024 * i);
             }
-            dma(src, lds_u32(&raw_lds[wid][0]) + 1024 * i);
         }
     }
-    auto stage = [&](int c0) {      // rows [c0, c0 + AM_CHUNK) of K and V: instruction j = 4 rows, lane i -> row 4 j + (i >> 4), chunk position i & 15
+    // The chunk, WAVE-OWNED: wave w requests the rows of the tiles it consumes - tiles w, w + 4, w + 8 (16 rows each), every
+    // tile in four instructions of 4 rows: instruction (u, r) covers chunk rows rl = 16 (w + 4 u) + 4 r + q4, lane (q4, l15)
+    // fetching 16-byte piece l15 ^ swizzle(rl) of its row (K: rl & 15 = 4 r + q4; V: ((rl & 3) << 2) | ((rl >> 2) & 3) =
+    // 4 q4 + r - neither depends on w or u) into LDS row rl.  So a lane's byte offset from row c0 of the head is
+    //   off(u, r) = koff[r] + 16384 u,   koff[r] = 4096 w + 1024 r + 256 q4 + 16 (l15 ^ swizzle):
+    // four values per image made once; the step over u is a scalar add to the base.  No wave reads another wave's rows of
+    // the images, so no barrier stands between a wave's requests and its own reads - only its own counted waits.
+    // The clamp.  A request must stay inside the head's max_seq rows.  (a) c0 + AM_CHUNK <= max_seq (wave-uniform): every
+    // row c0 + rl, rl < AM_CHUNK, is a cache row - no clamp.  (b) otherwise the row is min(c0 + rl, max_seq - 1) as before,
+    // taken on the 32-bit byte offsets: off = 256 rl + s and lim = 256 (max_seq - 1 - c0) + s carry the same s < 256, so
+    // min(off, lim) = 256 min(rl, max_seq - 1 - c0) + s, and c0 <= max_seq - 1 wherever a chunk is staged (c0 = 0, or
+    // c0 < c1 <= max_seq).  Offsets stay below 256 max_seq: 32 bits hold them for any cache under 16 M rows.  Clamped
+    // rows are fetched and masked (positions >= c1 never count), as they always were.
+    uint32_t koff[4], voff[4];
+    {
+        const uint32_t wq = ((threadIdx.x >> 6) << 12) | ((uint32_t)q4 << 8);
 #pragma unroll
-        for (int i = 0; i < AM_CHUNK / 4 / NWV; ++i) {
-            const int j = wid + NWV * i;
-            const int rl = 4 * j + q4, rg = min(c0 + rl, a.max_seq - 1);
-            dma(kc + (size_t)rg * D + ((l15 ^ (rl & 15)) << 3), lds_u32(k_lds) + j * 1024);
+        for (int r = 0; r < 4; ++r) {
+            koff[r] = wq + 1024 * r + ((uint32_t)(l15 ^ (4 * r + q4)) << 4);
+            voff[r] = wq + 1024 * r + ((uint32_t)(l15 ^ (4 * q4 + r)) << 4);
         }
+    }
+    static_assert(AM_CHUNK == 16 * 3 * NWV, "a chunk is three 16-row tiles per wave: 12 K and 12 V requests per wave");
+    constexpr int NREQ = AM_CHUNK / 4 / NWV;              // requests per wave and image
+    auto stage_image = [&](const bf16* head, const uint32_t (&off)[4], uint32_t lds_img, int c0) {
+        const bf16* base = head + (size_t)c0 * D;
+        const uint32_t dst = lds_img + wid * 4096;
+        if (c0 + AM_CHUNK <= max_seq_) {                  // (a)
 #pragma unroll
-        for (int i = 0; i < AM_CHUNK / 4 / NWV; ++i) {
-            const int j = wid + NWV * i;
-            const int rl = 4 * j + q4, rg = min(c0 + rl, a.max_seq - 1);
-            dma(vc + (size_t)rg * D + ((l15 ^ (((rl & 3) << 2) | ((rl >> 2) & 3))) << 3), lds_u32(v_lds) + j * 1024);
+            for (int u = 0; u < 3; ++u)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dma_s(base + u * 64 * D, off[r], dst + u * 16384 + r * 1024);
+        } else {                                          // (b)
+            const uint32_t last = (uint32_t)(max_seq_ - 1 - c0) << 8;
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dma_s(base, min(off[r] + 16384u * u, last | (off[r] & 0xF0u)), dst + u * 16384 + r * 1024);
         }
     };
-    stage(0);
+    stage_image(kc, koff, lds_u32(k_lds), 0);
+    __builtin_amdgcn_sched_barrier(0);
+    // From here on the struct.  The position first: read through the constant address space it is a scalar load the compiler
+    // counts itself - issued here, ahead of the V requests, waited for where the value is first used (positions[] is not
+    // written by this launch, and the dispatch invalidated the scalar cache, which load_uniform_i32 relies on too).
+    const int pos = *(const __attribute__((address_space(4))) int32_t*)(a.positions + b);
+    const bf16* vc = a.vcache + head_off;
+    stage_image(vc, voff, lds_u32(v_lds), 0);
+    const int r0 = rb * a.rows_per_block;
+    const int npass = a.rows_per_block / RPP;
+    const bf16* wbase = a.w_o + (size_t)kvh * GD + lr * 8;
+    const int ldw = hq * D;
     uint4 pre[PRE > 0 ? PRE : 1];
 #pragma unroll
     for (int p = 0; p < PRE; ++p) pre[p] = load_nt16(wbase + (size_t)(r0 + min(p, npass - 1) * RPP + rip) * ldw);
     __builtin_amdgcn_sched_barrier(0);
-    const int pos = load_uniform_i32(a.positions + b);
     tls.phase(0);
-    // in-order return: once at most the operations issued after them are outstanding, this wave's copy of the new token's inputs is in its slot
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (AM_CHUNK / 4 / NWV) + PRE) : "memory");
+    // Vector memory returns in issue order, and per wave that order is: NRAW new-token requests, NREQ K, NREQ V, PRE W_o
+    // loads.  A wait for "at most n outstanding" therefore means: everything but the n youngest has landed.
+    constexpr int W_NEW = 2 * NREQ + PRE;                 // younger than the new token's inputs: the whole chunk + W_o
+    constexpr int W_K0 = NREQ + PRE;                      // younger than chunk 0's K rows: its V rows + W_o
+    constexpr int W_V0 = PRE;                             // younger than chunk 0's V rows: W_o
+    constexpr int W_K = NREQ;                             // later chunks (W_o long landed - it is older): the V rows
+    constexpr int W_V = 0;
+    static_assert(NREQ == 12 && W_NEW == 24 + PRE && W_K0 == 12 + PRE && W_V0 == PRE && W_K == 12, "wait counts follow the request order above");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_NEW) : "memory");
     // The new token's G + 2 head vectors (q heads, k, v) are SPLIT over the waves - item i goes to wave i % 4 - instead of
     // every wave normalising and rotating all of them (0.74 us of ALU per wave in attn_oproj_kernel): each wave reads its
     // item from its own copy of the inputs, and the results meet in LDS behind the barrier that the cache chunk needs anyway.
@@ -507,7 +566,7 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
             csv[0] = c0v.x; csv[1] = c0v.y; csv[2] = c0v.z; csv[3] = c0v.w; csv[4] = c1v.x; csv[5] = c1v.y; csv[6] = c1v.z; csv[7] = c1v.w;
             snv[0] = s0v.x; snv[1] = s0v.y; snv[2] = s0v.z; snv[3] = s0v.w; snv[4] = s1v.x; snv[5] = s1v.y; snv[6] = s1v.z; snv[7] = s1v.w;
         }
-        const bool has_norm = a.q_gamma != nullptr;
+        const bool has_norm = q_gamma_ != nullptr;
         for (int item = wid; item < G + 2; item += NWV) {    // wave-uniform
             const float4 lo = *reinterpret_cast<const float4*>(slot + item * 512 + sub * 32), hi = *reinterpret_cast<const float4*>(slot + item * 512 + sub * 32 + 16);
             float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -544,7 +603,7 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
     }
     tls.phase(1);
     uint4 qf[4];
-    const int c1 = min(pos, a.max_seq);                 // cached positions [0, c1)
+    const int c1 = min(pos, max_seq_);                  // cached positions [0, c1)
     float m_run = -INFINITY, l_run = 0.f;                // of head l15 (lanes l15 >= G carry dummies)
     am_f32x4 o[D / 16];
 #pragma unroll
@@ -552,13 +611,16 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
     const int tq = l15 >> 2, tp = l15 & 3;
     for (int c0 = 0; c0 == 0 || c0 < c1; c0 += AM_CHUNK) {
         if (c0 > 0) {
-            __syncthreads();                               // everyone is done with the previous chunk's images
-            stage(c0);
+            // no barrier: a wave overwrites only the image rows it alone reads, and its reads of the previous chunk have
+            // returned (their values went through the MFMAs above; the asm statements keep the compiler's order)
+            stage_image(kc, koff, lds_u32(k_lds), c0);
+            stage_image(vc, voff, lds_u32(v_lds), c0);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_K) : "memory");
+        } else {
+            __syncthreads();                               // publishes q_sh / k_sh / v_sh; in front of the waits, so no wave idles at it with its rows landed
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_K0) : "memory");
         }
-        // chunk 0: everything but the four W_o preloads issued behind it
-        if (c0 > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PRE) : "memory");
-        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
         if (c0 == 0) {
             // q as B fragments: lane (l15 = head, q4) of k-step ks holds dims 32 ks + 8 q4 .. + 8 of head l15
 #pragma unroll
@@ -566,14 +628,15 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
                 const uint4 v = q_sh[min(l15, G - 1)][4 * ks + q4];
                 qf[ks] = l15 < G ? v : make_uint4(0, 0, 0, 0);
             }
-            // the new token: fifth partial (score = q . k_new per head, weight 1, value v_new) and its cache row - the last wave,
-            // which had the fewest items above
+            // the new token: fifth partial (score = q . k_new per head, weight 1, value v_new) - the last wave, which had the
+            // fewest items above (its cache row is stored behind the chunk loop: a store between the requests and their
+            // counted waits would be one more operation in the count)
             if (wid == NWV - 1 && lane < LPR) {
                 float kn[8], vn[8];
                 Vec<bf16> kb, vb2;
                 kb.raw = k_sh[lane]; vb2.raw = v_sh[lane];
                 kb.to_float(kn); vb2.to_float(vn);
-                const bool live = pos < a.max_seq;
+                const bool live = pos < max_seq_;
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     Vec<bf16> qb;
@@ -587,10 +650,6 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
                     if (lane == 0) { part[NWV][g][D] = live ? dsum : -INFINITY; part[NWV][g][D + 1] = live ? 1.f : 0.f; }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) part[NWV][g][lane * 8 + j] = vn[j];
-                }
-                if (rb == 0 && live) {
-                    *reinterpret_cast<uint4*>(a.kcache + head_off + (size_t)pos * D + lane * 8) = kb.raw;
-                    *reinterpret_cast<uint4*>(a.vcache + head_off + (size_t)pos * D + lane * 8) = vb2.raw;
                 }
             }
         }
@@ -638,7 +697,10 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
         for (int i = 0; i < D / 16; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[i][r] *= alpha;
-        // O^T += V^T . P^T: step 0 pairs tiles (wid, wid + 4), step 1 tile wid + 8 with zeros
+        // O^T += V^T . P^T: step 0 pairs tiles (wid, wid + 4), step 1 tile wid + 8 with zeros - all three this wave's own requests
+        if (c0 > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_V) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_V0) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int st2 = 0; st2 < 2; ++st2) {
             const int ta = wid + NWV * (2 * st2), tb = (st2 == 0) ? wid + NWV : ta;     // tb of step 1: any staged tile (weights zero)
@@ -657,6 +719,10 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(unsigned long long
         }
     }
     tls.phase(2);
+    if (rb == 0 && wid == NWV - 1 && lane < LPR && pos < max_seq_) {     // the new token's cache row (k_sh / v_sh: read-only since the barrier)
+        *reinterpret_cast<uint4*>(kcache_ + head_off + (size_t)pos * D + lane * 8) = k_sh[lane];
+        *reinterpret_cast<uint4*>(a.vcache + head_off + (size_t)pos * D + lane * 8) = v_sh[lane];
+    }
     // the waves' states -> LDS: lane (l15 = head g, q4) holds dims 16 i + 4 q4 + r of head g
     if (l15 < G) {
         if (q4 == 0) { part[wid][l15][D] = m_run; part[wid][l15][D + 1] = l_run; }
@@ -862,7 +928,10 @@ static hipError_t launch_attn_mfma(dim3 grid, hipStream_t st, const AttnArgs& a)
         if (he != hipSuccess) return he;
         attr = true;
     }
-    return launch_k(attn_oproj_mfma_kernel<G, OPROJ>, grid, dim3(256), lds, st, a);
+    // what the kernel derives instead of fetching: its GQA group is the whole of G, and the qkv row is q, k, v back to back
+    if (a.hq != G * a.hkv || a.g_total != G || a.g_off != 0 || a.qkv_ld != (a.hq + 2 * a.hkv) * 128) return hipErrorInvalidValue;
+    // the eight leading arguments fill the 14 preloaded dwords; the timeline pointer is the ninth
+    return launch_k<8>(attn_oproj_mfma_kernel<G, OPROJ>, grid, dim3(256), lds, st, a.qkv, a.kcache, a.rope_cos, a.rope_sin, a.q_gamma, a.k_gamma, a.hkv, a.max_seq, a);
 }
 
 // f(std::integral_constant<int, G>) for the GQA group sizes the attention kernels are instantiated for
@@ -962,7 +1031,7 @@ static pgk_status launch_attn_d(const StepCtx& cx, int layer, const AttnFlags& a
         he = with_group(G, [&](auto g) {
             constexpr int GG = decltype(g)::value;
             if constexpr (D == 128) {
-                if (pick.kernel == AK_FUSED_MFMA) return launch_attn_mfma<GG>(grid, st, a);
+                if (pick.kernel == AK_FUSED_MFMA) return launch_attn_mfma<GG>(dim3(c.num_kv_heads, c.hidden_size / e->oproj_rows, m), st, a);   // kv head in x, row slice in y
                 if (pick.kernel == AK_DIRECT_MFMA) return launch_attn_mfma<GG, false>(dim3(c.num_kv_heads, 1, m), st, a);
             }
             if (pick.kernel == AK_FUSED_DOT2) return launch_k(attn_oproj_kernel<D, GG>, grid, dim3(256), 0, st, a);

@@ -20,7 +20,7 @@ namespace pgk {
 //     for the same launch (no inter-launch gap, no event-packet cost to subtract).  bench.py's `roofline` uses these.
 // (2) Timeline of a REPLAYED step: every kernel takes a LEADING `tl` pointer (null outside the diagnostic capture; leading so
 //     that it is among the kernel arguments the dispatcher preloads into SGPRs: the first-instruction stamp test then waits
-//     for no scalar load);
+//     for no scalar load; attn_oproj_mfma_kernel alone takes it BEHIND the preloaded arguments - launch_k<TL_AT>, TLStamp::Deferred);
 //     when set, each workgroup stores the 100 MHz s_memrealtime value at its first instruction and after its last
 //     barrier into its own 16-byte slot - plain stores to distinct addresses, no atomics, nothing another kernel reads.
 //     pgk_engine_timeline reduces them per launch to first start / last start / first end / last end.
@@ -40,13 +40,23 @@ struct Probe {
 };
 extern thread_local Probe* g_probe;
 
-template <class... KArgs, class... Args>
+template <class Tup, size_t... I, size_t... J>
+inline auto tl_splice(unsigned long long* tl, const Tup& t, std::index_sequence<I...>, std::index_sequence<J...>) {
+    return std::make_tuple(std::get<I>(t)..., tl, std::get<sizeof...(I) + J>(t)...);
+}
+
+// TL_AT: how many of `args` stand in front of the timeline pointer in the kernel's signature.  0 everywhere but in a kernel
+// whose issue phase needs all 14 preloaded dwords for itself (attn_oproj_mfma_kernel: the pointer follows them, TLStamp's
+// deferred form).
+template <int TL_AT = 0, class... KArgs, class... Args>
 inline hipError_t launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
-    static_assert(sizeof...(KArgs) == sizeof...(Args) + 1, "launch_k: every decode-step kernel takes a leading timeline pointer");
+    static_assert(sizeof...(KArgs) == sizeof...(Args) + 1, "launch_k: every decode-step kernel takes a timeline pointer (leading unless TL_AT says otherwise)");
+    static_assert(TL_AT >= 0 && TL_AT <= (int)sizeof...(Args), "launch_k: timeline pointer position");
     Probe* p = g_probe;
     unsigned long long* tl = nullptr;
     auto go = [&](hipEvent_t e0, hipEvent_t e1) {
-        std::tuple<KArgs...> formal{tl, args...};   // implicit conversions to the kernel's formal parameter types happen here
+        // implicit conversions to the kernel's formal parameter types happen here
+        std::tuple<KArgs...> formal{tl_splice(tl, std::make_tuple(args...), std::make_index_sequence<TL_AT>{}, std::make_index_sequence<sizeof...(Args) - TL_AT>{})};
         std::apply([&](auto... ka) {
             if (e0) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, e0, e1, 0, ka...);
             else hipLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, ka...);
@@ -82,6 +92,10 @@ struct TLStamp {
     __device__ __forceinline__ explicit TLStamp(unsigned long long* tl) : p(tl), t0(0) {
         if (p) t0 = __builtin_amdgcn_s_memrealtime();
     }
+    // for a kernel whose timeline pointer is NOT among the preloaded arguments: the first-instruction stamp is taken
+    // whatever the pointer says, so that no scalar fetch is waited for here; the pointer is first tested in phase() / end()
+    struct Deferred {};
+    __device__ __forceinline__ TLStamp(unsigned long long* tl, Deferred) : p(tl), t0(__builtin_amdgcn_s_memrealtime()) {}
     // -DPGK_PHASE_STAMPS diagnostic builds: up to 8 phase stamps per workgroup (grids <= 256 workgroups), parked in the
     // launch's unused slots [256 + 4 wg, ...); pgk_engine_timeline prints their means per kernel class to stderr
     __device__ __forceinline__ void phase(int i) const {
