@@ -100,9 +100,14 @@ struct TLStamp {
     // launch's unused slots [256 + 4 wg, ...); pgk_engine_timeline prints their means per kernel class to stderr
     __device__ __forceinline__ void phase(int i) const {
 #ifdef PGK_PHASE_STAMPS
+        // fenced for the scheduler: nothing ties the clock read to the code around it, and in straight-line code (the GEMV
+        // kernel's first trip) it was hoisted above the waits for the weights it was meant to follow
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        __builtin_amdgcn_sched_barrier(0);
         if (p && threadIdx.x == 0) {
             const unsigned wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            if (wg < 256u) p[2 * (256 + 4 * wg) + i] = __builtin_amdgcn_s_memrealtime();
+            if (wg < 256u) p[2 * (256 + 4 * wg) + i] = now;
         }
 #endif
     }

@@ -44,18 +44,50 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
     __shared__ int s_bi[4][M];
     const int K = (C > 0) ? KC : a.K;
     const int N = N_;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    // wid through readfirstlane: the wave's rows, their base addresses and the trip loop's branches are then scalar
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int OUT_PER_TRIP = (EPI == EPI_SWIGLU) ? R / 2 : R;
     const int wave = blockIdx.x * 4 + wid, nwaves = gridDim.x * 4;
+    // The epilogue is lane-parallel: output (r, m) of a trip - row n0 + r of sequence m - belongs to lane m * OUT_PER_TRIP + r.
+    constexpr int NOUT = OUT_PER_TRIP * M;
+    static_assert(NOUT <= 64, "a trip's outputs fit the lanes of a wave");
+    const int my_m = min(lane, NOUT - 1) / OUT_PER_TRIP, my_r = min(lane, NOUT - 1) - my_m * OUT_PER_TRIP;
 
     auto row_of = [&](int n0, int r) -> int {
         if constexpr (EPI == EPI_SWIGLU) return (r < R / 2) ? min(n0 + r, N - 1) : N + min(n0 + r - R / 2, N - 1);
         else return min(n0 + r, N - 1);
     };
 
-    uint4 pre[R][CL > 0 ? CL : 1];
-    float psc[R][CL > 0 ? CL : 1];
-    float resv[R][M];
+    constexpr int CLD = CL > 0 ? CL : 1;
+    uint4 pre[R][CLD];
+    uint32_t psc[R][CLD];   // the scales as loaded (fp8: bf16 bits of the block scale; NVF4: the scale byte), converted where consumed
+    float resv = 0.f;
+    // every global load of one trip (C > 0): the R rows from output nfirst on (clamped), scales alongside the weights.  Nothing
+    // here touches a loaded value: a conversion at this point would be waited for inside the issue block.
+    auto load_trip = [&](uint4 (&wq)[R][CLD], uint32_t (&sq)[R][CLD], int nfirst) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = row_of(nfirst, r);
+            if constexpr (NV4) {
+                const uint8_t* wr = reinterpret_cast<const uint8_t*>(w_) + (size_t)row * (KC >> 1);
+                const uint8_t* sr = reinterpret_cast<const uint8_t*>(wscale_) + (size_t)row * (KC >> 5);
+#pragma unroll
+                for (int c = 0; c < CL; ++c) {
+                    const int k0 = lane * NW + c * 64 * NW, kk = k0 < KC ? k0 : k0 - 1024;
+                    wq[r][c] = load_nt16(wr + (kk >> 1));
+                    sq[r][c] = sr[kk >> 5];
+                }
+                continue;
+            }
+            const WT* wr = reinterpret_cast<const WT*>(w_) + (size_t)row * KC;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int k0 = lane * NW + c * 64 * NW;
+                wq[r][c] = load_nt16(wr + k0);
+                if constexpr (FP8) sq[r][c] = wscale_[(size_t)(row >> 7) * (KC >> 7) + (k0 >> 7)].bits;
+            }
+        }
+    };
     if constexpr (C > 0) {
         // ---- all global loads of the first trip, issued back to back; nothing is waited for until the prologue's ALU ----
         // Vector memory returns in ISSUE order.  The activation vectors are a few KB that the previous kernel left in L2,
@@ -64,30 +96,6 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
         // the weights first: the prologue then started only after the last weight chunk had arrived - in-kernel stamps,
         // tools/phase_stamps.py.)
         const int nf = min(wave * OUT_PER_TRIP, N - 1);  // waves beyond N recompute the last rows (never stored)
-        auto load_weights = [&]() {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int row = row_of(nf, r);
-                if constexpr (NV4) {
-                    const uint8_t* wr = reinterpret_cast<const uint8_t*>(w_) + (size_t)row * (KC >> 1);
-                    const uint8_t* sr = reinterpret_cast<const uint8_t*>(wscale_) + (size_t)row * (KC >> 5);
-#pragma unroll
-                    for (int c = 0; c < CL; ++c) {
-                        const int k0 = lane * NW + c * 64 * NW, kk = k0 < KC ? k0 : k0 - 1024;
-                        pre[r][c] = load_nt16(wr + (kk >> 1));
-                        psc[r][c] = k0 < KC ? nvf4_scale_value(sr[kk >> 5]) : 0.f;
-                    }
-                    continue;
-                }
-                const WT* wr = reinterpret_cast<const WT*>(w_) + (size_t)row * KC;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const int k0 = lane * NW + c * 64 * NW;
-                    pre[r][c] = load_nt16(wr + k0);
-                    if constexpr (FP8) psc[r][c] = to_f(wscale_[(size_t)(row >> 7) * (KC >> 7) + (k0 >> 7)]);
-                }
-            }
-        };
         constexpr bool NORM = PRO == PRO_NORM || PRO == PRO_NORM_SUM;
         constexpr int NP = (PRO == PRO_NORM_SUM) ? 8 : 1;
         const int np = (PRO == PRO_NORM_SUM) ? naux_ : 1;
@@ -118,12 +126,8 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
             else *reinterpret_cast<uint32_t*>(xs + (size_t)m * KC + at) = pack_bf16x2(src[0], src[1]);
         };
         // ---- activation loads ----
-        if constexpr (EPI == EPI_RESID) {
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-#pragma unroll
-                for (int m = 0; m < M; ++m) resv[r][m] = *(aux_ + (size_t)m * naux_ + min(nf + r, N - 1));
-        }
+        // the residual word of the first trip, loaded by the lane that adds it (lanes past NOUT re-read the last one)
+        if constexpr (EPI == EPI_RESID) resv = *(aux_ + (size_t)my_m * naux_ + min(nf + my_r, N - 1));
         if constexpr (NORM) {
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
@@ -159,7 +163,7 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
                 for (int v = 0; v < NV; ++v) ldrun(x_ + (size_t)m * KC, v, &hv[m][VW * v]);
         }
         __builtin_amdgcn_sched_barrier(0);      // keep the compiler from hoisting the weight stream above the small loads
-        load_weights();
+        load_trip(pre, psc, nf);
         __builtin_amdgcn_sched_barrier(0);
         // ---- prologue ALU, exact trip counts ----
         if constexpr (NORM) {
@@ -252,72 +256,66 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
     __syncthreads();
 
     // ---- body ----
-    float best_v[M];
-    int best_i[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) { best_v[m] = -INFINITY; best_i[m] = 0x7FFFFFFF; }
+    // EPI_LOGITS: every lane's running best over its OWN outputs (rows ascend from trip to trip, so `>` keeps the lowest row)
+    float best_v = -INFINITY;
+    int best_i = 0x7FFFFFFF;
 
-    for (int g = wave; g * OUT_PER_TRIP < N; g += nwaves) {
-        const int n0 = g * OUT_PER_TRIP;
-        float acc[R][M];
+    // one trip's chunks, held in registers (C > 0), against the LDS image: row by row chunk 0 .. CL - 1, elements in order
+    auto consume = [&](const uint4 (&wq)[R][CLD], const uint32_t (&sq)[R][CLD], float (&acc)[R][M]) {
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+        for (int c = 0; c < CLD; ++c) {
+            const int k0 = lane * NW + c * 64 * NW;
+            if constexpr (std::is_same<WT, bf16>::value && std::is_same<XT, bf16>::value) {
+                uint4 xr[M];
 #pragma unroll
-            for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
-        if (C > 0 && g == wave) {
-            // consume the preloaded chunks
+                for (int m = 0; m < M; ++m) xr[m] = *reinterpret_cast<const uint4*>(xs + (size_t)m * K + k0);
 #pragma unroll
-            for (int c = 0; c < (C > 0 ? CL : 1); ++c) {
-                const int k0 = lane * NW + c * 64 * NW;
-                if constexpr (std::is_same<WT, bf16>::value && std::is_same<XT, bf16>::value) {
-                    uint4 xr[M];
+                for (int r = 0; r < R; ++r)
 #pragma unroll
-                    for (int m = 0; m < M; ++m) xr[m] = *reinterpret_cast<const uint4*>(xs + (size_t)m * K + k0);
+                    for (int m = 0; m < M; ++m) acc[r][m] = dot8_bf16(wq[r][c], xr[m], acc[r][m]);
+            } else if constexpr (NV4) {
+                uint4 raw[R];
+                float p[R][M];
 #pragma unroll
-                    for (int r = 0; r < R; ++r)
+                for (int r = 0; r < R; ++r) {
+                    raw[r] = wq[r][c];
 #pragma unroll
-                        for (int m = 0; m < M; ++m) acc[r][m] = dot8_bf16(pre[r][c], xr[m], acc[r][m]);
-                    continue;
+                    for (int m = 0; m < M; ++m) p[r][m] = 0.f;
                 }
-                if constexpr (NV4) {
-                    uint4 raw[R];
-                    float p[R][M];
+                nvf4_dot32<XT, M, R>(raw, xs, K, k0 < KC ? k0 : k0 - 1024, p);
 #pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        raw[r] = pre[r][c];
+                for (int r = 0; r < R; ++r) {
+                    const float sc = k0 < KC ? nvf4_scale_value(sq[r][c]) : 0.f;
 #pragma unroll
-                        for (int m = 0; m < M; ++m) p[r][m] = 0.f;
-                    }
-                    nvf4_dot32<XT, M, R>(raw, xs, K, k0 < KC ? k0 : k0 - 1024, p);
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-#pragma unroll
-                        for (int m = 0; m < M; ++m) acc[r][m] = fmaf(psc[r][c], p[r][m], acc[r][m]);
-                    continue;
-                } else {
+                    for (int m = 0; m < M; ++m) acc[r][m] = fmaf(sc, p[r][m], acc[r][m]);
+                }
+            } else {
                 float xf[M][NW];
 #pragma unroll
                 for (int m = 0; m < M; ++m) XLoad<XT, NW>::load(xs + (size_t)m * K + k0, xf[m]);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     float wf[NW];
-                    WTraits<WT>::decode(pre[r][c], wf);
+                    WTraits<WT>::decode(wq[r][c], wf);
 #pragma unroll
                     for (int m = 0; m < M; ++m) {
                         if constexpr (FP8) {
                             float p = 0.f;
 #pragma unroll
                             for (int j = 0; j < NW; ++j) p = fmaf(wf[j], xf[m][j], p);
-                            acc[r][m] = fmaf(psc[r][c], p, acc[r][m]);
+                            acc[r][m] = fmaf(bf16_bits_to_f((uint16_t)sq[r][c]), p, acc[r][m]);
                         } else {
 #pragma unroll
                             for (int j = 0; j < NW; ++j) acc[r][m] = fmaf(wf[j], xf[m][j], acc[r][m]);
                         }
                     }
                 }
-                }
             }
-        } else if constexpr (NV4) {
+        }
+    };
+    // one trip streamed from memory as it is consumed: every trip of the any-K path (C == 0), the later trips otherwise
+    auto stream_trip = [&](int n0, float (&acc)[R][M]) {
+        if constexpr (NV4) {
             const uint8_t* wrow[R];
             const uint8_t* srow[R];
 #pragma unroll
@@ -339,50 +337,93 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
             if constexpr (FP8) gemv_rows_fp8<XT, M, R>(wrow, srow, xs, K, K, lane, acc);
             else gemv_rows<WT, XT, M, R>(wrow, xs, K, K, lane, acc);
         }
+    };
+    // ---- the tail of a trip: R * M wave sums side by side, then ONE epilogue across the lanes ----
+    // Lane m * OUT_PER_TRIP + r picks output (r, m) out of the wave-uniform sums, so the SwiGLU (one exp, one IEEE division),
+    // the residual add and the store are each a single instruction sequence and one predicated store to consecutive
+    // addresses per sequence.  (Before: lane 0 alone walked the outputs, each behind its own branch - three copies of the
+    // 24-instruction SwiGLU in a row in the gate/up kernel - after R * M reductions run one after the other.)
+    auto tail = [&](int n0, float (&acc)[R][M], bool have_res, float res) {
+        float s[R * M];
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int m = 0; m < M; ++m) acc[r][m] = wave_sum(acc[r][m]);
-        // ---- epilogue (lane 0 of the wave) ----
-        if (lane == 0) {
-            if constexpr (EPI == EPI_SWIGLU) {
+            for (int m = 0; m < M; ++m) s[r * M + m] = acc[r][m];
+        wave_sum_n<R * M>(s);
+        float val = s[0], up = s[(R / 2) * M];
 #pragma unroll
-                for (int r = 0; r < R / 2; ++r)
-                    if (n0 + r < N) {
+        for (int m = 0; m < M; ++m)
 #pragma unroll
-                        for (int m = 0; m < M; ++m) {
-                            const float gt = acc[r][m], up = acc[r + R / 2][m];
-                            *(a.out + (size_t)m * a.ld_out + n0 + r) = gt / (1.0f + __expf(-gt)) * up;
-                        }
-                    }
+            for (int r = 0; r < OUT_PER_TRIP; ++r) {
+                const bool mine = lane == m * OUT_PER_TRIP + r;
+                val = mine ? s[r * M + m] : val;
+                if constexpr (EPI == EPI_SWIGLU) up = mine ? s[(r + R / 2) * M + m] : up;
+            }
+        if constexpr (EPI == EPI_SWIGLU) val = val / (1.0f + __expf(-val)) * up;
+        if (lane < NOUT && n0 + my_r < N) {
+            const size_t o = (size_t)my_m * a.ld_out + n0 + my_r;
+            if constexpr (EPI == EPI_RESID) {
+                const float base = have_res ? res : *(aux_ + o);   // the any-K path loads it here
+                *(a.out + o) = base + val;
             } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    if (n0 + r < N) {
-#pragma unroll
-                        for (int m = 0; m < M; ++m) {
-                            const size_t o = (size_t)m * a.ld_out + n0 + r;
-                            if constexpr (EPI == EPI_RESID) {
-                                const float base = (C > 0 && g == wave) ? resv[r][m] : *(aux_ + o);
-                                *(a.out + o) = base + acc[r][m];
-                            } else if constexpr (EPI == EPI_LOGITS) {
-                                a.out[o] = acc[r][m];          // read by later launches only: ordinary stores
-                            } else {
-                                *(a.out + o) = acc[r][m];
-                            }
-                            if constexpr (EPI == EPI_LOGITS) {
-                                if (acc[r][m] > best_v[m]) { best_v[m] = acc[r][m]; best_i[m] = n0 + r; }
-                            }
-                        }
-                    }
+                *(a.out + o) = val;                  // EPI_LOGITS: read by later launches only, ordinary stores
+            }
+            if constexpr (EPI == EPI_LOGITS) {
+                if (val > best_v) { best_v = val; best_i = n0 + my_r; }
             }
         }
+    };
+    auto clear = [](float (&acc)[R][M]) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
+    };
+
+    // The preloaded first trip stands in front of the loop, so its registers die there; every later trip (the lm_head makes
+    // nine or ten) and the whole any-K path stream their rows as they consume them.
+    if constexpr (C > 0) {
+        if (wave * OUT_PER_TRIP < N) {
+            float acc[R][M];
+            clear(acc);
+            consume(pre, psc, acc);
+#ifdef PGK_PHASE_STAMPS
+            // the stamp's clock read depends on nothing: tie it to the sums, or it is placed in front of the FMAs and their waits
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int m = 0; m < M; ++m) asm volatile("" : "+v"(acc[r][m]));
+#endif
+            tls.phase(0);
+            tail(wave * OUT_PER_TRIP, acc, true, resv);
+            tls.phase(1);
+        }
+    }
+    for (int g = wave + (C > 0 ? nwaves : 0); g * OUT_PER_TRIP < N; g += nwaves) {
+        float acc[R][M];
+        clear(acc);
+        stream_trip(g * OUT_PER_TRIP, acc);
+        tail(g * OUT_PER_TRIP, acc, false, 0.f);
     }
     if constexpr (EPI == EPI_LOGITS) {
         __syncthreads();  // s_bv may still be read by the prologue reduction of a slower wave
+        // the lanes' bests merged once: greater value wins, lowest row on ties - what lane 0's walk over the rows gave
+        float wv[M];
+        int wi[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            wv[m] = readlane_f(best_v, m * OUT_PER_TRIP);
+            wi[m] = __builtin_amdgcn_readlane(best_i, m * OUT_PER_TRIP);
+#pragma unroll
+            for (int r = 1; r < OUT_PER_TRIP; ++r) {
+                const float v = readlane_f(best_v, m * OUT_PER_TRIP + r);
+                const int i = __builtin_amdgcn_readlane(best_i, m * OUT_PER_TRIP + r);
+                if (v > wv[m] || (v == wv[m] && i < wi[m])) { wv[m] = v; wi[m] = i; }
+            }
+        }
         if (lane == 0) {
 #pragma unroll
-            for (int m = 0; m < M; ++m) { s_bv[wid][m] = best_v[m]; s_bi[wid][m] = best_i[m]; }
+            for (int m = 0; m < M; ++m) { s_bv[wid][m] = wv[m]; s_bi[wid][m] = wi[m]; }
         }
         __syncthreads();
         if (threadIdx.x < M) {

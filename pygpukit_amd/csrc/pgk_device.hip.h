@@ -137,6 +137,22 @@ template <int LANES> __device__ __forceinline__ float group_sum(float v) {  // L
     return v;
 }
 __device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
+// N wave sums side by side: every value takes wave_sum's tree - XOR1, XOR2, half-mirror, mirror, then
+// ((lane 0 + lane 16) + lane 32) + lane 48 - so each result is wave_sum's bit for bit.  Written step by step ACROSS the
+// values: the N DPP chains are independent, so the compiler interleaves them and fills one chain's wait states with
+// the others' adds (N calls of wave_sum run strictly one after the other, 13 dependent instructions each).
+template <int N> __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += dpp_f<DPP_XOR1>(v[i]);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += dpp_f<DPP_XOR2>(v[i]);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += dpp_f<DPP_HALF_MIRROR>(v[i]);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += dpp_f<DPP_MIRROR>(v[i]);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = readlane_f(v[i], 0) + readlane_f(v[i], 16) + readlane_f(v[i], 32) + readlane_f(v[i], 48);
+}
 __device__ __forceinline__ float wave_max(float v) {
     v = group16_max(v);
     return fmaxf(fmaxf(readlane_f(v, 0), readlane_f(v, 16)), fmaxf(readlane_f(v, 32), readlane_f(v, 48)));

@@ -1,6 +1,9 @@
 """In-kernel phase stamps of the batch-1 decode step (diagnostic build of the library):
     make -C pygpukit_amd/csrc OUT=$PWD/tools/micro/libpgk_stamps.so BUILD=/tmp/build_stamps EXTRA=-DPGK_PHASE_STAMPS
-    PGK_LIB=$PWD/tools/micro/libpgk_stamps.so python tools/phase_stamps.py"""
+    PGK_LIB=$PWD/tools/micro/libpgk_stamps.so python tools/phase_stamps.py
+The library prints the stamps' means per kernel class to stderr (class 1 qkv, 2 attention, 4 gate/up, 5 down).  The GEMV kernels
+stamp their first trip: phase 0 = last weight chunk consumed, phase 1 = outputs stored - the tail is phase 1 - phase 0.
+The spans of the first two layers follow on stdout."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
