@@ -3,6 +3,7 @@
 
 #include "attn_core.hip.h"
 #include "engine_state.hip.h"
+#include "lds_dma.hip.h"
 
 namespace pgk {
 
@@ -448,18 +449,11 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
     // the whole chunk).  Per wave: NRAW instructions for ITS copy of the new token's fp32 q/k/v slices, the two gammas
     // and the RoPE row (3 KiB for G = 2: three instructions instead of 14 register loads), 24 for the chunk, then the four
     // W_o preloads as ordinary loads.
-    auto dma = [](const void* src, uint32_t lds_addr) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory", "m0");
-    };
-    auto lds_u32 = [](const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; };
     constexpr int HB = (G + 2) * 512;                     // bytes of the head slices in a wave's slot; then gq, gk, cos, sin (256 each)
     constexpr int NRAW = (HB + 1024 + 1023) / 1024;
     __shared__ __attribute__((aligned(16))) char raw_lds[NWV][NRAW * 1024];
-    // the same request from a SCALAR base and one 32-bit per-lane byte offset: no 64-bit address arithmetic per lane.  Every
-    // base here is made on the scalar unit from kernel arguments and workgroup ids (no VALU-written SGPR feeds it).
-    auto dma_s = [](const void* base, uint32_t voff, uint32_t lds_addr) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_addr) : "memory", "m0");
-    };
+    // Where it can, a request uses the scalar-base form (lds_dma16_so): no 64-bit address arithmetic per lane.  Every base
+    // here is made on the scalar unit from kernel arguments and workgroup ids (no VALU-written SGPR feeds it).
     {
         const char* row = reinterpret_cast<const char*>(qkv_ + (size_t)b * ((hq + 2 * hkv_) * D));
         const char* cosr = reinterpret_cast<const char*>(rope_cos_ + (size_t)b * 64);
@@ -472,7 +466,7 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
             const int o = 1024 * i + 16 * lane;
             if (1024 * (i + 1) <= HB) {                   // two whole head slices: the qkv row is the scalar base
                 const uint32_t within = (uint32_t)(16 * lane) & 511u;
-                dma_s(row, (lane < 32 ? head_byte(2 * i) : head_byte(2 * i + 1)) + within, lds_u32(&raw_lds[wid][0]) + 1024 * i);
+                lds_dma16_so(row, (lane < 32 ? head_byte(2 * i) : head_byte(2 * i + 1)) + within, lds_addr_of(&raw_lds[wid][0]) + 1024 * i);
             } else {
                 const char* src;
                 if (o < HB) {
@@ -481,7 +475,7 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
                     const int o2 = min(o - HB, 1023), seg = o2 >> 8, within = o2 & 255;
                     src = (seg == 0 ? gqp : seg == 1 ? gkp : seg == 2 ? cosr : sinr) + within;
                 }
-                dma(src, lds_u32(&raw_lds[wid][0]) + 1024 * i);
+                lds_dma16(src, lds_addr_of(&raw_lds[wid][0]) + 1024 * i);
             }
         }
     }
@@ -516,23 +510,23 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
 #pragma unroll
             for (int u = 0; u < 3; ++u)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) dma_s(base + u * 64 * D, off[r], dst + u * 16384 + r * 1024);
+                for (int r = 0; r < 4; ++r) lds_dma16_so(base + u * 64 * D, off[r], dst + u * 16384 + r * 1024);
         } else {                                          // (b)
             const uint32_t last = (uint32_t)(max_seq_ - 1 - c0) << 8;
 #pragma unroll
             for (int u = 0; u < 3; ++u)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) dma_s(base, min(off[r] + 16384u * u, last | (off[r] & 0xF0u)), dst + u * 16384 + r * 1024);
+                for (int r = 0; r < 4; ++r) lds_dma16_so(base, min(off[r] + 16384u * u, last | (off[r] & 0xF0u)), dst + u * 16384 + r * 1024);
         }
     };
-    stage_image(kc, koff, lds_u32(k_lds), 0);
+    stage_image(kc, koff, lds_addr_of(k_lds), 0);
     __builtin_amdgcn_sched_barrier(0);
     // From here on the struct.  The position first: read through the constant address space it is a scalar load the compiler
     // counts itself - issued here, ahead of the V requests, waited for where the value is first used (positions[] is not
     // written by this launch, and the dispatch invalidated the scalar cache, which load_uniform_i32 relies on too).
     const int pos = *(const __attribute__((address_space(4))) int32_t*)(a.positions + b);
     const bf16* vc = a.vcache + head_off;
-    stage_image(vc, voff, lds_u32(v_lds), 0);
+    stage_image(vc, voff, lds_addr_of(v_lds), 0);
     const int r0 = rb * a.rows_per_block;
     const int npass = a.rows_per_block / RPP;
     const bf16* wbase = a.w_o + (size_t)kvh * GD + lr * 8;
@@ -613,8 +607,8 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
         if (c0 > 0) {
             // no barrier: a wave overwrites only the image rows it alone reads, and its reads of the previous chunk have
             // returned (their values went through the MFMAs above; the asm statements keep the compiler's order)
-            stage_image(kc, koff, lds_u32(k_lds), c0);
-            stage_image(vc, voff, lds_u32(v_lds), c0);
+            stage_image(kc, koff, lds_addr_of(k_lds), c0);
+            stage_image(vc, voff, lds_addr_of(v_lds), c0);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_K) : "memory");
         } else {
             __syncthreads();                               // publishes q_sh / k_sh / v_sh; in front of the waits, so no wave idles at it with its rows landed

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void batched_mfma_kernel(unsigned long long* t
             if (ok) a.out[o] = resv + y[0];
         } else if constexpr (EPI == EPI_SWIGLU) {
             if (ok) {
-                const float act = y[0] / (1.0f + __expf(-y[0])) * y[NT - 1];
+                const float act = silu_mul(y[0], y[NT - 1]);
                 if (a.out16) a.out16[o] = from_f<bf16>(act);
                 else a.out[o] = act;
             }
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256) void batched_reg_kernel(unsigned long long* tl
             if (ok) a.out[o] = resv + y[0];
         } else if constexpr (EPI == EPI_SWIGLU) {
             if (ok) {
-                const float act = y[0] / (1.0f + __expf(-y[0])) * y[NT - 1];
+                const float act = silu_mul(y[0], y[NT - 1]);
                 if (a.out16) a.out16[o] = from_f<bf16>(act);
                 else a.out[o] = act;
             }
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
                 if (ok) a.out[o] = v;
             } else if constexpr (EPI == EPI_SWIGLU) {
                 if (ok) {
-                    const float act = y[0] / (1.0f + __expf(-y[0])) * y[NT - 1];
+                    const float act = silu_mul(y[0], y[NT - 1]);
                     if (a.out16) a.out16[o] = from_f<bf16>(act);
                     else a.out[o] = act;
                 }

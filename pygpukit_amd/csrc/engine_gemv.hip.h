@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void fused_gemv_kernel(unsigned long long* tl,
                 val = mine ? s[r * M + m] : val;
                 if constexpr (EPI == EPI_SWIGLU) up = mine ? s[(r + R / 2) * M + m] : up;
             }
-        if constexpr (EPI == EPI_SWIGLU) val = val / (1.0f + __expf(-val)) * up;
+        if constexpr (EPI == EPI_SWIGLU) val = silu_mul(val, up);
         if (lane < NOUT && n0 + my_r < N) {
             const size_t o = (size_t)my_m * a.ld_out + n0 + my_r;
             if constexpr (EPI == EPI_RESID) {

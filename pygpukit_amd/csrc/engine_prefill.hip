@@ -235,22 +235,10 @@ __global__ void swiglu_rows_kernel(const bf16* gu, bf16* act, int n, int I, cons
             g.load(gu + s * 2 * I + c * 8);
             u.load(gu + s * 2 * I + I + c * 8);
         }
-        float gf[8], uf[8];
-        g.to_float(gf);
-        u.to_float(uf);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) gf[j] = gf[j] / (1.0f + __expf(-gf[j])) * uf[j];
-        g.from_float(gf);
+        g = swiglu8(g, u);
         if (q8) {   // 16 lanes x 8 columns = one scale block; total and stride are multiples of 16, so groups stay whole
-            g.to_float(gf);
-            float amax = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(gf[j]));
-            amax = group16_max(amax);
-            const float sc = amax > 0.f ? amax / 448.0f : 1.0f;
-            uint2 o;
-            o.x = pack_fp8x4(gf[0] / sc, gf[1] / sc, gf[2] / sc, gf[3] / sc);
-            o.y = pack_fp8x4(gf[4] / sc, gf[5] / sc, gf[6] / sc, gf[7] / sc);
+            float sc;
+            const uint2 o = quant_e4m3_block16(g, sc);
             *reinterpret_cast<uint2*>(q8 + s * I + c * 8) = o;
             if ((c & 15) == 0) q8s[s * (I >> 7) + (c >> 4)] = sc;
         } else {

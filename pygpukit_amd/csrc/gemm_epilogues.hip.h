@@ -1,4 +1,5 @@
-// Arguments of the GEMM epilogues that finish an engine step inside the projection (ops_gemm256.hip; callers: ops_gemm.hip, engine_prefill.hip).
+// What the GEMM epilogues that finish an engine step inside the projection (ops_gemm256.hip; callers: ops_gemm.hip, engine_prefill.hip)
+// share with each other and with the separate passes they replace (engine_prefill.hip): arguments and per-row arithmetic.
 #pragma once
 #include "pgk_device.hip.h"
 
@@ -53,6 +54,35 @@ __device__ __forceinline__ void qkv_head_finish(float (&x)[8], int sub, int slot
         const int kvh = is_k ? slot - hd.hq : slot - hd.hq - hd.hkv;
         ov.store((is_k ? hd.kcache : hd.vcache) + ((size_t)kvh * hd.max_seq + pos) * 128 + sub * 8);
     }
+}
+
+// act = bf16(silu(g) * u) for 8 columns of bf16 g and u: swiglu_rows_kernel and the SwiGLU epilogues all call this on the values a
+// plain bf16 epilogue would have stored, so GEMM + swiglu_rows_kernel and the fused forms agree bit for bit
+__device__ __forceinline__ Vec<bf16> swiglu8(const Vec<bf16>& g, const Vec<bf16>& u) {
+    float gf[8], uf[8];
+    g.to_float(gf);
+    u.to_float(uf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gf[e] = silu_mul(gf[e], uf[e]);
+    Vec<bf16> act;
+    act.from_float(gf);
+    return act;
+}
+
+// One 128-column e4m3 scale block held by 16 consecutive lanes, 8 bf16 values each (quantize_fp8_rows' contract): scale = absmax
+// over the block / 448 (1 for an all-zero block), returned in `sc` to all 16 lanes with the lane's eight codes.
+__device__ __forceinline__ uint2 quant_e4m3_block16(const Vec<bf16>& v, float& sc) {
+    float f[8];
+    v.to_float(f);
+    float amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
+    amax = group16_max(amax);
+    sc = amax > 0.f ? amax / 448.0f : 1.0f;
+    uint2 o;
+    o.x = pack_fp8x4(f[0] / sc, f[1] / sc, f[2] / sc, f[3] / sc);
+    o.y = pack_fp8x4(f[4] / sc, f[5] / sc, f[6] / sc, f[7] / sc);
+    return o;
 }
 
 }  // namespace pgk

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "attn_core.hip.h"
+#include "lds_dma.hip.h"
 #include "pgk_internal.h"
 
 namespace pgk {
@@ -219,19 +220,15 @@ __global__ __launch_bounds__(64 * NW) void attn_short_kernel(const bf16* q, cons
     const int kv_need = min(kv_len, causal_off + min(qb0 + 16 * NW, q_len));
     const int nstep = (kv_need + 31) >> 5;
     {
-        const uint32_t k0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)k_lds;
-        const uint32_t v0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)v_lds;
-        auto dma = [](const void* src, uint32_t lds_addr) {
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory", "m0");
-        };
+        const uint32_t k0 = lds_addr_of(k_lds), v0 = lds_addr_of(v_lds);
         const int ninst = nstep * 8;                       // 4 rows each
         for (int j = wid; j < ninst; j += NW) {
             const int r = 4 * j + q4;
-            dma(kh + (size_t)min(r, kv_len - 1) * sd.ks + ((l15 ^ (r & 15)) << 3), k0 + j * 1024);
+            lds_dma16(kh + (size_t)min(r, kv_len - 1) * sd.ks + ((l15 ^ (r & 15)) << 3), k0 + j * 1024);
         }
         for (int j = wid; j < ninst; j += NW) {
             const int r = 4 * j + q4;
-            dma(vh + (size_t)min(r, kv_len - 1) * sd.ks + ((l15 ^ (((r & 3) << 2) | ((r >> 2) & 3))) << 3), v0 + j * 1024);
+            lds_dma16(vh + (size_t)min(r, kv_len - 1) * sd.ks + ((l15 ^ (((r & 3) << 2) | ((r >> 2) & 3))) << 3), v0 + j * 1024);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMAs (and its query fragments); the barrier makes the images everyone's

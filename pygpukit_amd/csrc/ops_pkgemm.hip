@@ -23,6 +23,7 @@
 // mul launches (src/pygpukit/llm/layers/attention.py, mlp.py; native/ops/matmul/matmul.cu:142-235).
 
 #include "gemv_core.hip.h"
+#include "lds_dma.hip.h"
 #include "mfma_common.hip.h"
 #include "pgk_internal.h"
 #include "pkgemm.hip.h"
@@ -34,12 +35,6 @@ constexpr int PK_MT = 2;           // m-tiles per workgroup
 constexpr int PK_MB = PK_MT * 16;  // rows per m-block
 constexpr int PK_RING = 16;        // k-steps of weights in flight per n-tile
 
-__device__ __forceinline__ void pk_dma16(const void* src, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory", "m0");
-}
-__device__ __forceinline__ uint32_t pk_lds_addr(const char* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
-}
 // 16-byte chunk c of a row lives at chunk position pk_swz(c, row): involution inside aligned groups of 16 chunks
 __device__ __forceinline__ int pk_swz(int c, int row) { return (c & ~15) | ((c ^ row) & 15); }
 
@@ -149,12 +144,12 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_kernel(PkArgs g) {
         const bf16* gsafe = has_gamma ? gm : reinterpret_cast<const bf16*>(g.rope_cos);
         gbits[0] = gsafe[d].bits; gbits[1] = gsafe[d + 64].bits;
         if (is_q || is_k) {
-            const uint32_t r0 = pk_lds_addr(reinterpret_cast<const char*>(rope_lds));
+            const uint32_t r0 = lds_addr_of(rope_lds);
             constexpr int IPT = PK_MB / 4;                    // instructions per table: 4 rows each
             for (int j = wid; j < 2 * IPT; j += 4) {           // instruction j: table j / IPT, rows 4 (j % IPT) + q, 16 bytes per lane
                 const int row = 4 * (j % IPT) + q;
                 const int pos = min(g.start_pos + min(m0 + row, g.M - 1), g.max_seq - 1);
-                pk_dma16(((j / IPT) ? g.rope_sin : g.rope_cos) + (size_t)pos * 64 + 4 * l15, r0 + j * 1024);
+                lds_dma16(((j / IPT) ? g.rope_sin : g.rope_cos) + (size_t)pos * 64 + 4 * l15, r0 + j * 1024);
             }
         }
     }
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_kernel(PkArgs g) {
     // in group 4 j + (i >> 4) at chunk position i & 15.  row = group / groups-per-row through a 16-bit reciprocal (exact for
     // the <= 2048 groups of a block, no integer division in the issue path).
     {
-        const uint32_t lds0 = pk_lds_addr(a_lds);
+        const uint32_t lds0 = lds_addr_of(a_lds);
         const int ndma = PK_MB * rb / 1024, gpr = KS >> 2;
         const uint32_t magic = (65536u + gpr - 1) / gpr;
         const bf16* abase = g.a + (size_t)ks0 * 32;
@@ -186,7 +181,7 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_kernel(PkArgs g) {
             const int grp = 4 * j + q;
             const int row = (int)(((uint32_t)grp * magic) >> 16), gi = grp - row * gpr;
             const int c = gi * 16 + ((l15 ^ row) & 15);
-            pk_dma16(abase + (size_t)min(m0 + row, g.M - 1) * g.lda + c * 8, lds0 + j * 1024);
+            lds_dma16(abase + (size_t)min(m0 + row, g.M - 1) * g.lda + c * 8, lds0 + j * 1024);
         }
     }
     // weight ring: exactly NTW * PK_RING loads behind the DMAs (clamped k-step: the explicit wait below counts them)
@@ -323,7 +318,7 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_kernel(PkArgs g) {
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + mt * 16 + 4 * q + r;
                 const float gf = to_f(from_f<bf16>(acc[0][mt][r])), uf = to_f(from_f<bf16>(acc[1][mt][r]));
-                if (m < g.M) c[(size_t)m * g.ldc + n] = from_f<bf16>(gf / (1.0f + __expf(-gf)) * uf);
+                if (m < g.M) c[(size_t)m * g.ldc + n] = from_f<bf16>(silu_mul(gf, uf));
             }
     } else {
         // one head of 128: lane holds dims d = 16 wid + l15 (tile 0) and d + 64 (tile 1) of rows m
@@ -458,14 +453,14 @@ __global__ __launch_bounds__(PK_THREADS) void pkgemm_resid_kernel(PkResidArgs g)
         for (int i = 0; i < EPT; ++i) gnb[i] = gsafe[en[i]].bits;
     }
     {
-        const uint32_t lds0 = pk_lds_addr(a_lds);
+        const uint32_t lds0 = lds_addr_of(a_lds);
         const int ndma = MB * rb / 1024, gpr = KS >> 2;
         const uint32_t magic = (65536u + gpr - 1) / gpr;
         for (int j = wid; j < ndma; j += 4) {
             const int grp = 4 * j + q;
             const int row = (int)(((uint32_t)grp * magic) >> 16), gi = grp - row * gpr;
             const int c = gi * 16 + ((l15 ^ row) & 15);
-            pk_dma16(g.a + (size_t)min(m0 + row, g.M - 1) * g.lda + c * 8, lds0 + j * 1024);
+            lds_dma16(g.a + (size_t)min(m0 + row, g.M - 1) * g.lda + c * 8, lds0 + j * 1024);
         }
     }
     const int ksn = KS;

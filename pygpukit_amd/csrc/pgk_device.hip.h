@@ -43,6 +43,10 @@ template <> __device__ __forceinline__ bf16 from_f<bf16>(float f) { return bf16{
 // epilogue (conv1d) call this one function, so a fused result equals the op applied to the same fp32 value bit for bit
 __device__ __forceinline__ float gelu_tanh(float x) { return x * 0.5f * (1.0f + tanhf(0.7978845608f * (x + 0.044715f * x * x * x))); }
 
+// SwiGLU's silu(g) * u, the one expression every kernel that fuses it uses (GEMV / GEMM epilogues, swiglu_rows_kernel): a fused
+// result equals the separate pass on the same fp32 values bit for bit
+__device__ __forceinline__ float silu_mul(float g, float u) { return g / (1.0f + __expf(-g)) * u; }
+
 // ---- 16-byte vectors ----------------------------------------------------------------------
 // Vec<T>::N elements of T in one 16-byte access: 4 x fp32 or 8 x 16-bit.
 template <class T> struct Vec {
