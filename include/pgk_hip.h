@@ -172,6 +172,18 @@ pgk_status pgk_cast(const void* src, pgk_dtype src_dt, void* dst, pgk_dtype dst_
 const char* pgk_base_op_plan(const char* op, size_t rows, int features, pgk_dtype dt, int aligned);
 int pgk_base_op_grid(const char* op, size_t n_or_rows, int features, pgk_dtype dt, int aligned);
 
+/* Host-only queries of the byte movers' dispatch (csrc/tensor_plan.h; DESIGN.md "Byte-mover dispatch leaves"): the kernel
+ * instantiation a call takes and the number of blocks it launches, from the functions the launchers themselves call.  The work
+ * is batch * rows rows of row_bytes bytes.  op: "transpose_2d" (batch 1) / "transpose_batched" (batch <= 65535): matrices of
+ * rows x row_bytes / itemsize -> "tile64"; "transpose_3d_021", "repeat_interleave", "slice_rows", "kv_cache_write" (seq * cache
+ * heads rows), "embedding_lookup", "scatter_last_logits": output rows -> "vec16" .. "vec1"; "split_qkv": rows of q + k + v bytes,
+ * low_bits also carrying q_bytes | k_bytes | v_bytes; "paged_cache_write": tokens * kv heads rows, whole 16-byte chunks ->
+ * "vec16"; "argmax": rows of row_bytes / itemsize elements -> "block256" / "block1024".  low_bits: the OR of the addresses the
+ * launcher tests (the low four bits count).  NULL / -1 and pgk_last_error for a call the entry point rejects, and for an empty one,
+ * which launches nothing.  No device is touched. */
+const char* pgk_tensor_op_plan(const char* op, size_t batch, size_t rows, size_t row_bytes, int itemsize, unsigned low_bits);
+int pgk_tensor_op_grid(const char* op, size_t batch, size_t rows, size_t row_bytes, int itemsize, unsigned low_bits);
+
 /* ------------------------------------------------------------------------ norms ----- */
 /* ops.cuh:152-155 rmsnorm(input[rows,features], gamma[features]) -> out (may alias input) */
 pgk_status pgk_rmsnorm(const void* x, const void* gamma, void* out, int rows, int features, float eps,
@@ -291,7 +303,8 @@ pgk_status pgk_paged_attention_v1(const void* q, const void* k_cache, const void
 pgk_status pgk_paged_cache_write(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
                                  const int32_t* slot_mapping, int n_tokens, int num_kv_heads, int block_size, int head_dim,
                                  int itemsize, pgk_stream s);
-/* ops.cuh:520-528 scatter_last_token_logits (continuous_batching.cuh:103-133): out[b] = logits[seq_start[b] + seq_lens[b] - 1] */
+/* ops.cuh:520-528 scatter_last_token_logits (continuous_batching.cuh:103-133): out[b] = logits[seq_start[b] + seq_lens[b] - 1];
+ * any vocabulary and alignment: 16-, 8-, 4-, 2- or 1-byte vectors by the row's byte size and the two addresses (tensor_plan.h) */
 pgk_status pgk_scatter_last_token_logits(const void* logits, void* out, const int32_t* seq_start, const int32_t* seq_lens,
                                          int batch, int vocab, int itemsize, pgk_stream s);
 /* ops.cuh:530-539 prepare_position_ids (continuous_batching.cuh:139-165) */

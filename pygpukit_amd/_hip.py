@@ -174,6 +174,8 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_ln_linear_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
                "pgk_gemm_plan": ([C.c_char_p, _I, _I, _I, _I, _I], C.c_char_p),
                "pgk_base_op_plan": ([C.c_char_p, _Z, _I, _I, _I], C.c_char_p), "pgk_base_op_grid": ([C.c_char_p, _Z, _I, _I, _I], C.c_int),
+               "pgk_tensor_op_plan": ([C.c_char_p, _Z, _Z, _Z, _I, C.c_uint], C.c_char_p),
+               "pgk_tensor_op_grid": ([C.c_char_p, _Z, _Z, _Z, _I, C.c_uint], C.c_int),
                "pgk_audio_log_mel_plan": ([_I, _I, _I], C.c_int),
                "pgk_adaln_plan": ([_I, _I, _I], C.c_char_p),
                "pgk_flux_qk_norm_rope_plan": ([_I, _I, _I], C.c_char_p),

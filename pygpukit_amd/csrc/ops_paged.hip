@@ -15,6 +15,7 @@
 
 #include "attn_core.hip.h"
 #include "pgk_internal.h"
+#include "tensor_plan.h"
 
 namespace pgk {
 
@@ -144,12 +145,12 @@ __global__ void paged_cache_write_kernel(const char* k_new, const char* v_new, c
 }
 
 // logits [batch_tokens, vocab] -> out [batch, vocab]: row seq_start[b] + seq_len[b] - 1 of each sequence
-__global__ void scatter_last_logits_kernel(const char* logits, char* out, const int32_t* seq_start, const int32_t* seq_lens, int row_bytes) {
+template <class V>
+__global__ void scatter_last_logits_kernel(const V* logits, V* out, const int32_t* seq_start, const int32_t* seq_lens, int row_vecs) {
     const int b = blockIdx.x;
-    const size_t src = (size_t)(seq_start[b] + seq_lens[b] - 1) * row_bytes, dst = (size_t)b * row_bytes;
-    for (int c = threadIdx.x * 16; c + 16 <= row_bytes; c += blockDim.x * 16)
-        *reinterpret_cast<uint4*>(out + dst + c) = *reinterpret_cast<const uint4*>(logits + src + c);
-    for (int c = (row_bytes & ~15) + threadIdx.x; c < row_bytes; c += blockDim.x) out[dst + c] = logits[src + c];
+    const V* src = logits + (size_t)(seq_start[b] + seq_lens[b] - 1) * row_vecs;
+    V* dst = out + (size_t)b * row_vecs;
+    for (int v = threadIdx.x; v < row_vecs; v += blockDim.x) dst[v] = src[v];
 }
 
 // continuous_batching.cuh:139-165: prefill tokens get their index in the sequence, decode tokens the context length
@@ -223,13 +224,13 @@ pgk_status pgk_paged_attention_v1(const void* q, const void* k_cache, const void
 pgk_status pgk_paged_cache_write(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int32_t* slot_mapping,
                                  int n_tokens, int num_kv_heads, int block_size, int head_dim, int itemsize, pgk_stream s) {
     PGK_REQUIRE(k_new && v_new && k_cache && v_cache && slot_mapping, "pgk_paged_cache_write: null pointer");
-    PGK_REQUIRE(n_tokens >= 0 && num_kv_heads >= 1 && block_size >= 1 && (head_dim * itemsize) % 16 == 0,
+    PGK_REQUIRE(n_tokens >= 0 && num_kv_heads >= 1 && block_size >= 1 && head_dim >= 1 && itemsize >= 1 &&
+                    paged_write_row_ok((size_t)head_dim * itemsize),
                 "pgk_paged_cache_write: bad shape (tokens=%d, Hkv=%d, block=%d, row bytes=%d)", n_tokens, num_kv_heads, block_size,
                 head_dim * itemsize);
     if (!n_tokens) return PGK_OK;
-    const long long total = (long long)n_tokens * num_kv_heads * (head_dim * itemsize / 16);
-    const int blocks = (int)(ceil_div(total, 256) > 4096 ? 4096 : ceil_div(total, 256));
-    paged_cache_write_kernel<16><<<blocks, 256, 0, resolve_stream(s)>>>((const char*)k_new, (const char*)v_new, (char*)k_cache, (char*)v_cache,
+    const int blocks = paged_write_grid((size_t)n_tokens * num_kv_heads, (size_t)head_dim * itemsize);      // tensor_plan.h
+    paged_cache_write_kernel<16><<<blocks, TN_BLOCK, 0, resolve_stream(s)>>>((const char*)k_new, (const char*)v_new, (char*)k_cache, (char*)v_cache,
                                                                        slot_mapping, n_tokens, num_kv_heads, block_size, head_dim * itemsize);
     PGK_LAUNCH_CHECK();
     return PGK_OK;
@@ -239,9 +240,12 @@ pgk_status pgk_scatter_last_token_logits(const void* logits, void* out, const in
                                          int vocab, int itemsize, pgk_stream s) {
     PGK_REQUIRE(logits && out && seq_start && seq_lens, "pgk_scatter_last_token_logits: null pointer");
     PGK_REQUIRE(batch >= 1 && vocab >= 1, "pgk_scatter_last_token_logits: bad shape");
-    PGK_REQUIRE(((size_t)vocab * itemsize) % 16 == 0, "pgk_scatter_last_token_logits: rows of %zu bytes are not 16-byte multiples",
-                (size_t)vocab * itemsize);
-    scatter_last_logits_kernel<<<batch, 256, 0, resolve_stream(s)>>>((const char*)logits, (char*)out, seq_start, seq_lens, vocab * itemsize);
+    const size_t row_bytes = (size_t)vocab * itemsize;
+    PGK_REQUIRE(itemsize >= 1 && row_bytes <= 0x7fffffffu, "pgk_scatter_last_token_logits: rows of %zu bytes", row_bytes);
+    const int w = pick_vec_bytes(row_bytes, addr_bits({logits, out}));      // tensor_plan.h
+    const int row_vecs = (int)(row_bytes / w);
+    hipStream_t st = resolve_stream(s);
+    PGK_BY_VEC(w, scatter_last_logits_kernel<V><<<batch, TN_BLOCK, 0, st>>>((const V*)logits, (V*)out, seq_start, seq_lens, row_vecs));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
 }

@@ -3,14 +3,11 @@
 
 #include "pgk_device.hip.h"
 #include "pgk_internal.h"
+#include "tensor_plan.h"
+
+#include <string>
 
 namespace pgk {
-
-static inline int cap_grid(size_t items, int block = 256) {
-    size_t g = (items + block - 1) / block;
-    if (g < 1) g = 1;
-    return (int)(g > 4096 ? 4096 : g);
-}
 
 // ---- 2-D transpose through a padded 64x64 LDS tile ----------------------------------------
 template <class E>
@@ -140,28 +137,23 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const T* x, int n, int32_t
     }
 }
 
-// pick the widest vector type that divides row_bytes and keeps both pointers aligned
-static inline int pick_vec_bytes(size_t row_bytes, std::initializer_list<const void*> ptrs) {
-    for (int w : {16, 8, 4, 2, 1}) {
-        bool ok = (row_bytes % w) == 0;
-        for (const void* p : ptrs) ok = ok && ((reinterpret_cast<uintptr_t>(p) % w) == 0);
-        if (ok) return w;
+// launch transpose2d_kernel on the tile grid of tensor_plan.h
+static pgk_status launch_transpose(const char* who, const void* in, void* out, int batch, int rows, int cols, int itemsize, hipStream_t st) {
+    dim3 grid(transpose_tiles_x(cols), transpose_tiles_y(rows), batch);
+    switch (itemsize) {
+        case 1: transpose2d_kernel<uint8_t><<<grid, TN_BLOCK, 0, st>>>((const uint8_t*)in, (uint8_t*)out, rows, cols); break;
+        case 2: transpose2d_kernel<uint16_t><<<grid, TN_BLOCK, 0, st>>>((const uint16_t*)in, (uint16_t*)out, rows, cols); break;
+        case 4: transpose2d_kernel<uint32_t><<<grid, TN_BLOCK, 0, st>>>((const uint32_t*)in, (uint32_t*)out, rows, cols); break;
+        case 8: transpose2d_kernel<uint2><<<grid, TN_BLOCK, 0, st>>>((const uint2*)in, (uint2*)out, rows, cols); break;
+        default: return set_error(PGK_ERR_INVALID, "%s: itemsize %d", who, itemsize);
     }
-    return 1;
+    PGK_LAUNCH_CHECK();
+    return PGK_OK;
 }
 
 }  // namespace pgk
 
 using namespace pgk;
-
-#define PGK_BY_VEC(w, ...)                                           \
-    switch (w) {                                                     \
-        case 16: { using V = uint4; __VA_ARGS__; } break;            \
-        case 8: { using V = uint2; __VA_ARGS__; } break;             \
-        case 4: { using V = uint32_t; __VA_ARGS__; } break;          \
-        case 2: { using V = uint16_t; __VA_ARGS__; } break;          \
-        default: { using V = uint8_t; __VA_ARGS__; } break;          \
-    }
 
 extern "C" {
 
@@ -169,34 +161,14 @@ pgk_status pgk_transpose_2d(const void* in, void* out, int rows, int cols, int i
     PGK_REQUIRE(in && out, "pgk_transpose_2d: null pointer");
     PGK_REQUIRE(rows >= 0 && cols >= 0, "pgk_transpose_2d: bad shape");
     if (!rows || !cols) return PGK_OK;
-    hipStream_t st = resolve_stream(s);
-    dim3 grid(ceil_div(cols, 64), ceil_div(rows, 64));
-    switch (itemsize) {
-        case 1: transpose2d_kernel<uint8_t><<<grid, 256, 0, st>>>((const uint8_t*)in, (uint8_t*)out, rows, cols); break;
-        case 2: transpose2d_kernel<uint16_t><<<grid, 256, 0, st>>>((const uint16_t*)in, (uint16_t*)out, rows, cols); break;
-        case 4: transpose2d_kernel<uint32_t><<<grid, 256, 0, st>>>((const uint32_t*)in, (uint32_t*)out, rows, cols); break;
-        case 8: transpose2d_kernel<uint2><<<grid, 256, 0, st>>>((const uint2*)in, (uint2*)out, rows, cols); break;
-        default: return set_error(PGK_ERR_INVALID, "pgk_transpose_2d: itemsize %d", itemsize);
-    }
-    PGK_LAUNCH_CHECK();
-    return PGK_OK;
+    return launch_transpose("pgk_transpose_2d", in, out, 1, rows, cols, itemsize, resolve_stream(s));
 }
 
 pgk_status pgk_transpose_batched(const void* in, void* out, int batch, int rows, int cols, int itemsize, pgk_stream s) {
     PGK_REQUIRE(in && out, "pgk_transpose_batched: null pointer");
-    PGK_REQUIRE(batch >= 0 && batch <= 65535 && rows >= 0 && cols >= 0, "pgk_transpose_batched: bad shape (batch %d <= 65535)", batch);
+    PGK_REQUIRE(transpose_batch_ok(batch) && rows >= 0 && cols >= 0, "pgk_transpose_batched: bad shape (batch %d <= 65535)", batch);
     if (!batch || !rows || !cols) return PGK_OK;
-    hipStream_t st = resolve_stream(s);
-    dim3 grid(ceil_div(cols, 64), ceil_div(rows, 64), batch);
-    switch (itemsize) {
-        case 1: transpose2d_kernel<uint8_t><<<grid, 256, 0, st>>>((const uint8_t*)in, (uint8_t*)out, rows, cols); break;
-        case 2: transpose2d_kernel<uint16_t><<<grid, 256, 0, st>>>((const uint16_t*)in, (uint16_t*)out, rows, cols); break;
-        case 4: transpose2d_kernel<uint32_t><<<grid, 256, 0, st>>>((const uint32_t*)in, (uint32_t*)out, rows, cols); break;
-        case 8: transpose2d_kernel<uint2><<<grid, 256, 0, st>>>((const uint2*)in, (uint2*)out, rows, cols); break;
-        default: return set_error(PGK_ERR_INVALID, "pgk_transpose_batched: itemsize %d", itemsize);
-    }
-    PGK_LAUNCH_CHECK();
-    return PGK_OK;
+    return launch_transpose("pgk_transpose_batched", in, out, batch, rows, cols, itemsize, resolve_stream(s));
 }
 
 pgk_status pgk_transpose_4d_0213(const void* in, void* out, int d0, int d1, int d2, int d3, int itemsize, pgk_stream s) {
@@ -214,10 +186,10 @@ pgk_status pgk_transpose_3d_021(const void* in, void* out, int d0, int d1, int d
     if (!d0 || !d1 || !d2) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     const size_t row_bytes = (size_t)d2 * itemsize;
-    const int w = pick_vec_bytes(row_bytes, {in, out});
+    const int w = pick_vec_bytes(row_bytes, addr_bits({in, out}));
     const int row_vecs = (int)(row_bytes / w);
     const int grid = cap_grid((size_t)d0 * d1 * row_vecs);
-    PGK_BY_VEC(w, row_map_kernel<0, V><<<grid, 256, 0, st>>>((const V*)in, (V*)out, d0, d1, 1, row_vecs));
+    PGK_BY_VEC(w, row_map_kernel<0, V><<<grid, TN_BLOCK, 0, st>>>((const V*)in, (V*)out, d0, d1, 1, row_vecs));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
 }
@@ -229,10 +201,10 @@ pgk_status pgk_repeat_interleave_axis1(const void* in, void* out, int d0, int d1
     if (!d0 || !d1 || !d2) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     const size_t row_bytes = (size_t)d2 * itemsize;
-    const int w = pick_vec_bytes(row_bytes, {in, out});
+    const int w = pick_vec_bytes(row_bytes, addr_bits({in, out}));
     const int row_vecs = (int)(row_bytes / w);
     const int grid = cap_grid((size_t)d0 * d1 * repeats * row_vecs);
-    PGK_BY_VEC(w, row_map_kernel<1, V><<<grid, 256, 0, st>>>((const V*)in, (V*)out, d0, d1, repeats, row_vecs));
+    PGK_BY_VEC(w, row_map_kernel<1, V><<<grid, TN_BLOCK, 0, st>>>((const V*)in, (V*)out, d0, d1, repeats, row_vecs));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
 }
@@ -242,18 +214,11 @@ pgk_status pgk_split_qkv_batch(const void* qkv, void* q, void* k, void* v, int r
     PGK_REQUIRE(qkv && q && k && v, "pgk_split_qkv_batch: null pointer");
     if (!rows) return PGK_OK;
     hipStream_t st = resolve_stream(s);
-    int w = 16;
-    for (; w > 1; w >>= 1) {
-        if (w < itemsize) { w = itemsize; break; }
-        const bool ok = ((size_t)q_dim * itemsize) % w == 0 && ((size_t)k_dim * itemsize) % w == 0 &&
-                        ((size_t)v_dim * itemsize) % w == 0 && (uintptr_t)qkv % w == 0 && (uintptr_t)q % w == 0 &&
-                        (uintptr_t)k % w == 0 && (uintptr_t)v % w == 0;
-        if (ok) break;
-    }
-    if (w < itemsize) w = itemsize;
+    const int w = split_qkv_vec_bytes(itemsize, split_qkv_bits((size_t)q_dim * itemsize, (size_t)k_dim * itemsize, (size_t)v_dim * itemsize,
+                                                               addr_bits({qkv, q, k, v})));
     const int qv = q_dim * itemsize / w, kv = k_dim * itemsize / w, vv = v_dim * itemsize / w;
     const int grid = cap_grid((size_t)rows * (qv + kv + vv));
-    PGK_BY_VEC(w, split_qkv_kernel<V><<<grid, 256, 0, st>>>((const V*)qkv, (V*)q, (V*)k, (V*)v, rows, qv, kv, vv));
+    PGK_BY_VEC(w, split_qkv_kernel<V><<<grid, TN_BLOCK, 0, st>>>((const V*)qkv, (V*)q, (V*)k, (V*)v, rows, qv, kv, vv));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
 }
@@ -265,9 +230,9 @@ pgk_status pgk_embedding_lookup(const void* table, void* out, int hidden, int it
     PGK_REQUIRE(ids || h_id >= 0, "pgk_embedding_lookup: negative token id %d", h_id);
     hipStream_t st = resolve_stream(s);
     const size_t row_bytes = (size_t)hidden * itemsize;
-    const int w = pick_vec_bytes(row_bytes, {table, out});
+    const int w = pick_vec_bytes(row_bytes, addr_bits({table, out}));
     const int row_vecs = (int)(row_bytes / w);
-    PGK_BY_VEC(w, gather_rows_kernel<V><<<n_ids, 256, 0, st>>>((const V*)table, (V*)out, ids, h_id, row_vecs));
+    PGK_BY_VEC(w, gather_rows_kernel<V><<<n_ids, TN_BLOCK, 0, st>>>((const V*)table, (V*)out, ids, h_id, row_vecs));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
 }
@@ -278,10 +243,10 @@ pgk_status pgk_slice_rows_range_ptr(const void* table, void* out, const int32_t*
     if (!count) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     const size_t row_bytes = (size_t)row_elems * itemsize;
-    const int w = pick_vec_bytes(row_bytes, {table, out});
+    const int w = pick_vec_bytes(row_bytes, addr_bits({table, out}));
     const int row_vecs = (int)(row_bytes / w);
     const int grid = cap_grid((size_t)count * row_vecs);
-    PGK_BY_VEC(w, slice_rows_kernel<V><<<grid, 256, 0, st>>>((const V*)table, (V*)out, start_buf, count, row_vecs));
+    PGK_BY_VEC(w, slice_rows_kernel<V><<<grid, TN_BLOCK, 0, st>>>((const V*)table, (V*)out, start_buf, count, row_vecs));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
 }
@@ -295,10 +260,10 @@ pgk_status pgk_kv_cache_write(const void* new_kv, void* cache, int seq, int hkv,
     if (!seq) return PGK_OK;
     hipStream_t st = resolve_stream(s);
     const size_t row_bytes = (size_t)d * itemsize;
-    const int w = pick_vec_bytes(row_bytes, {new_kv, cache});
+    const int w = pick_vec_bytes(row_bytes, addr_bits({new_kv, cache}));
     const int dvecs = (int)(row_bytes / w);
     const int grid = cap_grid((size_t)seq * hc * dvecs);
-    PGK_BY_VEC(w, kv_write_kernel<V><<<grid, 256, 0, st>>>((const V*)new_kv, (V*)cache, seq, hkv, hc, max_seq, dvecs,
+    PGK_BY_VEC(w, kv_write_kernel<V><<<grid, TN_BLOCK, 0, st>>>((const V*)new_kv, (V*)cache, seq, hkv, hc, max_seq, dvecs,
                                                           h_pos, pos_buf));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
@@ -308,10 +273,78 @@ pgk_status pgk_argmax(const void* x, int rows, int n, pgk_dtype dt, int32_t* out
     PGK_REQUIRE(x && out_idx, "pgk_argmax: null pointer");
     PGK_REQUIRE(rows >= 1 && n >= 1, "pgk_argmax: bad shape [%d,%d]", rows, n);
     hipStream_t st = resolve_stream(s);
-    const int block = n >= 16384 ? 1024 : 256;
+    const int block = argmax_block(n);
     PGK_DISPATCH_FLOAT(dt, "pgk_argmax", argmax_kernel<T><<<rows, block, 0, st>>>((const T*)x, n, out_idx));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
+}
+
+// The kernel instantiation a byte mover takes and the number of blocks it launches, as the launchers of this file and the
+// helpers of ops_paged.hip decide them (tests assert both; see DESIGN.md "Byte-mover dispatch leaves").  Built from the functions
+// of tensor_plan.h that those launchers call; needs no device.  The work is `batch * rows` rows of `row_bytes` bytes:
+//   transpose_2d / transpose_batched   [batch] matrices of `rows` x (row_bytes / itemsize)            -> tile64
+//   transpose_3d_021, repeat_interleave, slice_rows, kv_cache_write, embedding_lookup, scatter_last_logits
+//                                      output rows (kv_cache_write: seq * cache heads)                 -> vec16 .. vec1
+//   split_qkv                          rows of q + k + v bytes; low_bits also carries q_bytes | k_bytes | v_bytes
+//   paged_cache_write                  tokens * kv heads rows of head_dim * itemsize bytes             -> vec16
+//   argmax                             rows of n = row_bytes / itemsize elements                       -> block256 / block1024
+// `low_bits`: the OR of the addresses the launcher tests.  NULL / -1 (and pgk_last_error) for an op name or shape that the
+// entry point itself rejects, and for an empty call, which launches nothing.
+static int tensor_op_query(const char* who, const char* op, size_t batch, size_t rows, size_t row_bytes, int itemsize, unsigned low_bits,
+                           const char** leaf) {
+    const auto fail = [&](const char* why) {
+        set_error(PGK_ERR_INVALID, "%s: %s (op=%s batch=%zu rows=%zu row_bytes=%zu itemsize=%d)", who, why, op ? op : "NULL", batch, rows,
+                  row_bytes, itemsize);
+        return -1;
+    };
+    if (!op) return fail("null op");
+    if (itemsize < 1 || batch < 1 || rows < 1 || row_bytes < 1 || row_bytes % (size_t)itemsize) return fail("bad shape");
+    if (batch > 0x7fffffffu || rows > 0x7fffffffu || row_bytes > 0x7fffffffu || batch * rows > 0x7fffffffu) return fail("bad shape");
+    const std::string o(op);
+    const unsigned bits = low_bits & 15u;
+    const size_t nrows = batch * rows;
+    if (o == "transpose_2d" || o == "transpose_batched") {
+        if (itemsize != 1 && itemsize != 2 && itemsize != 4 && itemsize != 8) return fail("itemsize must be 1, 2, 4 or 8");
+        if (o == "transpose_2d" ? batch != 1 : !transpose_batch_ok((long long)batch)) return fail("batch beyond 65535 (transpose_2d: 1)");
+        *leaf = "tile64";
+        return transpose_tiles_x((int)(row_bytes / itemsize)) * transpose_tiles_y((int)rows) * (int)batch;
+    }
+    if (o == "transpose_3d_021" || o == "repeat_interleave" || o == "slice_rows" || o == "kv_cache_write") {
+        const int w = pick_vec_bytes(row_bytes, bits);
+        *leaf = vec_leaf(w);
+        return cap_grid(nrows * (row_bytes / w));
+    }
+    if (o == "embedding_lookup" || o == "scatter_last_logits") {      // a block per output row
+        *leaf = vec_leaf(pick_vec_bytes(row_bytes, bits));
+        return (int)nrows;
+    }
+    if (o == "split_qkv") {
+        const int w = split_qkv_vec_bytes(itemsize, bits);
+        *leaf = vec_leaf(w);
+        return cap_grid(nrows * (row_bytes / w));
+    }
+    if (o == "paged_cache_write") {
+        if (!paged_write_row_ok(row_bytes)) return fail("rows must be whole 16-byte chunks");
+        *leaf = "vec16";
+        return paged_write_grid(nrows, row_bytes);
+    }
+    if (o == "argmax") {
+        if (itemsize != 2 && itemsize != 4) return fail("float32, float16 or bfloat16 rows");
+        *leaf = argmax_block((int)(row_bytes / itemsize)) == 1024 ? "block1024" : "block256";
+        return (int)nrows;
+    }
+    return fail("op must be one of transpose_2d, transpose_batched, transpose_3d_021, repeat_interleave, split_qkv, embedding_lookup, "
+                "slice_rows, kv_cache_write, argmax, paged_cache_write, scatter_last_logits");
+}
+
+const char* pgk_tensor_op_plan(const char* op, size_t batch, size_t rows, size_t row_bytes, int itemsize, unsigned low_bits) {
+    const char* leaf = nullptr;
+    return tensor_op_query("pgk_tensor_op_plan", op, batch, rows, row_bytes, itemsize, low_bits, &leaf) < 0 ? nullptr : leaf;
+}
+
+int pgk_tensor_op_grid(const char* op, size_t batch, size_t rows, size_t row_bytes, int itemsize, unsigned low_bits) {
+    const char* leaf = nullptr;
+    return tensor_op_query("pgk_tensor_op_grid", op, batch, rows, row_bytes, itemsize, low_bits, &leaf);
 }
 
 }  // extern "C"

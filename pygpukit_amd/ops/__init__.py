@@ -24,7 +24,7 @@ from pygpukit_amd.ops.nn import (fa3_fp8_available, get_sm_version, quantize_fp8
                                 sdpa_causal_strided, sdpa_noncausal, sdpa_noncausal_strided, sigmoid, silu, slice_rows_range_ptr, split_qkv_batch, swiglu, tanh,
                                 embed_token_position_ptr, ln_linear, ln_linear_plan, ln_linear_qkv_cache_ptr, group_norm, group_norm_silu)
 from pygpukit_amd.ops.nn import relbias_plan, relpos_bias_table, relpos_bucket, relpos_compute_bias, sdpa_relbias, sdpa_relbias_strided
-from pygpukit_amd.ops.plan import BASE_PLAN_OPS, base_op_grid, base_op_plan
+from pygpukit_amd.ops.plan import BASE_PLAN_OPS, TENSOR_PLAN_OPS, base_op_grid, base_op_plan, tensor_op_grid, tensor_op_plan
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis
 from pygpukit_amd.ops.unary import abs, cos, exp, log, neg, relu, rsqrt, sin, sqrt
 from pygpukit_amd.ops.paged import (allocate_kv_cache, argmax_sample, check_eos, compute_cumsum, copy_to_paged_cache, gather_embeddings,

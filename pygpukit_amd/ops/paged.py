@@ -89,12 +89,15 @@ def gather_embeddings(token_ids: GPUArray, embeddings: GPUArray, total_tokens: i
 
 
 def scatter_last_token_logits(logits: GPUArray, seq_start_positions: GPUArray, seq_lens: GPUArray, batch_size: int,
-                              vocab_size: int) -> GPUArray:
+                              vocab_size: int, *, out: GPUArray | None = None) -> GPUArray:
+    """logits [batch_tokens, vocab] -> [batch, vocab]: row seq_start[b] + seq_lens[b] - 1 of each sequence (lengths >= 1).  Any
+    vocabulary and any view: the copy uses the widest of 16-, 8-, 4-, 2- or 1-byte vectors that divides a row's byte size and
+    both addresses (50257 float16 words: 2 bytes; ops.tensor_op_plan("scatter_last_logits", ...) names it)."""
     if logits.ndim != 2 or logits.shape[1] != vocab_size:
         raise ValueError(f"scatter_last_token_logits: logits must be [batch_tokens, {vocab_size}]")
     if seq_start_positions.dtype != int32 or seq_lens.dtype != int32:
         raise ValueError("scatter_last_token_logits: positions / lengths must be int32")
-    out = GPUArray((batch_size, vocab_size), logits.dtype)
+    out = check_out(out, (batch_size, vocab_size), logits.dtype, "scatter_last_token_logits")
     call("pgk_scatter_last_token_logits", logits._p, out._p, seq_start_positions._p, seq_lens._p, batch_size, vocab_size,
          logits.itemsize, None)
     return out

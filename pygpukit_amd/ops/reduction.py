@@ -10,7 +10,8 @@ from pygpukit_amd.ops._common import call, validate_float
 
 
 def argmax_rows(a: GPUArray, *, out: GPUArray | None = None) -> GPUArray:
-    """Index of the maximum of each row of a 1-D or 2-D array -> int32 [rows]; ties -> lowest index."""
+    """Index of the maximum of each row of a 1-D or 2-D array -> int32 [rows]; ties -> lowest index (+0.0 and -0.0 tie).
+    NaN is skipped, unlike np.argmax: it never wins, and a row of nothing but NaN gives 0, as does a row of -inf."""
     validate_float(a, "argmax")
     rows, n = (1, a.shape[0]) if a.ndim == 1 else (a.shape[0], a.size // a.shape[0])
     o = out if out is not None else GPUArray((rows,), int32)
@@ -19,7 +20,8 @@ def argmax_rows(a: GPUArray, *, out: GPUArray | None = None) -> GPUArray:
 
 
 def argmax(a: GPUArray) -> GPUArray:
-    """Flat index of the maximum -> int64 [1] on the device (reduction.py:249-268; np.argmax semantics, ties -> lowest)."""
+    """Flat index of the maximum -> int64 [1] on the device (reduction.py:249-268; np.argmax semantics, ties -> lowest).
+    NaN is skipped, unlike np.argmax: it never wins, and an array of nothing but NaN gives 0."""
     validate_float(a, "argmax")
     o = GPUArray((1,), int32)
     call("pgk_argmax", a._p, 1, a.size, a.dtype.code, o._p, None)
