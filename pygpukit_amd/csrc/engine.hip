@@ -1052,11 +1052,11 @@ pgk_status pgk_engine_linear_plan(pgk_engine eh, int batch, int max_position, in
                       af.direct ? "direct" : (tiled ? "normrows" : "none"));
             auto bat = [&](const char* name, bool wfp8, bool logits, bool have_copy, int N, int K) {
                 const char* wn = wfp8 ? "fp8" : "bf16";
-                if (tiled) {             // launch_batched_tiled / launch_batched_mt
+                if (tiled) {             // launch_batched_tiled
                     const int rows = mt_rows_per_group(N, logits);
                     ok = ok && emit("proj name=%s kernel=batched_mt w=%s rows=%d mp=0 tiles=%d copy=%d grid=%d n=%d k=%d\n", name, wn, rows, mt_tiles(M),
                                     batched_reads_copy(wfp8, rows, have_copy) ? 1 : 0, logits ? batched_lm_blocks(V) : ceil_div(N, rows), N, K);
-                } else if (batched_is_reg(K)) {   // launch_batched / launch_batched_reg
+                } else if (batched_is_reg(K)) {   // launch_batched: the register-fragment kernel
                     const int rows = batched_reg_rows(N, logits);
                     ok = ok && emit("proj name=%s kernel=batched_reg w=%s rows=%d mp=0 tiles=1 copy=%d grid=%d n=%d k=%d\n", name, wn, rows,
                                     batched_reads_copy(wfp8, rows, have_copy) ? 1 : 0, logits ? batched_lm_blocks(V) : ceil_div(N, rows), N, K);

@@ -1,5 +1,6 @@
 // Batched decode projections on MFMA (3..64 sequences per launch): kernels in engine_batched.hip.h, run-time dispatch here.
-// Its own translation unit so that the ~150 template instances compile beside engine.hip instead of inside it (engine_prefill.hip: the same for the prefill).
+// Its own translation unit so that the 247 kernels (76 batched_reg_kernel, 14 batched_mfma_kernel, 156 batched_mt_kernel instances and the
+// row norm below) compile beside engine.hip instead of inside it (engine_prefill.hip: the same for the prefill).
 
 #include <cstdlib>
 #include <type_traits>
@@ -70,28 +71,30 @@ pgk_status norm_rows_bf16(const float* h, const bf16* gamma, bf16* x16, int M, i
 
 template <class WT>
 static pgk_status batched_proj_t(int pro, int epi, const FusedArgs& a, int M, hipStream_t st, int nblk) {
+    // What the engine's steps launch (decode_chunk_batched / decode_chunk_packed, engine.hip) and nothing else: the lm_head is bf16 in
+    // every weight format; 3..16 sequences run norm -> store (qkv) / SwiGLU (gate_up) / logits and plain -> residual (o, down).
+    constexpr bool BF16 = std::is_same<WT, bf16>::value;
     if (M > 16) {
         PGK_REQUIRE(pro == PRO_PLAIN, "batched_proj: more than 16 sequences take pre-normalised bf16 rows (PRO_PLAIN)");
         switch (epi) {
             case EPI_STORE: return launch_batched_tiled<WT, EPI_STORE>(a, M, st);
             case EPI_RESID: return launch_batched_tiled<WT, EPI_RESID>(a, M, st);
             case EPI_SWIGLU: return launch_batched_tiled<WT, EPI_SWIGLU>(a, M, st);
-            case EPI_LOGITS: return launch_batched_tiled<WT, EPI_LOGITS>(a, M, st, nblk);
+            case EPI_LOGITS:
+                if constexpr (BF16) return launch_batched_tiled<WT, EPI_LOGITS>(a, M, st, nblk);
+                break;
+            default: return set_error(PGK_ERR_INVALID, "batched_proj: epilogue %d", epi);
         }
-        return set_error(PGK_ERR_INVALID, "batched_proj: epilogue %d", epi);
-    }
-    if (pro == PRO_NORM) {
+    } else if (pro == PRO_NORM) {
         switch (epi) {
             case EPI_STORE: return launch_batched<WT, PRO_NORM, EPI_STORE>(a, M, st);
             case EPI_SWIGLU: return launch_batched<WT, PRO_NORM, EPI_SWIGLU>(a, M, st);
-            case EPI_LOGITS: return launch_batched<WT, PRO_NORM, EPI_LOGITS>(a, M, st, nblk);
+            case EPI_LOGITS:
+                if constexpr (BF16) return launch_batched<WT, PRO_NORM, EPI_LOGITS>(a, M, st, nblk);
+                break;
         }
-    } else if (pro == PRO_PLAIN) {
-        switch (epi) {
-            case EPI_STORE: return launch_batched<WT, PRO_PLAIN, EPI_STORE>(a, M, st);
-            case EPI_RESID: return launch_batched<WT, PRO_PLAIN, EPI_RESID>(a, M, st);
-            case EPI_SWIGLU: return launch_batched<WT, PRO_PLAIN, EPI_SWIGLU>(a, M, st);
-        }
+    } else if (pro == PRO_PLAIN && epi == EPI_RESID) {
+        return launch_batched<WT, PRO_PLAIN, EPI_RESID>(a, M, st);
     }
     return set_error(PGK_ERR_INVALID, "batched_proj: prologue %d with epilogue %d is not instantiated", pro, epi);
 }

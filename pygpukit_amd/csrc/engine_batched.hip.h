@@ -13,42 +13,34 @@
 //   (store / residual add / SiLU(g)*u / logits + per-workgroup argmax partials, lowest index on ties).
 // fp8 weights: 8 codes per lane per step, widened to bf16 with the block scale in registers (as ops_wsgemm.hip).
 
-// MP: activation rows held in LDS (8 or 16).  S: 32-k steps per wave preloaded into registers (K = 128 S when it is one of
-// the instantiated 8 / 16 / 24; any further steps stream through a plain loop).
-template <class WT, int PRO, int EPI, int MP, int S>
+// ---- pieces the three kernels share ----
+// fp8 weights: the scale of the 128 x 128 block that holds W[row][k]
+__device__ __forceinline__ float w_block_scale(const bf16* wscale, size_t row, int K, int k) { return to_f(wscale[(row >> 7) * (size_t)(K >> 7) + (k >> 7)]); }
+
+// the B operand of one weight fragment: fp8 codes (.x / .y) widened to bf16 with their block scale, bf16 as loaded
+template <class WT>
+__device__ __forceinline__ uint4 w_frag_bf16(const uint4& wv, const float& wsc) {
+    if constexpr (std::is_same<WT, fp8e4m3>::value) {
+        return fp8x8_to_bf16x8(make_uint2(wv.x, wv.y), wsc);
+    } else {
+        return wv;
+    }
+}
+
+// LDS-image kernel: any K that is a multiple of 128 (launch_batched sends K = 128 x {8, 16, 24, 32} to the register-resident variant
+// below).  MP: activation rows held in LDS (8 or 16).  A wave streams its K quarter of the group's weights (steps = K / 128 k-steps)
+// through a plain loop.
+template <class WT, int PRO, int EPI, int MP>
 __global__ __launch_bounds__(256) void batched_mfma_kernel(unsigned long long* tl, FusedArgs a, int M, int steps /* K / 128 per wave */, int nblk_logits) {
     const TLStamp tls(tl);
     constexpr bool FP8 = std::is_same<WT, fp8e4m3>::value;
     constexpr int NT = (EPI == EPI_SWIGLU) ? 2 : 1;       // weight row groups per workgroup
-    constexpr int MAXS = S > 0 ? S : 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // x image [K/8][MP] x 16 B | partial tiles
     __shared__ float s_ss[4][16];
     const int K = a.K, N = a.N;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, q = lane >> 4, l15 = lane & 15;
     const int ngroups = (N + 15) >> 4;                     // 16-row groups; a workgroup takes groups blockIdx.x, + gridDim.x, ...
     const int kw0 = wid * steps * 32;                      // first k of this wave
-    uint4 wv[NT][MAXS];
-    float wsc[NT][MAXS];
-    auto load_w = [&](int n0) {
-        const int nrow = min(n0 + l15, N - 1);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const size_t row = (size_t)(t == 0 ? nrow : N + nrow);
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                const int k = kw0 + s * 32 + 8 * q;
-                if constexpr (FP8) {
-                    const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(a.w) + row * K + k);
-                    wv[t][s] = make_uint4(v.x, v.y, 0, 0);
-                    wsc[t][s] = to_f(a.wscale[(row >> 7) * (size_t)(K >> 7) + (k >> 7)]);
-                } else {
-                    wv[t][s] = load_nt16(reinterpret_cast<const bf16*>(a.w) + row * K + k);
-                }
-            }
-        }
-    };
-    // ---- weight loads of the first group's K quarter, all issued before the prologue touches the activations ----
-    load_w(blockIdx.x * 16);
     const int em = tid >> 4, en = tid & 15;                // epilogue element of this thread: (row em, column n0 + en)
 
     // ---- prologue: M rows -> bf16 LDS image, chunk c (8 k) of row m at (c * MP + m) * 16 ----
@@ -127,32 +119,16 @@ __global__ __launch_bounds__(256) void batched_mfma_kernel(unsigned long long* t
     // ---- body: one 16-row group per trip; the LDS image of the activations stays, the partial tiles have their own area ----
     float* red = reinterpret_cast<float*>(smem + (size_t)nchunk * MP * 16);   // [NT][4 waves][16 m][16 n]
     const int am = l15 & (MP - 1);
-    auto bfrag = [&](int t, int s) -> uint4 {
-        if constexpr (FP8) {
-            return fp8x8_to_bf16x8(make_uint2(wv[t][s].x, wv[t][s].y), wsc[t][s]);
-        } else {
-            return wv[t][s];
-        }
-    };
     float bv = -INFINITY;          // EPI_LOGITS: best of this thread's elements over the workgroup's groups
     int bi = 0x7FFFFFFF;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
         const int n0 = g * 16;
-        if (g != (int)blockIdx.x) load_w(n0);
         float resv = 0.f;
         if constexpr (EPI == EPI_RESID) resv = a.res[(size_t)min(em, M - 1) * a.ld_out + min(n0 + en, N - 1)];
         f32x4_t acc[NT];
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const int kc = (kw0 >> 3) + s * 4 + q;
-            const uint4 af = *reinterpret_cast<const uint4*>(smem + ((size_t)kc * MP + am) * 16);
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af), __builtin_bit_cast(bf16x8_t, bfrag(t, s)), acc[t], 0, 0, 0);
-        }
-        for (int s = S; s < steps; ++s) {          // steps beyond the preloaded ones stream through a plain loop
+        for (int s = 0; s < steps; ++s) {
             const int k = kw0 + s * 32 + 8 * q;
             const uint4 af = *reinterpret_cast<const uint4*>(smem + ((size_t)((k >> 3)) * MP + am) * 16);
             const int nrow = min(n0 + l15, N - 1);
@@ -162,7 +138,7 @@ __global__ __launch_bounds__(256) void batched_mfma_kernel(unsigned long long* t
                 uint4 b;
                 if constexpr (FP8) {
                     const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(a.w) + row * K + k);
-                    const float sc = to_f(a.wscale[(row >> 7) * (size_t)(K >> 7) + (k >> 7)]);
+                    const float sc = w_block_scale(a.wscale, row, K, k);
                     b = fp8x8_to_bf16x8(v, sc);
                 } else {
                     b = load_nt16(reinterpret_cast<const bf16*>(a.w) + row * K + k);
@@ -274,7 +250,7 @@ __global__ __launch_bounds__(256) void batched_reg_kernel(unsigned long long* tl
                     if constexpr (FP8) {
                         const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(w_) + row * K + k);
                         wv[t][s] = make_uint4(v.x, v.y, 0, 0);
-                        wsc[t][s] = to_f(a.wscale[(row >> 7) * (size_t)(K >> 7) + (k >> 7)]);
+                        wsc[t][s] = w_block_scale(a.wscale, row, K, k);
                     } else {
                         wv[t][s] = load_nt16(reinterpret_cast<const bf16*>(w_) + row * K + k);
                     }
@@ -290,14 +266,13 @@ __global__ __launch_bounds__(256) void batched_reg_kernel(unsigned long long* tl
     // prologue started when the last weight byte had landed - the batch-1 kernels' lesson).
     const float* src = x_ + (size_t)min(l15, M - 1) * K + kw0 + 8 * q;
     uint4 af[S];
-    constexpr bool HOLD_FIRST = PRO == PRO_NORM && S <= 8;      // raw rows held in registers across the reduction
-    if constexpr (!HOLD_FIRST) load_w(blockIdx.x * RPG);        // (deep K: the rows are re-read after the barrier anyway)
+    constexpr bool HOLD = PRO == PRO_NORM && S <= 8;            // raw rows held in registers across the reduction
+    if constexpr (!HOLD) load_w(blockIdx.x * RPG);        // (deep K: the rows are re-read after the barrier anyway)
     auto pack8 = [](const float4& u, const float4& v, float inv, const float* g) {
         return make_uint4(pack_bf16x2(u.x * inv * g[0], u.y * inv * g[1]), pack_bf16x2(u.z * inv * g[2], u.w * inv * g[3]),
                           pack_bf16x2(v.x * inv * g[4], v.y * inv * g[5]), pack_bf16x2(v.z * inv * g[6], v.w * inv * g[7]));
     };
     if constexpr (PRO == PRO_NORM) {
-        constexpr bool HOLD = S <= 8;                      // raw rows stay in registers across the reduction
         float4 r0[HOLD ? S : 1], r1[HOLD ? S : 1];
         float ss = 0.f;
         if constexpr (HOLD) {
@@ -353,13 +328,7 @@ __global__ __launch_bounds__(256) void batched_reg_kernel(unsigned long long* tl
         for (int s = 0; s < S; ++s) af[s] = make_uint4(0, 0, 0, 0);      // rows past the batch contribute nothing
     }
 
-    auto bfrag = [&](int t, int s) -> uint4 {
-        if constexpr (FP8) {
-            return fp8x8_to_bf16x8(make_uint2(wv[t][s].x, wv[t][s].y), wsc[t][s]);
-        } else {
-            return wv[t][s];
-        }
-    };
+    auto bfrag = [&](int t, int s) -> uint4 { return w_frag_bf16<WT>(wv[t][s], wsc[t][s]); };   // (a binder: profiles/batched_share_isa.txt)
     float bv = -INFINITY;
     int bi = 0x7FFFFFFF;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
@@ -476,7 +445,7 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
                     if constexpr (FP8) {
                         const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(a.w) + row * K + k);
                         wv[t][s] = make_uint4(v.x, v.y, 0, 0);
-                        wsc[t][s] = to_f(a.wscale[(row >> 7) * (size_t)(K >> 7) + (k >> 7)]);
+                        wsc[t][s] = w_block_scale(a.wscale, row, K, k);
                     } else {
                         wv[t][s] = load_nt16(reinterpret_cast<const bf16*>(a.w) + row * K + k);
                     }
@@ -500,13 +469,7 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
             for (int t = 0; t < MT; ++t) af[buf][j][t] = *reinterpret_cast<const uint4*>(xrow[t] + (c * CH + j) * 32);
     };
     if constexpr (NCH == 1) load_a(0, 0);
-    auto bfrag = [&](int t, int s) -> uint4 {
-        if constexpr (FP8) {
-            return fp8x8_to_bf16x8(make_uint2(wv[t][s].x, wv[t][s].y), wsc[t][s]);
-        } else {
-            return wv[t][s];
-        }
-    };
+    auto bfrag = [&](int t, int s) -> uint4 { return w_frag_bf16<WT>(wv[t][s], wsc[t][s]); };   // (a binder: profiles/batched_share_isa.txt)
     float bv[MT];
     int bi[MT];
 #pragma unroll
@@ -602,93 +565,86 @@ __global__ __launch_bounds__(256) void batched_mt_kernel(unsigned long long* tl,
     tls.end();
 }
 
-template <class WT, int EPI, int S>
-static pgk_status launch_batched_mt(const FusedArgs& a, int M, hipStream_t st, int nblk_logits) {
-    const int rpg = mt_rows_per_group(a.N, EPI == EPI_LOGITS);   // engine_state.hip.h
-    const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ceil_div(a.N, rpg);
-    const bool two = mt_tiles(M) == 2;
-    hipError_t he = hipSuccess;
-    if constexpr (EPI == EPI_LOGITS) {
-        if (two) he = launch_k(batched_mt_kernel<WT, EPI, S, 16, 2>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
-        else he = launch_k(batched_mt_kernel<WT, EPI, S, 16, 4>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
-    } else {
-        if (rpg == 16 && two) he = launch_k(batched_mt_kernel<WT, EPI, S, 16, 2>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
-        else if (rpg == 16) he = launch_k(batched_mt_kernel<WT, EPI, S, 16, 4>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
-        else if (two) he = launch_k(batched_mt_kernel<WT, EPI, S, 4, 2>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
-        else he = launch_k(batched_mt_kernel<WT, EPI, S, 4, 4>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
-    }
-    PGK_CHECK_HIP(he);
-    return PGK_OK;
+// ---------------------------------------------------------------------------------------------------------------------
+// Launchers.  Only what the engine's steps reach is instantiated (decode_chunk_batched / decode_chunk_packed, engine.hip; the
+// prologue x epilogue pairs and the bf16-only lm_head: batched_proj_t, engine_batched.hip).
+
+// Run-time value to compile-time constant: the result of f(std::integral_constant<int, V>) for the V among Vs that equals v; false when
+// none does.
+template <int... Vs, class F>
+static bool with_constant(int v, F f) { return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...); }
+// ... for the rows per workgroup: the lm_head's are always 16 (batched_reg_rows / mt_rows_per_group, engine_state.hip.h)
+template <int EPI, int... Rows, class F>
+static bool with_rows(int rpg, F f) {
+    if constexpr (EPI == EPI_LOGITS) return with_constant<16>(rpg, f);
+    else return with_constant<Rows...>(rpg, f);
 }
 
 template <class WT, int EPI>
 static pgk_status launch_batched_tiled(const FusedArgs& a, int M, hipStream_t st, int nblk_logits = 0) {
     PGK_REQUIRE(a.xin16 != nullptr, "batched decode projection: %d sequences need bf16 input rows", M);
     PGK_REQUIRE(M > 16 && M <= 64, "batched decode projection: tiled kernels take 17..64 sequences, got %d", M);
-    switch (a.K / 128) {
-        case 2: return launch_batched_mt<WT, EPI, 2>(a, M, st, nblk_logits);
-        case 4: return launch_batched_mt<WT, EPI, 4>(a, M, st, nblk_logits);
-        case 8: return launch_batched_mt<WT, EPI, 8>(a, M, st, nblk_logits);
-        case 16: return launch_batched_mt<WT, EPI, 16>(a, M, st, nblk_logits);
-        case 24: return launch_batched_mt<WT, EPI, 24>(a, M, st, nblk_logits);
-        case 32: return launch_batched_mt<WT, EPI, 32>(a, M, st, nblk_logits);
-    }
-    return set_error(PGK_ERR_UNSUPPORTED, "batched decode projection: K=%d is not 128 x {2,4,8,16,24,32}", a.K);
-}
-
-template <class WT, int PRO, int EPI, int S>
-static pgk_status launch_batched_reg(const FusedArgs& a, int M, hipStream_t st, int nblk_logits) {
-    const int rpg = batched_reg_rows(a.N, EPI == EPI_LOGITS);   // engine_state.hip.h
+    const int rpg = mt_rows_per_group(a.N, EPI == EPI_LOGITS);   // engine_state.hip.h
     const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ceil_div(a.N, rpg);
-    const float* x = (PRO == PRO_NORM) ? a.h : a.xin;
-    hipError_t he;
-    if (rpg == 16) he = launch_k(batched_reg_kernel<WT, PRO, EPI, S, 16>, dim3(grid), dim3(256), 0, st, a.w, a.wp, x, a.gamma, a.N, a.K, M, nblk_logits, a);
-    else if (rpg == 8) he = launch_k(batched_reg_kernel<WT, PRO, EPI, S, 8>, dim3(grid), dim3(256), 0, st, a.w, a.wp, x, a.gamma, a.N, a.K, M, nblk_logits, a);
-    else he = launch_k(batched_reg_kernel<WT, PRO, EPI, S, 4>, dim3(grid), dim3(256), 0, st, a.w, a.wp, x, a.gamma, a.N, a.K, M, nblk_logits, a);
+    hipError_t he = hipSuccess;
+    bool found = false;      // all three values matched an instantiated one
+    const bool width = with_constant<2, 4, 8, 16, 24, 32>(a.K / 128, [&](auto s) {
+        found = with_rows<EPI, 16, 4>(rpg, [&](auto r) {
+            return with_constant<2, 4>(mt_tiles(M), [&](auto t) {
+                he = launch_k(batched_mt_kernel<WT, EPI, decltype(s)::value, decltype(r)::value, decltype(t)::value>, dim3(grid), dim3(256), 0, st, a, M, nblk_logits);
+                return true;
+            });
+        });
+        return true;
+    });
+    if (!width) return set_error(PGK_ERR_UNSUPPORTED, "batched decode projection: K=%d is not 128 x {2,4,8,16,24,32}", a.K);
+    if (!found) return set_error(PGK_ERR_INVALID, "batched decode projection: %d rows per workgroup with %d M tiles is not instantiated", rpg, mt_tiles(M));
     PGK_CHECK_HIP(he);
     return PGK_OK;
 }
 
-template <class WT, int PRO, int EPI, int MP, int S>
-static pgk_status launch_batched_s(const FusedArgs& a, int M, int steps, int grid, size_t lds, hipStream_t st, int nblk_logits) {
-    static bool done = false;
+template <class WT, int PRO, int EPI, int MP>
+static pgk_status launch_batched_lds(const FusedArgs& a, int M, int steps, int grid, size_t lds, hipStream_t st, int nblk_logits) {
+    static bool done = false;      // once per instantiation
     if (lds > 48 * 1024 && !done) {
-        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&batched_mfma_kernel<WT, PRO, EPI, MP, S>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
+        PGK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&batched_mfma_kernel<WT, PRO, EPI, MP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          160 * 1024 - 2048));
         done = true;
     }
-    PGK_CHECK_HIP(launch_k(batched_mfma_kernel<WT, PRO, EPI, MP, S>, dim3(grid), dim3(256), lds, st, a, M, steps, nblk_logits));
+    PGK_CHECK_HIP(launch_k(batched_mfma_kernel<WT, PRO, EPI, MP>, dim3(grid), dim3(256), lds, st, a, M, steps, nblk_logits));
     return PGK_OK;
 }
 
 template <class WT, int PRO, int EPI>
 static pgk_status launch_batched(const FusedArgs& a, int M, hipStream_t st, int nblk_logits = 0) {
     PGK_REQUIRE(a.K % 128 == 0 && M >= 1 && M <= 16, "batched decode projection: K=%d must be a multiple of 128 and M=%d in [1,16]", a.K, M);
-    const int steps = a.K / 128, ngroups = ceil_div(a.N, 16);
+    const int steps = a.K / 128;
     // register-resident activations at the instantiated widths; the LDS-image kernel below for every other K
     if (batched_is_reg(a.K)) {   // engine_state.hip.h
-        if (steps == 8) return launch_batched_reg<WT, PRO, EPI, 8>(a, M, st, nblk_logits);
-        if (steps == 16) return launch_batched_reg<WT, PRO, EPI, 16>(a, M, st, nblk_logits);
-        if (steps == 24) return launch_batched_reg<WT, PRO, EPI, 24>(a, M, st, nblk_logits);
-        if (steps == 32) return launch_batched_reg<WT, PRO, EPI, 32>(a, M, st, nblk_logits);
-        return set_error(PGK_ERR_UNSUPPORTED, "batched decode projection: K=%d has no register-fragment kernel", a.K);
+        const int rpg = batched_reg_rows(a.N, EPI == EPI_LOGITS);
+        const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ceil_div(a.N, rpg);
+        const float* x = (PRO == PRO_NORM) ? a.h : a.xin;
+        hipError_t he = hipSuccess;
+        bool found = false;      // both values matched an instantiated one
+        const bool width = with_constant<8, 16, 24, 32>(steps, [&](auto s) {
+            found = with_rows<EPI, 16, 8, 4>(rpg, [&](auto r) {
+                he = launch_k(batched_reg_kernel<WT, PRO, EPI, decltype(s)::value, decltype(r)::value>, dim3(grid), dim3(256), 0, st, a.w, a.wp, x, a.gamma, a.N, a.K, M,
+                              nblk_logits, a);
+                return true;
+            });
+            return true;
+        });
+        if (!width) return set_error(PGK_ERR_UNSUPPORTED, "batched decode projection: K=%d has no register-fragment kernel", a.K);
+        if (!found) return set_error(PGK_ERR_INVALID, "batched decode projection: %d rows per workgroup is not instantiated", rpg);
+        PGK_CHECK_HIP(he);
+        return PGK_OK;
     }
     // the prologue (RMSNorm of the M rows) is per workgroup: large N (lm_head) runs 2048 workgroups over several groups each
-    const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ngroups;
+    const int grid = (EPI == EPI_LOGITS) ? nblk_logits : ceil_div(a.N, 16);
     constexpr int NT = (EPI == EPI_SWIGLU) ? 2 : 1;
     const int mp = M <= 8 ? 8 : 16;
     const size_t lds = (size_t)(a.K / 8) * mp * 16 + (size_t)NT * 4 * 256 * 4;
     PGK_REQUIRE(lds <= 158 * 1024, "batched decode projection: K=%d does not fit the LDS image", a.K);
-#define PGK_BS(MPV, SV) return launch_batched_s<WT, PRO, EPI, MPV, SV>(a, M, steps, grid, lds, st, nblk_logits);
-    if (mp == 8) {
-        if (steps == 8) PGK_BS(8, 8)
-        if (steps == 16) PGK_BS(8, 16)
-        if (steps == 24) PGK_BS(8, 24)
-        PGK_BS(8, 0)
-    }
-    if (steps == 8) PGK_BS(16, 8)
-    if (steps == 16) PGK_BS(16, 16)
-    if (steps == 24) PGK_BS(16, 24)
-    PGK_BS(16, 0)
-#undef PGK_BS
+    return mp == 8 ? launch_batched_lds<WT, PRO, EPI, 8>(a, M, steps, grid, lds, st, nblk_logits)
+                   : launch_batched_lds<WT, PRO, EPI, 16>(a, M, steps, grid, lds, st, nblk_logits);
 }

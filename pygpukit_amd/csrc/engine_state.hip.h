@@ -210,7 +210,8 @@ inline int gemv_grid(int R, bool swiglu, int n_out, int force_grid) {
 }
 
 // engine_batched.hip.h, 3..16 sequences: register-resident activation fragments at the instantiated widths K = 128 x
-// {8, 16, 24, 32} (batched_reg_kernel), the LDS-image kernel (batched_mfma_kernel) for every other K
+// {8, 16, 24, 32} (batched_reg_kernel); every other multiple of 128 streams through the LDS-image kernel (batched_mfma_kernel),
+// which is therefore never launched at those four widths
 inline bool batched_is_reg(int K) { const int s = K / 128; return s == 8 || s == 16 || s == 24 || s == 32; }
 // ... weight rows per workgroup of batched_reg_kernel: enough workgroups to pull HBM bandwidth - fewer weight rows per
 // workgroup when N / 16 would leave CUs idle (the LDS-image kernel: always 16)

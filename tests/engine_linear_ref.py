@@ -68,7 +68,8 @@ MIN_STEP = ST.MIN_STEP
 # H, I, query heads, kv heads, head_dim.  W: the benchmark's widths (qkv N = 4096: 4 rows per wave at K = 1024; gate_up 6 rows
 # per wave; down at K = 3072).  W6: 2176 pairs leave 6-row workgroups a tail.  T: generic K everywhere, head_dim 64, GQA 3.
 # X: K = 512 and 1536 (preload depths 1 and 3), qkv N = 2048 (2 rows per wave).  P: K = 256 in o_proj - no carried norms, so
-# the packed decode step keeps its split-K slabs.  B4: 4096 gate / up pairs (4 pair rows per wave).
+# the packed decode step keeps its split-K slabs.  B4: 4096 gate / up pairs (4 pair rows per wave); down at K = 4096 (the
+# register-fragment batched kernel's deepest width, 32 k-steps per wave).
 SHAPES = {"W": (1024, 3072, 16, 8, 128), "W6": (1024, 2176, 16, 8, 128), "T": (640, 896, 6, 2, 64), "X": (512, 1536, 8, 4, 128),
           "P": (512, 1024, 2, 1, 128), "B4": (512, 4096, 4, 2, 128)}
 DENSITY = {"QL": 0.35, "LM": 0.35, "O": 0.3, "GUb": 0.35, "D": 0.25}
@@ -507,7 +508,7 @@ RIGS = {
     "X": _rig("X", decode=(1, 4, 5), prefill=(17,)),
     "W6": _rig("W6", decode=(1, 5), prefill=(17, 128)),
     "P": _rig("P", decode=(33,), replay=(33,), prefill=(17,)),
-    "B4": _rig("B4", kinds=("GUa", "GUb"), decode=(1, 4)),
+    "B4": _rig("B4", kinds=("GUa", "GUb", "D"), decode=(1, 4, 5)),
 }
 CHUNKED = (100, 50)            # one chunked prefill: 100 rows, then 50 at start_pos = 100
 

@@ -343,6 +343,7 @@ EXPECT = {
     ("P", 33): {"0.form": "packed", "0.carried": 0, "0.proj.o.kernel": "pkgemm", "0.proj.o.splits": 2, "0.proj.down.kernel": "pkgemm", "0.proj.down.splits": 8},
     ("B4", 1): {"0.form": "gemv", "0.proj.gate_up.r": 4, "0.proj.gate_up.c": 1, "0.proj.gate_up.n": 4096},
     ("B4", 4): {"0.form": "gemv", "0.act": "bf16", "0.proj.gate_up.r": 4},
+    ("B4", 5): {"0.form": "batched", "0.proj.down.kernel": "batched_reg", "0.proj.down.rows": 4, "0.proj.down.k": 4096, "0.proj.gate_up.kernel": "batched_lds"},
 }
 # w8a16 engines hold the dequantised fragment-major copy, so their chunks of 17..64 sequences take the packed step as well
 EXPECT[("W-fp8", 19)] = {"0.form": "packed", "0.m": 19}

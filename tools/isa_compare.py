@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of two `hipcc --cuda-device-only -S` outputs of the same source file (parent / result): the resource
 metadata of each kernel ('; Kernel info:' block) and the number of instructions per mnemonic class.  Nothing is run.
-usage: tools/isa_compare.py parent.s result.s [label]     (label: the source file's name for the `file` column)"""
+usage: tools/isa_compare.py [--rename-parent REGEX REPLACEMENT] parent.s result.s [label]
+(label: the source file's name for the `file` column; --rename-parent: re.sub on the parent's kernel names before the two files are
+matched by name, for a kernel whose template parameters changed)
+A file that defines no kernel gives an empty table (c++filt is not started without names: it would wait on standard input)."""
 import re, subprocess, sys
 
 CLASSES = ("v_mfma", "v_exp_f32", "ds_", "global_", "s_barrier")
@@ -34,7 +37,7 @@ def kernels(path):
             if s and not s.startswith(".") and not s.endswith(":"):
                 body.append(re.sub(r"\.LBB\d+_\d+", ".LBB", s))
         i += 1
-    names = subprocess.run(["c++filt"] + list(out), capture_output=True, text=True).stdout.split("\n")
+    names = subprocess.run(["c++filt"] + list(out), capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout.split("\n") if out else []
     short = lambda n: re.sub(r"^void |\(.*$|pgk::", "", n).replace("__hip_bfloat16", "bf16").replace("_Float16", "f16")
     return {short(n): k for n, k in zip(names, out.values())}
 
@@ -44,8 +47,13 @@ def count(k, cls):
 
 
 def main():
-    par, res = kernels(sys.argv[1]), kernels(sys.argv[2])
-    label = sys.argv[3] if len(sys.argv) > 3 else ""
+    argv, rename = sys.argv[1:], None
+    if argv and argv[0] == "--rename-parent":
+        rename, argv = argv[1:3], argv[3:]
+    par, res = kernels(argv[0]), kernels(argv[1])
+    if rename:
+        par = {re.sub(rename[0], rename[1], n): k for n, k in par.items()}
+    label = argv[2] if len(argv) > 2 else ""
     print(f"{'kernel (result)':<46s} {'file':<18s} {'VGPR p/r':>9s} {'SGPR p/r':>9s} {'SGPRalloc p/r':>13s} {'occ p/r':>7s} {'LDS p/r':>13s} {'scr p/r':>7s} "
           f"{'mfma p/r':>9s} {'exp p/r':>8s} {'ds p/r':>8s} {'global p/r':>10s} {'barrier p/r':>11s} {'insts p/r':>11s} {'delta':>7s}  verdict")
     for name in sorted(res):
