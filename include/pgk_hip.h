@@ -639,6 +639,12 @@ pgk_status pgk_engine_launches_per_step(pgk_engine e, int* n);
  * with the cache length as its span; the replay runs the kernels named here over more slices than nsplit / span say,
  * which report the eager step. */
 pgk_status pgk_engine_attn_plan(pgk_engine e, int batch, int max_position, char* out, size_t n);
+/* Read-only, no device: what wave `wave` (0..3) of the fused MFMA decode attention kernel requests for a context of c1 cached
+ * rows, and its counted waits.  pre: W_o preloads of the form (4 fused with o_proj, 0 batch form); c0: start of a later chunk
+ * (a positive multiple of 192).  out[5]: [0..2] requests allowed outstanding at the waits for the new token's inputs, chunk 0's
+ * K rows, chunk 0's V rows; [3] tiles of 16 rows the wave stages at c0 (0 where c0 >= c1); [4] requests allowed outstanding at
+ * the wait for their K rows.  A tile is 4 K and 4 V requests; chunk 0 is always 3 tiles per wave. */
+pgk_status pgk_attn_mfma_plan(int c1, int c0, int wave, int pre, int32_t* out);
 /* Read-only: the PROJECTION launches (w_qkv, w_o, w_gate_up, w_down, lm_head), computed by the functions the launchers
  * themselves call; no device work, no state change.
  * prefill_n == 0: one decode step of `batch` sequences whose largest position is `max_position`.  Per chunk one line

@@ -142,7 +142,7 @@ _PROTOS = {
     "pgk_engine_read_clock": [_V, C.POINTER(C.c_uint64), _I, _V],
     "pgk_engine_kv_ptr": [_V, _I, c_void_pp, c_void_pp], "pgk_engine_state_ptr": [_V, c_void_pp, c_void_pp], "pgk_engine_launches_per_step": [_V, C.POINTER(_I)],
     "pgk_engine_attn_plan": [_V, _I, _I, C.c_char_p, _Z],
-    "pgk_engine_linear_plan": [_V, _I, _I, _I, C.c_char_p, _Z],
+    "pgk_attn_mfma_plan": [_I, _I, _I, _I, c_i32_p],    "pgk_engine_linear_plan": [_V, _I, _I, _I, C.c_char_p, _Z],
     "pgk_moe_topk_softmax": [_V, _V, _V, _I, _I, _I, _I, _I, _V], "pgk_moe_softmax_topk": [_V, _I, _I, _I, _V],
     "pgk_moe_compute_permutation": [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V],
     "pgk_moe_gather": [_V, _V, _V, _I, _I, _I, _I, _V], "pgk_moe_scatter": [_V, _I, _V, _V, _V, _I, _I, _I, _I, _V],

@@ -972,6 +972,20 @@ pgk_status pgk_engine_attn_plan(pgk_engine eh, int batch, int max_position, char
     return PGK_OK;
 }
 
+// Read-only, no device: the request plan of wave `wave` of attn_oproj_mfma_kernel for a context of c1 cached rows, from the
+// functions the kernel itself calls (attn_tail_plan.h).  pre: W_o preloads (4 fused, 0 batch form); c0: a later chunk's start.
+//   out[0..2] waits of the issue phase: new token, chunk 0 K, chunk 0 V   [3] tiles the loop stages at c0   [4] wait for their K
+pgk_status pgk_attn_mfma_plan(int c1, int c0, int wave, int pre, int32_t* out) {
+    PGK_REQUIRE(out && c1 >= 0 && wave >= 0 && wave < AM_WAVES && c0 > 0 && c0 % AM_CHUNK == 0 && (pre == 0 || pre == 4), "pgk_attn_mfma_plan: bad argument");
+    const int n = c0 < c1 ? am_live_tiles(c0, c1, wave) : 0;      // the loop ends at the first chunk start that is no cached row
+    out[0] = am_wait_new(pre);
+    out[1] = am_wait_k0(pre);
+    out[2] = am_wait_v0(pre);
+    out[3] = n;
+    out[4] = am_wait_k(n);
+    return PGK_OK;
+}
+
 // Read-only: what the PROJECTIONS of one decode step (prefill_n == 0: `batch` sequences, largest position `max_position`) or of
 // one prefill call of prefill_n tokens launch, from the functions the launchers themselves call (next_chunk, attn_flags,
 // gemv_rows / gemv_preload / gemv_grid, batched_is_reg / batched_reg_rows / mt_rows_per_group / mt_tiles / batched_reads_copy,

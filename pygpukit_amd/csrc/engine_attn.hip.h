@@ -2,6 +2,7 @@
 #pragma once
 
 #include "attn_core.hip.h"
+#include "attn_tail_plan.h"
 #include "engine_state.hip.h"
 #include "lds_dma.hip.h"
 
@@ -396,7 +397,8 @@ __global__ __launch_bounds__(256) void attn_oproj_kernel(unsigned long long* tl,
 // of LDS: the one-tile prefill kernel's scheme (ops_attention.hip, attn_short_kernel) with the G query heads of the kv
 // head as the only live columns:
 //   * chunks of 192 positions: K and V rows [c0, c0 + 192) -> LDS (K: 16-byte chunks XOR row & 15; V: layout (b) of the
-//     CDNA guide for ds_read_b64_tr_b16); chunk 0 is requested before the position is known (clamped rows);
+//     CDNA guide for ds_read_b64_tr_b16); chunk 0 is requested before the position is known (clamped rows),
+//     a later chunk by live tiles only;
 //   * wave w takes tiles w, w + 4, w + 8 of the chunk (16 positions each): S^T = K.Q^T - rows = positions, columns =
 //     heads - so a lane holds ONE head's scores of 4 consecutive positions per tile; max / sum are lane-local + two
 //     shuffles; exp'd and packed to bf16 they are the B operand of O^T = V^T.P^T with no LDS round trip (k-slot j of lane
@@ -404,7 +406,23 @@ __global__ __launch_bounds__(256) void attn_oproj_kernel(unsigned long long* tl,
 //   * every wave keeps a running (m, l, O^T) across chunks; at the end the four waves' states and the new token's
 //     (score, 1, v) meet in LDS and are combined per output element, then the W_o slice product as before.
 // The new token's k/v never enter the LDS images (the DMA of its cache row would race the write): it is a fifth partial.
-constexpr int AM_CHUNK = 192;   // positions per staged chunk: 12 tiles, 3 per wave
+// AM_CHUNK = 192 positions per staged chunk (12 tiles, 3 per wave): attn_tail_plan.h, with the live-tile and wait-count
+// arithmetic of the request order.
+
+// s_waitcnt takes an immediate: a counted wait whose count depends on the context picks among the few legal ones with a
+// wave-uniform branch (am_wait_vm_tiles: 4 per live tile)
+template <int N>
+__device__ __forceinline__ void am_wait_vm() {
+    static_assert(N >= 0 && N <= 63, "vmcnt holds 6 bits");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int (*COUNT)(int)>
+__device__ __forceinline__ void am_wait_vm_tiles(int n) {
+    if (n >= 3) am_wait_vm<COUNT(3)>();
+    else if (n == 2) am_wait_vm<COUNT(2)>();
+    else if (n == 1) am_wait_vm<COUNT(1)>();
+    else am_wait_vm<COUNT(0)>();
+}
 
 __device__ __forceinline__ int am_koff(int row, int ch) { return row * 256 + ((ch ^ (row & 15)) << 4); }
 __device__ __forceinline__ int am_voff(int row, int ch) { return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4); }
@@ -503,30 +521,36 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
     }
     static_assert(AM_CHUNK == 16 * 3 * NWV, "a chunk is three 16-row tiles per wave: 12 K and 12 V requests per wave");
     constexpr int NREQ = AM_CHUNK / 4 / NWV;              // requests per wave and image
-    auto stage_image = [&](const bf16* head, const uint32_t (&off)[4], uint32_t lds_img, int c0) {
+    // ntile: the wave's first ntile tiles only (wave-uniform; chunk 0: the constant 3) - its last row is below c0 + 64 ntile,
+    // which is what (a) asks of the cache.
+    auto stage_image = [&](const bf16* head, const uint32_t (&off)[4], uint32_t lds_img, int c0, int ntile) {
         const bf16* base = head + (size_t)c0 * D;
         const uint32_t dst = lds_img + wid * 4096;
-        if (c0 + AM_CHUNK <= max_seq_) {                  // (a)
+        if (c0 + 64 * ntile <= max_seq_) {                // (a)
 #pragma unroll
             for (int u = 0; u < 3; ++u)
+                if (u < ntile) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) lds_dma16_so(base + u * 64 * D, off[r], dst + u * 16384 + r * 1024);
+                    for (int r = 0; r < 4; ++r) lds_dma16_so(base + u * 64 * D, off[r], dst + u * 16384 + r * 1024);
+                }
         } else {                                          // (b)
             const uint32_t last = (uint32_t)(max_seq_ - 1 - c0) << 8;
 #pragma unroll
             for (int u = 0; u < 3; ++u)
+                if (u < ntile) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) lds_dma16_so(base, min(off[r] + 16384u * u, last | (off[r] & 0xF0u)), dst + u * 16384 + r * 1024);
+                    for (int r = 0; r < 4; ++r) lds_dma16_so(base, min(off[r] + 16384u * u, last | (off[r] & 0xF0u)), dst + u * 16384 + r * 1024);
+                }
         }
     };
-    stage_image(kc, koff, lds_addr_of(k_lds), 0);
+    stage_image(kc, koff, lds_addr_of(k_lds), 0, 3);
     __builtin_amdgcn_sched_barrier(0);
     // From here on the struct.  The position first: read through the constant address space it is a scalar load the compiler
     // counts itself - issued here, ahead of the V requests, waited for where the value is first used (positions[] is not
     // written by this launch, and the dispatch invalidated the scalar cache, which load_uniform_i32 relies on too).
     const int pos = *(const __attribute__((address_space(4))) int32_t*)(a.positions + b);
     const bf16* vc = a.vcache + head_off;
-    stage_image(vc, voff, lds_addr_of(v_lds), 0);
+    stage_image(vc, voff, lds_addr_of(v_lds), 0, 3);
     const int r0 = rb * a.rows_per_block;
     const int npass = a.rows_per_block / RPP;
     const bf16* wbase = a.w_o + (size_t)kvh * GD + lr * 8;
@@ -537,14 +561,13 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
     __builtin_amdgcn_sched_barrier(0);
     tls.phase(0);
     // Vector memory returns in issue order, and per wave that order is: NRAW new-token requests, NREQ K, NREQ V, PRE W_o
-    // loads.  A wait for "at most n outstanding" therefore means: everything but the n youngest has landed.
-    constexpr int W_NEW = 2 * NREQ + PRE;                 // younger than the new token's inputs: the whole chunk + W_o
-    constexpr int W_K0 = NREQ + PRE;                      // younger than chunk 0's K rows: its V rows + W_o
-    constexpr int W_V0 = PRE;                             // younger than chunk 0's V rows: W_o
-    constexpr int W_K = NREQ;                             // later chunks (W_o long landed - it is older): the V rows
-    constexpr int W_V = 0;
-    static_assert(NREQ == 12 && W_NEW == 24 + PRE && W_K0 == 12 + PRE && W_V0 == PRE && W_K == 12, "wait counts follow the request order above");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_NEW) : "memory");
+    // loads.  A wait for "at most n outstanding" therefore means: everything but the n youngest has landed.  The counts are
+    // attn_tail_plan.h's: am_wait_new = the whole chunk + W_o, am_wait_k0 = chunk 0's V rows + W_o, am_wait_v0 = W_o; later
+    // chunks (W_o long landed - it is older) am_wait_k = the V rows of the wave's live tiles, then 0.
+    static_assert(NREQ == 3 * AM_TILE_REQ && am_wait_new(PRE) == 2 * NREQ + PRE && am_wait_k0(PRE) == NREQ + PRE && am_wait_v0(PRE) == PRE &&
+                      am_wait_k(3) == NREQ && am_wait_k(2) == 8 && am_wait_k(1) == 4 && am_wait_k(0) == 0,
+                  "wait counts follow the request order above");
+    am_wait_vm<am_wait_new(PRE)>();
     // The new token's G + 2 head vectors (q heads, k, v) are SPLIT over the waves - item i goes to wave i % 4 - instead of
     // every wave normalising and rotating all of them (0.74 us of ALU per wave in attn_oproj_kernel): each wave reads its
     // item from its own copy of the inputs, and the results meet in LDS behind the barrier that the cache chunk needs anyway.
@@ -596,8 +619,8 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
         }
     }
     tls.phase(1);
-    uint4 qf[4];
     const int c1 = min(pos, max_seq_);                  // cached positions [0, c1)
+    uint4 qf[4];
     float m_run = -INFINITY, l_run = 0.f;                // of head l15 (lanes l15 >= G carry dummies)
     am_f32x4 o[D / 16];
 #pragma unroll
@@ -605,14 +628,19 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
     const int tq = l15 >> 2, tp = l15 & 3;
     for (int c0 = 0; c0 == 0 || c0 < c1; c0 += AM_CHUNK) {
         if (c0 > 0) {
+            // The position is long known: a wave requests only its live tiles - the test the consumer below makes - so a
+            // context that ends early in the chunk costs the requests of what it holds, not 24 per wave (context 194 against
+            // 190: +48 us per step before).  Rows of a live tile at or past c1 are fetched and masked as ever.
+            // Dead tiles keep the previous chunk's rows: finite cache rows under weights of zero, as the clamped rows were.
             // no barrier: a wave overwrites only the image rows it alone reads, and its reads of the previous chunk have
             // returned (their values went through the MFMAs above; the asm statements keep the compiler's order)
-            stage_image(kc, koff, lds_addr_of(k_lds), c0);
-            stage_image(vc, voff, lds_addr_of(v_lds), c0);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_K) : "memory");
+            const int nlive = __builtin_amdgcn_readfirstlane(am_live_tiles(c0, c1, wid));
+            stage_image(kc, koff, lds_addr_of(k_lds), c0, nlive);
+            stage_image(vc, voff, lds_addr_of(v_lds), c0, nlive);
+            am_wait_vm_tiles<am_wait_k>(nlive);
         } else {
             __syncthreads();                               // publishes q_sh / k_sh / v_sh; in front of the waits, so no wave idles at it with its rows landed
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_K0) : "memory");
+            am_wait_vm<am_wait_k0(PRE)>();
         }
         __builtin_amdgcn_sched_barrier(0);
         if (c0 == 0) {
@@ -692,8 +720,8 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[i][r] *= alpha;
         // O^T += V^T . P^T: step 0 pairs tiles (wid, wid + 4), step 1 tile wid + 8 with zeros - all three this wave's own requests
-        if (c0 > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_V) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_V0) : "memory");
+        if (c0 > 0) am_wait_vm<0>();
+        else am_wait_vm<am_wait_v0(PRE)>();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int st2 = 0; st2 < 2; ++st2) {
