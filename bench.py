@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: BASELINE.json metric "decode tokens/sec/GPU + prefill TFLOPS, Qwen3-0.6B bf16".
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in the environment - what
     `python -m torch.distributed.run --nproc-per-node N bench.py ...` sets, or any other launcher; nothing here imports torch)
+
+A plain run does what the headline needs and nothing else: weights and engine set up, the prompt prefilled, W + K replayed
+steps, the outputs dumped if asked for, one JSON line.  `--full` adds every other measurement described below (config 4,
+the extras, the per-kernel roofline, both prefill timings, the CPU baseline) AFTER the headline and the dump, so `value`,
+`ms_per_step` and the dumped arrays come out of the same code, in the same order, in both kinds of run.
 
 Headline (`value`) at every N = BASELINE config 2 per GPU: random-init Qwen3-0.6B-shape bf16 weights, a 128-token
 prompt prefilled through the MFMA path, then K single-token greedy decode steps, each ONE replay of the whole-step
@@ -13,12 +18,12 @@ memory).  A "step" = one decode token for every sequence resident on the GPU.  F
 independent sequence: "weak" scaling, no collective inside the timed region; the token logs are all-gathered over
 RCCL after it.  `value` = sequences x K / max-over-ranks wall time, inputs resident in HBM.
 
-BASELINE config 4 (batch 64 decode, data-parallel over the node) runs at EVERY N under `extras.config4`:
+With `--full`, BASELINE config 4 (batch 64 decode, data-parallel over the node) runs at EVERY N under `extras.config4`:
   weak    b_local = 8 sequences per GPU (global 8 N),
   strong  b_local = 64 / N sequences per GPU (global 64; N = 1: all 64 on one GPU, one pass over the weights per step),
 each with its own barrier + device-sync bracket and max-over-ranks time; values are whole-job tokens/s.
 
-Extra objects on the JSON line:
+Objects on the JSON line (`full` says which kind of run wrote it; all but `step_roofline` need `--full`):
   roofline         the decode-step kernel with the largest share of the step's device time: algorithmic bytes per
                    launch / its average dispatch duration (start/stop events on every launch of eager steps on the
                    launch stream: the begin -> end interval rocprofv3 --kernel-trace reports), vs 8 TB/s HBM;
@@ -152,6 +157,10 @@ def main() -> None:
                          "sequence follows the CONTEXT, not this capacity")
     ap.add_argument("--weight-format", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline (and the dump), also run every other leg: prefill timings, per-kernel roofline, "
+                         "config 4, the extras, the CPU baseline (--cpu-decode-tokens, --no-cpu-baseline, --long-prefill, "
+                         "--no-config5, --no-extras and --config4-steps shape those legs and do nothing without --full)")
     ap.add_argument("--cpu-decode-tokens", type=int, default=16)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--long-prefill", type=int, default=2048,
@@ -301,6 +310,60 @@ def main() -> None:
         gather.pop("all_tokens")
     if args.dump_outputs and cp.rank == 0:
         dump_outputs(args.dump_outputs, eng.logits(B).to_numpy(), tokens)
+
+    # ---- whole-step roofline: arithmetic on the headline's own device time, no run of its own ----
+    ctx_mid = P + W + K // 2
+    ab = algorithmic_bytes_per_token(cfg, ctx_mid, args.weight_format)
+    step_ms = dev_ms_max / K
+    step_bytes = ab["weights"] + ab["lm_head"] + B * (ab["kv_read"] + ab["kv_write"] + ab["logits"])
+    step_roofline = {"bound": "hbm", "achieved": step_bytes / (step_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": step_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "bytes_per_step": step_bytes,
+                     "launches_per_step": eng.launches_per_step(), "ctx_mid": ctx_mid, "step_us": step_ms * 1e3}
+
+    result = {
+        "metric": "decode tokens/sec/GPU + prefill TFLOPS (% MFMA peak), Qwen3-0.6B bf16",
+        "value": cp.world * B * K / wall_max, "unit": "tokens/s", "n_gpus": cp.world, "steps": K, "warmup": W,
+        "ms_per_step": wall_max * 1e3 / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16" if args.weight_format == "bf16" else "fp8-e4m3 weights x bf16", "data": "synthetic",
+        "config": {"workload": f"Qwen3-0.6B-shape random-init {args.weight_format}, prefill {P} + {K}-token greedy decode, "
+                               f"whole-step hipGraph, {B} sequence(s) per GPU (BASELINE config 2{'' if cp.world == 1 else ' on every GPU: data-parallel replicas'})",
+                   "batch_per_gpu": B, "global_batch": cp.world * B, "prompt_len": P, "parallelism": f"dp{cp.world}",
+                   "layers": cfg["num_layers"], "max_seq_len": max_seq},
+        "full": args.full, "tokens_per_s_per_gpu": B * K / wall_max, "device_ms_per_step": step_ms, "step_roofline": step_roofline,
+        "first_tokens": [int(t) for t in tokens[: min(8, len(tokens)), 0]],
+    }
+    if gather is not None:
+        result["token_gather"] = gather
+    if bcast is not None:
+        result["weight_broadcast"] = bcast
+    if args.layers:
+        result["INVALID"] = "layer count overridden"
+    if args.full:
+        result.update(full_legs(args, cp, cfg, eng, new_engine, weights, mine, ops, timed_ms, step_roofline))
+    result["setup_s"] = time.perf_counter() - t_setup
+    if args.full and cp.rank == 0 and cp.world == 1 and not args.no_cpu_baseline:
+        del eng
+        result["cpu_baseline"] = cpu_baseline(cfg, weights, [int(t) for t in mine[0]], args.cpu_decode_tokens)
+    elif args.full and cp.rank == 0:
+        result["cpu_baseline"] = None
+    if cp.rank == 0:
+        emit(result)
+    cp.barrier()
+    if comm is not None:
+        comm.destroy()
+    cp.shutdown()
+
+
+def full_legs(args, cp, cfg, eng, new_engine, weights, mine, ops, timed_ms, step_roofline) -> dict:
+    """Everything `--full` measures beyond the headline, on the headline's engine and weights after its steps and its dump:
+    the 128-token prefill, the per-kernel roofline, config 4 and the other extras, the long prefill.  Returns the
+    result line's additional objects; fills `step_roofline["sum_of_kernel_us"]`."""
+    from pygpukit_amd import _hip
+    from pygpukit_amd import parallel as DP
+    from pygpukit_amd.llm import synthetic as S
+    from pygpukit_amd.llm.engine import Engine
+
+    B, K, W, P = args.batch_per_gpu, args.steps, args.warmup, args.prompt_len
     pf_ms = timed_ms(lambda: eng.prefill([int(t) for t in mine[0]], seq=0, want_last_logits=False), 5)    # slot 0's rows are rewritten with the same values
     pf_med = float(np.median(pf_ms))
     pf_flops = prefill_flops(cfg, P, all_rows=False)
@@ -308,8 +371,6 @@ def main() -> None:
     # ---- per-kernel timing: eager steps, start/stop events on every launch (rank 0's numbers are reported) ----
     prof = eng.profile_step(B, 8)
     ctx_mid = P + W + K // 2
-    ab = algorithmic_bytes_per_token(cfg, ctx_mid, args.weight_format)
-    step_ms = dev_ms_max / K
     rows = []
     kb = kernel_bytes_per_launch(cfg, ctx_mid, B)
     NAMES = {"norm_qkv": "fused_gemv_kernel<PRO_NORM, EPI_STORE> (RMSNorm + qkv projection)",
@@ -334,11 +395,7 @@ def main() -> None:
     if roofline:
         roofline["timing"] = ("start/stop hipEvents on every launch (hipExtLaunchKernelGGL, the launch stream) of 8 eager steps: "
                               "dispatch begin -> end, the interval rocprofv3 --kernel-trace reports; nothing subtracted")
-    step_bytes = ab["weights"] + ab["lm_head"] + B * (ab["kv_read"] + ab["kv_write"] + ab["logits"])
-    step_roofline = {"bound": "hbm", "achieved": step_bytes / (step_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": step_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "bytes_per_step": step_bytes,
-                     "launches_per_step": eng.launches_per_step(), "ctx_mid": ctx_mid,
-                     "sum_of_kernel_us": total_us, "step_us": step_ms * 1e3}
+    step_roofline["sum_of_kernel_us"] = total_us
 
     extras = None
     if not args.no_extras and B == 1 and args.weight_format == "bf16" and P == 128:
@@ -420,40 +477,10 @@ def main() -> None:
             except Exception as e:  # noqa: BLE001 - an extra leg must never take the headline down
                 extras["config5_llama8b_prefill4096"] = {"error": f"{type(e).__name__}: {e}"}
 
-    result = {
-        "metric": "decode tokens/sec/GPU + prefill TFLOPS (% MFMA peak), Qwen3-0.6B bf16",
-        "value": cp.world * B * K / wall_max, "unit": "tokens/s", "n_gpus": cp.world, "steps": K, "warmup": W,
-        "ms_per_step": wall_max * 1e3 / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16" if args.weight_format == "bf16" else "fp8-e4m3 weights x bf16", "data": "synthetic",
-        "config": {"workload": f"Qwen3-0.6B-shape random-init {args.weight_format}, prefill {P} + {K}-token greedy decode, "
-                               f"whole-step hipGraph, {B} sequence(s) per GPU (BASELINE config 2{'' if cp.world == 1 else ' on every GPU: data-parallel replicas'})",
-                   "batch_per_gpu": B, "global_batch": cp.world * B, "prompt_len": P, "parallelism": f"dp{cp.world}",
-                   "layers": cfg["num_layers"], "max_seq_len": max_seq},
-        "tokens_per_s_per_gpu": B * K / wall_max, "device_ms_per_step": step_ms,
-        "roofline": roofline, "roofline_kernels": rows, "step_roofline": step_roofline,
-        "prefill": {"ms": pf_med, "tflops": pf_flops / (pf_med * 1e-3) / 1e12, "flops": pf_flops, "logits": "last row only",
-                    "frac_mfma_peak": pf_flops / (pf_med * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, "runs_ms": [round(x, 3) for x in pf_ms]},
-        "prefill_long": long_pf, "extras": extras,
-        "first_tokens": [int(t) for t in tokens[: min(8, len(tokens)), 0]],
-        "setup_s": time.perf_counter() - t_setup,
-    }
-    if gather is not None:
-        result["token_gather"] = gather
-    if bcast is not None:
-        result["weight_broadcast"] = bcast
-    if args.layers:
-        result["INVALID"] = "layer count overridden"
-    if cp.rank == 0 and cp.world == 1 and not args.no_cpu_baseline:
-        del eng
-        result["cpu_baseline"] = cpu_baseline(cfg, weights, [int(t) for t in mine[0]], args.cpu_decode_tokens)
-    elif cp.rank == 0:
-        result["cpu_baseline"] = None
-    if cp.rank == 0:
-        emit(result)
-    cp.barrier()
-    if comm is not None:
-        comm.destroy()
-    cp.shutdown()
+    return {"roofline": roofline, "roofline_kernels": rows,
+            "prefill": {"ms": pf_med, "tflops": pf_flops / (pf_med * 1e-3) / 1e12, "flops": pf_flops, "logits": "last row only",
+                        "frac_mfma_peak": pf_flops / (pf_med * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, "runs_ms": [round(x, 3) for x in pf_ms]},
+            "prefill_long": long_pf, "extras": extras}
 
 
 if __name__ == "__main__":

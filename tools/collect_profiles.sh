@@ -29,7 +29,7 @@ pmc() {   # name, kernel filter, program args...
 cd $R
 if [ "$part" = 1 ]; then
   echo "== part 1" | tee $O/progress.log
-  timeout -k 10 500 python bench.py > $O/bench_n1.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/progress.log
+  timeout -k 10 500 python bench.py --full > $O/bench_n1.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/progress.log
   timeout -k 10 120 python tools/timeline_dump.py 1 150 bf16 $O/decode_timeline.json > $O/decode_timeline.txt 2>&1 || echo "timeline failed" | tee -a $O/progress.log
   timeout -k 10 120 python tools/timeline_dump.py 1 2048 fp8 $O/config3_timeline.json > $O/config3_timeline.txt 2>&1 || echo "timeline c3 failed" | tee -a $O/progress.log
   stats decode $BENCH

@@ -17,7 +17,7 @@ timeout -k 10 200 python tools/prefill_prof.py 128 20 > $O/pf.log 2>&1 || exit 1
 timeout -k 10 200 python tools/prefill_prof.py 2048 5 >> $O/pf.log 2>&1 || exit 1
 cat $O/pf.log
 echo "== bench" | tee -a $O/progress.log
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/progress.log
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/progress.log
 cat $O/bench.json; tail -5 $O/bench.err
 echo "== timeline" | tee -a $O/progress.log
 timeout -k 10 120 python tools/timeline_dump.py 1 150 bf16 $O/tl_b1.json > $O/tl_b1.txt 2>&1 || exit 1

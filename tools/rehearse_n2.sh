@@ -11,7 +11,7 @@ mkdir -p $O
 cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0 PGK_REHEARSE_SHARED_GPU=1
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${NPROC:-2} --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus ${NPROC:-2} --steps 16 --warmup 4 --no-cpu-baseline --config4-steps 8 > $O/bench_n2.json 2> $O/bench_n2.err
+    bench.py --gpus ${NPROC:-2} --steps 16 --warmup 4 --full --no-cpu-baseline --config4-steps 8 > $O/bench_n2.json 2> $O/bench_n2.err
 echo "rc=$?" | tee $O/rc.txt
 head -c 3000 $O/bench_n2.json; echo; tail -15 $O/bench_n2.err | cut -c1-300
 exit 0
