@@ -532,6 +532,34 @@ pgk_status pgk_sdpa_fixed_cache(const void* q, const void* k_cache, const void* 
                                 int q_len, int max_seq, int d, float scale, int h_context_len,
                                 const int32_t* ctx_buf, void* workspace, pgk_dtype dt, pgk_stream s);
 
+/* [build-defined] Sliding-window attention (Mistral, Phi-3, Gemma's local layers, Qwen2's use_sliding_window): pgk_sdpa_causal's
+ * contract and mask with a lower edge - query row i of q_len sees the keys max(0, off + i - window + 1) .. off + i with
+ * off = kv_len - q_len: `window` keys including its own (HuggingFace's kv_idx > q_idx - sliding_window).  window >= 1,
+ * kv_len >= q_len >= 1; window >= kv_len is plain causal attention.  f16 / bf16 with head_dim 64 / 128 on 16-byte aligned q / k / v,
+ * 8-byte aligned out and strides that are multiples of 8 (out: 4) elements run the MFMA flash kernel with the FlashWindow policy
+ * at EVERY q_len: a query tile walks only the KV tiles of its band.  Anything else - float32 included - and
+ * PYGPUKIT_FLASH_ATTENTION=0 run the window form of the one-workgroup-per-row fallback (min(window, kv_len) <= 15360,
+ * q_len <= 65535, PGK_ERR_UNSUPPORTED beyond). */
+pgk_status pgk_sdpa_window(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d, int window,
+                           float scale, int64_t q_stride_h, int64_t q_stride_s, int64_t kv_stride_h, int64_t kv_stride_s, int64_t o_stride_h,
+                           int64_t o_stride_s, pgk_dtype dt, pgk_stream s);
+/* Host-only: "window_flash" or "window_rows", the kernel pgk_sdpa_window takes, and through *nsplit (may be NULL) the KV runs per
+ * query tile of the flash kernel on the current device (1 for the fallback).  aligned: as pgk_relbias_plan.  NULL (and
+ * pgk_last_error) for arguments that pgk_sdpa_window rejects. */
+const char* pgk_sdpa_window_plan(int hq, int hkv, int q_len, int kv_len, int d, int window, pgk_dtype dt, int aligned, int* nsplit);
+/* One query row Q [hq, 1, d] over a fixed cache with a window: positions max(0, ctx - window) .. ctx - 1, ctx = ctx_buf[0] when
+ * ctx_buf is non-NULL, else h_context_len.  The split-KV chunks cut the WINDOW, so the grid is fixed by min(capacity, window):
+ * `workspace` must hold pgk_sdpa_decode_workspace_bytes(hq, d, min(capacity, window)).  ring == 0: caches [hc, capacity, d],
+ * position p in row p, ctx <= capacity.  ring != 0: position p in row p % capacity (pgk_kv_cache_write_ring) and ctx may pass
+ * capacity when window <= capacity.  d 64 / 128 with aligned buffers and a workspace; other head dims run pgk_sdpa_window over the
+ * prefix of a linear cache (host length only).  For a chunk of q_len > 1 rows over a linear cache call pgk_sdpa_window on the prefix. */
+pgk_status pgk_sdpa_window_fixed_cache(const void* q, const void* k_cache, const void* v_cache, void* out, int hq, int hc, int capacity, int d,
+                                       int window, int ring, float scale, int h_context_len, const int32_t* ctx_buf, void* workspace,
+                                       pgk_dtype dt, pgk_stream s);
+/* pgk_kv_cache_write into a rolling cache [hc, capacity, d]: row s of new_kv goes to row (pos + s) % capacity; seq <= capacity. */
+pgk_status pgk_kv_cache_write_ring(const void* new_kv, void* cache, int seq, int hkv, int hc, int capacity, int d, int itemsize, int h_pos,
+                                   const int32_t* pos_buf, pgk_stream s);
+
 /* ---------------------------------------------------------------------- engine ------ */
 /* Native decode/prefill launcher: one C call (or one hipGraph launch) per token step instead of
  * ~21 Python-dispatched launches per layer.  Replaces the device-dispatch half

@@ -27,3 +27,6 @@ from pygpukit_amd.ops.conv import conv1d, conv2d  # noqa: F401,E402
 from pygpukit_amd.ops.nn.norm import group_norm, group_norm_silu  # noqa: F401,E402
 from pygpukit_amd.ops.nn.relpos import (relbias_plan, relpos_bias_table, relpos_bucket, relpos_compute_bias, sdpa_relbias,  # noqa: F401,E402
                                         sdpa_relbias_strided)
+from pygpukit_amd.ops.nn.window import (kv_cache_update_ring, kv_cache_update_ring_ptr, sdpa_sliding_window,  # noqa: F401,E402
+                                        sdpa_sliding_window_fixed_cache, sdpa_sliding_window_fixed_cache_ptr, sdpa_sliding_window_strided,
+                                        sdpa_window_plan)

@@ -124,6 +124,9 @@ _PROTOS = {
     "pgk_llama4_qk_norm_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _I, _V, _I, _V],
     "pgk_sdpa_irope_fixed_cache": [_V, _V, _V, _V, _I, _I, _I, _I, _F, _F, _I, _V, _V, _I, _V],
     "pgk_sdpa_fixed_cache": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I, _V, _V, _I, _V],
+    "pgk_sdpa_window": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
+    "pgk_sdpa_window_fixed_cache": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _F, _I, _V, _V, _I, _V],
+    "pgk_kv_cache_write_ring": [_V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V],
     "pgk_pope_inplace": [_V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V], "pgk_alibi_compute_bias": [_V, _V, _I, _I, _I, _V],
     "pgk_alibi_add_bias": [_V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V],
     "pgk_sdpa_alibi": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
@@ -180,6 +183,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_adaln_plan": ([_I, _I, _I], C.c_char_p),
                "pgk_flux_qk_norm_rope_plan": ([_I, _I, _I], C.c_char_p),
                "pgk_relbias_plan": ([_I, _I, _I, _I], C.c_char_p),
+               "pgk_sdpa_window_plan": ([_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}

@@ -370,12 +370,19 @@ __device__ __host__ __forceinline__ int decode_chunk_len(int ctx, int nsplit, in
 struct DecodePlain { int host_ctx; const int32_t* ctx_buf; float scale; };
 struct DecodeIrope { int host_pos; const int32_t* pos_buf; float scale, attn_scale, floor_scale; };
 struct DecodeAlibi { int host_ctx; const int32_t* ctx_buf; float scale; const float* slopes; };   // slopes: [Hq] fp32
+//   DecodeWindow pgk_sdpa_window_fixed_cache (ops_attention.hip): positions lo = max(0, ctx - window) .. ctx - 1.  The chunks cut
+//                                            [lo, ctx), not [0, ctx): every workgroup has live rows at any context and the grid
+//                                            is decode_nsplit(min(cache rows, window)).  ring: the cache is [Hkv][C][D] with
+//                                            position p in row p % C (max_seq carries C), ctx is not bounded by C, and a chunk
+//                                            that crosses the wrap point is walked as two row ranges into the same state.
+struct DecodeWindow { int host_ctx; const int32_t* ctx_buf; float scale; int window, ring; };
 
 // Phase 1: workgroup (chunk, group of G consecutive query heads of one kv head: G divides Hq / Hkv) -> G partial records.
 template <class T, int D, int G, class X>
 __global__ __launch_bounds__(256) void decode_phase1_kernel(const T* q, const T* kc, const T* vc, float* ws, int hq, int hkv,
                                                             int max_seq, int nsplit, X ex) {
     constexpr bool IROPE = std::is_same<X, DecodeIrope>::value, ALIBI = std::is_same<X, DecodeAlibi>::value;
+    constexpr bool WINDOW = std::is_same<X, DecodeWindow>::value;
     constexpr int LPR = D / 8, PPW = 64 / LPR, RS = D + 2;
     __shared__ float lds[4 * PPW * G * RS];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -385,14 +392,19 @@ __global__ __launch_bounds__(256) void decode_phase1_kernel(const T* q, const T*
         const int pos = max(ex.pos_buf ? ex.pos_buf[0] : ex.host_pos, 0);
         ctx = min(pos, max_seq - 1) + 1;
         qmul = irope_temperature(pos, ex.attn_scale, ex.floor_scale) * ex.scale;
+    } else if constexpr (WINDOW) {
+        ctx = max(ex.ctx_buf ? ex.ctx_buf[0] : ex.host_ctx, 0);
+        if (!ex.ring) ctx = min(ctx, max_seq);
     } else {
         ctx = min(ex.ctx_buf ? ex.ctx_buf[0] : ex.host_ctx, max_seq);
         if constexpr (ALIBI) ctx = max(ctx, 0);
     }
     const int h0 = blockIdx.y * G;
     const int kv_head = h0 / (hq / hkv);
-    const int chunk = decode_chunk_len(ctx, nsplit);
-    const int c0 = min(blockIdx.x * chunk, ctx), c1 = min(c0 + chunk, ctx);
+    int lo = 0;           // first live position
+    if constexpr (WINDOW) lo = max(ctx - (ex.ring ? min(ex.window, max_seq) : ex.window), 0);     // a ring holds its last max_seq positions
+    const int chunk = decode_chunk_len(ctx - lo, nsplit);
+    const int c0 = min(lo + blockIdx.x * chunk, ctx), c1 = min(c0 + chunk, ctx);
     float qf[G][8];
     const int sub = lane % LPR;
 #pragma unroll
@@ -411,18 +423,27 @@ __global__ __launch_bounds__(256) void decode_phase1_kernel(const T* q, const T*
 #pragma unroll
         for (int g = 0; g < G; ++g) bias.slope[g] = ex.slopes[h0 + g];
         decode_walk<T, D, G>(kbase, vbase, c0, c1, qf, lane, wid, st, bias);
+    } else if constexpr (WINDOW) {
+        if (ex.ring) {      // workgroup-uniform
+            const RingSpan rs = ring_span(c0, c1, max_seq);
+            decode_walk<T, D, G>(kbase, vbase, rs.r0, rs.r0 + rs.n0, qf, lane, wid, st);
+            decode_walk<T, D, G>(kbase, vbase, 0, rs.n1, qf, lane, wid, st);
+        } else {
+            decode_walk<T, D, G>(kbase, vbase, c0, c1, qf, lane, wid, st);
+        }
     } else {
         decode_walk<T, D, G>(kbase, vbase, c0, c1, qf, lane, wid, st);
     }
     decode_block_merge<D, G>(st, lds, ws + ((size_t)h0 * nsplit + blockIdx.x) * RS, (size_t)nsplit * RS, lane, wid);
 }
 
-// Phase 1 over decode_nsplit(max_seq) chunks, then phase 2.  ws: pgk_sdpa_decode_workspace_bytes(hq, D, max_seq)
+// Phase 1 over decode_nsplit(split_rows) chunks, then phase 2.  ws: pgk_sdpa_decode_workspace_bytes(hq, D, split_rows).
+// split_rows: the rows the chunks cut at full context - max_seq (0), or DecodeWindow's decode_window_rows(max_seq, window)
 template <class T, int D, class X>
 static pgk_status launch_split_decode(const void* q, const void* kc, const void* vc, void* out, void* ws, int hq, int hkv, int max_seq,
-                                      const X& ex, hipStream_t st) {
-    constexpr bool FIVE = !std::is_same<X, DecodePlain>::value;
-    const int nsplit = decode_nsplit(max_seq), G = decode_heads_per_group(hq, hkv, nsplit, FIVE);
+                                      const X& ex, hipStream_t st, int split_rows = 0) {
+    constexpr bool FIVE = std::is_same<X, DecodeIrope>::value || std::is_same<X, DecodeAlibi>::value;
+    const int nsplit = decode_nsplit(split_rows > 0 ? split_rows : max_seq), G = decode_heads_per_group(hq, hkv, nsplit, FIVE);
     auto phase1 = [&](auto g) {
         decode_phase1_kernel<T, D, decltype(g)::value, X><<<dim3(nsplit, hq / G), 256, 0, st>>>((const T*)q, (const T*)kc, (const T*)vc,
                                                                                              (float*)ws, hq, hkv, max_seq, nsplit, ex);

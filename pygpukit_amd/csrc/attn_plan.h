@@ -93,6 +93,29 @@ __host__ __device__ inline RelbiasTile relbias_tile_class(int kv0, int qw0, int 
     return rel + FL_BKV - 1 <= -radius ? RELBIAS_FAR_LEFT : (rel - 31 >= radius ? RELBIAS_FAR_RIGHT : RELBIAS_NEAR);
 }
 
+// ---- sliding window: pgk_sdpa_window (flash_fwd_kernel with FlashWindow at every q_len, or the fallback with a lower bound on its
+// key loop) and pgk_sdpa_window_fixed_cache (decode_phase1_kernel with DecodeWindow) -------------------------------------------
+// Row i sees `window` keys, its own included: max(0, mask_off + i - window + 1) .. mask_off + i.
+inline SdpaKernel sdpa_window_pick(bool half, int d, bool in_aligned, bool out_aligned8, const FlashStrides& sd, bool flash_on) {
+    return sdpa_full_pick(half, d, in_aligned, out_aligned8, sd, flash_on);
+}
+// keys the heaviest query tile walks: the windows of its 128 rows span window + 127 keys
+inline int window_kv_seen(int kv_len, int window) { return (long long)window + FL_BQ - 1 < kv_len ? window + FL_BQ - 1 : kv_len; }
+// rows the split-KV decode cuts into chunks: the live rows at full context.  decode_nsplit of THIS fixes the grid and sizes the
+// workspace (pgk_sdpa_decode_workspace_bytes(hq, d, decode_window_rows(..))), so a captured graph replays as ctx passes window.
+inline int decode_window_rows(int cache_rows, int window) { return window < cache_rows ? window : cache_rows; }
+// Ring cache [Hc][C][D]: position p lives in row p % C.  The logical slice [c0, c1) (0 <= c1 - c0 <= C) is the row range
+// [r0, r0 + n0) followed, when it crosses the wrap point, by [0, n1): one modulo per slice, none per row.
+struct RingSpan { int r0, n0, n1; };
+__host__ __device__ inline RingSpan ring_span(int c0, int c1, int C) {
+    RingSpan s;
+    s.r0 = c0 % C;
+    const int n = c1 - c0;
+    s.n0 = s.r0 + n <= C ? n : C - s.r0;
+    s.n1 = n - s.n0;
+    return s;
+}
+
 // KV runs per query tile of the second-generation kernels: enough workgroups for two per CU (the kernels' occupancy), never more
 // runs than the shortest useful run of two KV tiles allows for the heaviest query tile.  cus: device_cu_count()
 inline int flash_nsplit(int nqt, int hq, int kv_len, int cus) {
@@ -140,5 +163,8 @@ pgk_status flash_prefill_q8(const void* q, const void* k, const void* v, uint8_t
 // table: [hq][2 * radius + 1] fp32 on the device, 0 <= radius <= FL_RELBIAS_MAX_RADIUS; scale > 0; any q_len, kv_len >= 1
 pgk_status flash_prefill_relbias(const void* q, const void* k, const void* v, const float* table, void* out, int hq, int hkv, int q_len,
                                  int kv_len, int d, int radius, float scale, const FlashStrides& sd, int dt16, hipStream_t st);
+// kv_len >= q_len >= 1, window >= 1 (clamped to kv_len), scale > 0
+pgk_status flash_prefill_window(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
+                                int window, float scale, const FlashStrides& sd, int dt16, hipStream_t st);
 
 }  // namespace pgk

@@ -53,6 +53,13 @@ struct FlashRelBias {
     int radius;              // 0 .. FL_RELBIAS_MAX_RADIUS
 };
 
+// sdpa_sliding_window (pgk_sdpa_window, ops_attention.hip): FlashPlain's diagonal and a second, lower one - row i sees the keys
+// max(0, mask_off + i - window + 1) .. mask_off + i, `window` of them including its own.  The policy walks a BAND of KV tiles
+// (flash_walk_band, flash_core.hip.h) instead of the triangle.
+struct FlashWindow {
+    int window;              // 1 .. kv_len (the launcher clamps: a wider window is plain causal attention)
+};
+
 // V^T image: [D][64 kv] 16-bit = 128-byte rows, 8-byte chunk c8 (0..15) of row d at d*128 + ((c8 ^ ((d>>1) & 15)) << 3):
 // the 32 rows a half-wave reads at one c8 then fall on 32 different bank pairs
 __device__ __forceinline__ int fl_v_off(int d, int c8) { return d * 128 + ((c8 ^ ((d >> 1) & 15)) << 3); }

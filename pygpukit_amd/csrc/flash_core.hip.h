@@ -211,6 +211,61 @@ __device__ __forceinline__ void flash_walk(const FlashWork& w, FlashVStage<T, DT
     }
 }
 
+// The band form of the walk (FlashWindow): row i sees the keys mask_off + i - window + 1 .. mask_off + i, so the 128 rows of
+// query tile qt see nothing left of key mask_off + 128 qt - window + 1 and the walk starts at that key's tile, t_lo, not at 0;
+// the KV split cuts [t_lo, t_hi).  Past the first window / 128 query tiles every tile walks the same (window + 127) / 64 + 1
+// tiles at most, whatever kv_len is.  Per wave (all tests wave-uniform):
+//   * a tile entirely LEFT of the window of the wave's first row (the leftmost of its 32 windows) is skipped, as a tile
+//     entirely above the diagonal of its last row is;
+//   * a tile that reaches left of the window of the wave's LAST row straddles some row's left edge and takes the lower-edge
+//     mask - local kv row >= lo_lim, per lane - before flash_softmax_pv (whose own branch masks the diagonal and the ragged end);
+//   * every other tile - the interior of the band - runs flash_softmax_pv's unmasked path.
+// A row whose keys of a tile are all masked keeps (m, l) = (-inf, 0) and p = exp2(-inf) = 0, as an early causal row does; a
+// wave for which a whole KV run is empty (a run left of its windows, or above its diagonal) stores zeros and the record
+// (-inf, 0), to which flash_merge_kernel gives the weight 0.  The loop body is flash_walk's, the pipeline unchanged.
+template <class T, int DT, class LoadK, class StoreK, class RetireQ, class QK>
+__device__ __forceinline__ void flash_walk_band(const FlashWork& w, int window, FlashVStage<T, DT>& vst, const T* vh, int q_len, int kv_len, int nsplit,
+                                                int ql, int h, char* vs0, f32x16_fl (&o)[DT], float& m_run, float& l_run, LoadK&& load_k,
+                                                StoreK&& store_k, RetireQ&& retire_q, QK&& qk) {
+    constexpr int V_BYTES = DT * 32 * 128;
+    const int q_last = min(w.qt * FL_BQ + FL_BQ - 1, q_len - 1);
+    const int kv_end = min(kv_len, w.mask_off + q_last + 1);
+    const int t_hi = (kv_end + FL_BKV - 1) / FL_BKV;
+    const int t_lo = max(0, w.mask_off + w.qt * FL_BQ - window + 1) / FL_BKV;     // < t_hi: window >= 1
+    const int nt = t_hi - t_lo;
+    const int t0 = t_lo + (int)((long long)nt * w.split / nsplit), t1 = t_lo + (int)((long long)nt * (w.split + 1) / nsplit);
+    const int lo_first = w.mask_off + w.qw0 - window + 1;       // left edge of the wave's first row (negative: the row sees key 0)
+    f32x16_fl sc0, sc1;
+    if (t0 < t1) {
+        load_k(t0);
+        vst.load(vh, t0);
+        store_k(t0 & 1);
+        vst.store(vs0 + (t0 & 1) * V_BYTES);
+    }
+    retire_q();
+    __syncthreads();
+    for (int t = t0; t < t1; ++t) {
+        const int buf = t & 1, kv0 = t * FL_BKV;
+        if (t + 1 < t1) { load_k(t + 1); vst.load(vh, t + 1); }
+        const bool cur = kv0 <= w.mask_off + w.qw0 + 31 && kv0 + FL_BKV - 1 >= lo_first;     // inside this wave's band (wave-uniform)
+        if (cur) {
+            qk(buf, kv0, sc0, sc1);
+            if (kv0 < lo_first + 31) {      // left of the last row's edge: some row's window starts inside this tile (wave-uniform)
+                const int lo_lim = lo_first + ql - kv0 - 4 * h;     // local kv row >= lo_lim is visible
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kvl = (r & 3) + 8 * (r >> 2);
+                    sc0[r] = kvl >= lo_lim ? sc0[r] : -INFINITY;
+                    sc1[r] = 32 + kvl >= lo_lim ? sc1[r] : -INFINITY;
+                }
+            }
+            flash_softmax_pv<T, DT, false>(w, kv0, kv_len, ql, h, sc0, sc1, o, m_run, l_run, vs0 + buf * V_BYTES, 1.0f);
+        }
+        if (t + 1 < t1) { store_k(buf ^ 1); vst.store(vs0 + (buf ^ 1) * V_BYTES); }
+        __syncthreads();
+    }
+}
+
 // The row's sum over both lane halves; inv = its reciprocal, 0 for a row that saw no key
 __device__ __forceinline__ float flash_row_sum(float l_run, float& inv) {
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);

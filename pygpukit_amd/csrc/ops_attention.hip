@@ -311,22 +311,25 @@ __global__ __launch_bounds__(64 * NW) void attn_short_kernel(const bf16* q, cons
 
 // fp32 / odd head_dim fallback: one workgroup per (head, query row), scores kept in LDS.
 // CAUSAL = false is sdpa_noncausal's fallback: every row attends all kv_len keys.
-template <class T, bool CAUSAL = true>
-__global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k, const T* v, T* out, int hq, int hkv,
-                                                         int q_len, int kv_len, int d, float scale, FlashStrides sd) {
+// WINDOW = true is sdpa_sliding_window's (sdpa_window_naive_kernel): a lower bound on the key loops, the row's last `window` causal
+// keys [p_lo, n_att); its scores sit at sc[p - p_lo], so the LDS row is min(kv_len, window) floats.
+template <class T, bool CAUSAL, bool WINDOW>
+__device__ __forceinline__ void sdpa_naive_row(const T* q, const T* k, const T* v, T* out, int hq, int hkv, int q_len, int kv_len, int d,
+                                               float scale, FlashStrides sd, int window) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = reinterpret_cast<float*>(smem);  // [kv_len]
+    float* sc = reinterpret_cast<float*>(smem);  // [n_att - p_lo]: kv_len, or min(kv_len, window)
     __shared__ float red[16];
     const int head = blockIdx.x, qi = blockIdx.y, kvh = head / (hq / hkv);
     const T* qr = q + (size_t)head * sd.qh + (size_t)qi * sd.qs;
     const int n_att = CAUSAL ? min(kv_len, (kv_len - q_len) + qi + 1) : kv_len;
+    const int p_lo = WINDOW ? max(n_att - window, 0) : 0;
     float mx = -INFINITY;
-    for (int p = threadIdx.x; p < n_att; p += blockDim.x) {
+    for (int p = p_lo + threadIdx.x; p < n_att; p += blockDim.x) {
         const T* kr = k + (size_t)kvh * sd.kh + (size_t)p * sd.ks;
         float dot = 0.f;
         for (int j = 0; j < d; ++j) dot = fmaf(to_f(qr[j]), to_f(kr[j]), dot);
         dot *= scale;
-        sc[p] = dot;
+        sc[p - p_lo] = dot;
         mx = fmaxf(mx, dot);
     }
     mx = wave_max(mx);
@@ -336,9 +339,9 @@ __global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k,
     mx = red[0];
     for (int w = 1; w < 4; ++w) mx = fmaxf(mx, red[w]);
     float sum = 0.f;
-    for (int p = threadIdx.x; p < n_att; p += blockDim.x) {
-        const float e = expf(sc[p] - mx);
-        sc[p] = e;
+    for (int p = p_lo + threadIdx.x; p < n_att; p += blockDim.x) {
+        const float e = expf(sc[p - p_lo] - mx);
+        sc[p - p_lo] = e;
         sum += e;
     }
     sum = block_sum(sum, red + 8);
@@ -346,9 +349,21 @@ __global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k,
     const float inv = 1.f / sum;
     for (int j = threadIdx.x; j < d; j += blockDim.x) {
         float acc = 0.f;
-        for (int p = 0; p < n_att; ++p) acc = fmaf(sc[p], to_f(v[(size_t)kvh * sd.kh + (size_t)p * sd.ks + j]), acc);
+        for (int p = p_lo; p < n_att; ++p) acc = fmaf(sc[p - p_lo], to_f(v[(size_t)kvh * sd.kh + (size_t)p * sd.ks + j]), acc);
         out[(size_t)head * sd.oh + (size_t)qi * sd.os + j] = from_f<T>(acc * inv);
     }
+}
+
+template <class T, bool CAUSAL = true>
+__global__ __launch_bounds__(256) void sdpa_naive_kernel(const T* q, const T* k, const T* v, T* out, int hq, int hkv,
+                                                         int q_len, int kv_len, int d, float scale, FlashStrides sd) {
+    sdpa_naive_row<T, CAUSAL, false>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, 0);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void sdpa_window_naive_kernel(const T* q, const T* k, const T* v, T* out, int hq, int hkv, int q_len,
+                                                                int kv_len, int d, float scale, FlashStrides sd, int window) {
+    sdpa_naive_row<T, true, true>(q, k, v, out, hq, hkv, q_len, kv_len, d, scale, sd, window);
 }
 
 template <class T, int D>
@@ -412,6 +427,29 @@ static pgk_status sdpa_dispatch(const void* q, const void* k, const void* v, voi
     if (!CAUSAL && q_len > 65535) return set_error(PGK_ERR_UNSUPPORTED, "sdpa_noncausal: fallback kernel supports q_len <= 65535 (got %d)", q_len);
     dim3 grid(hq, q_len);
     sdpa_naive_kernel<T, CAUSAL><<<grid, 256, lds, st>>>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, d, scale, sd);
+    PGK_CHECK_HIP(hipGetLastError());
+    return PGK_OK;
+}
+
+// pgk_sdpa_window (and pgk_sdpa_window_fixed_cache's general path): the second-generation flash kernel with the FlashWindow
+// policy at every q_len, or the window form of the fallback.  window >= 1, kv_len >= q_len >= 1.
+static const char* window_leaf(SdpaKernel pick) { return pick == SDPA_FLASH2 ? "window_flash" : "window_rows"; }
+
+template <class T>
+static pgk_status sdpa_window_dispatch(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
+                                       int window, float scale, const FlashStrides& sd, hipStream_t st) {
+    constexpr bool HALF = !std::is_same<T, float>::value;
+    const bool in16 = aligned16(q) && aligned16(k) && aligned16(v), out8 = (reinterpret_cast<uintptr_t>(out) & 7u) == 0;
+    if constexpr (HALF) {
+        if (sdpa_window_pick(HALF, d, in16, out8, sd, !flash_attention_off()) == SDPA_FLASH2)
+            return flash_prefill_window(q, k, v, out, hq, hkv, q_len, kv_len, d, window, scale, sd, std::is_same<T, f16>::value ? 1 : 0, st);
+    }
+    const int w = window < kv_len ? window : kv_len;
+    const size_t lds = (size_t)w * 4;
+    if (lds > 60 * 1024) return set_error(PGK_ERR_UNSUPPORTED, "sdpa_window: fallback kernel supports min(window, kv_len) <= 15360 (got %d)", w);
+    if (q_len > 65535) return set_error(PGK_ERR_UNSUPPORTED, "sdpa_window: fallback kernel supports q_len <= 65535 (got %d)", q_len);
+    sdpa_window_naive_kernel<T><<<dim3(hq, q_len), 256, lds, st>>>((const T*)q, (const T*)k, (const T*)v, (T*)out, hq, hkv, q_len, kv_len, d, scale, sd,
+                                                                  w);
     PGK_CHECK_HIP(hipGetLastError());
     return PGK_OK;
 }
@@ -480,6 +518,68 @@ pgk_status pgk_sdpa_fixed_cache(const void* q, const void* k_cache, const void* 
     const FlashStrides sd{(long long)q_len * d, d, (long long)max_seq * d, d, (long long)q_len * d, d};
     PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_fixed_cache",
                        return (sdpa_dispatch<T, true>(q, k_cache, v_cache, out, hq, hc, q_len, h_context_len, d, scale, sd, st)));
+    return PGK_OK;
+}
+
+pgk_status pgk_sdpa_window(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d, int window,
+                           float scale, int64_t q_stride_h, int64_t q_stride_s, int64_t kv_stride_h, int64_t kv_stride_s, int64_t o_stride_h,
+                           int64_t o_stride_s, pgk_dtype dt, pgk_stream s) {
+    PGK_REQUIRE(q && k && v && out, "pgk_sdpa_window: null pointer");
+    PGK_REQUIRE(hq > 0 && hkv > 0 && hq % hkv == 0, "pgk_sdpa_window: n_heads mismatch (Hq=%d, Hkv=%d)", hq, hkv);
+    PGK_REQUIRE(q_len > 0 && kv_len > 0 && d > 0, "pgk_sdpa_window: bad shape q_len=%d kv_len=%d D=%d", q_len, kv_len, d);
+    PGK_REQUIRE(kv_len >= q_len, "pgk_sdpa_window: kv_len %d < q_len %d", kv_len, q_len);
+    PGK_REQUIRE(window >= 1, "pgk_sdpa_window: window %d < 1", window);
+    PGK_REQUIRE(q_stride_h >= 0 && q_stride_s >= 0 && kv_stride_h >= 0 && kv_stride_s >= 0 && o_stride_h >= 0 && o_stride_s >= 0,
+                "pgk_sdpa_window: negative stride");
+    if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
+    const FlashStrides sd{q_stride_h, q_stride_s, kv_stride_h, kv_stride_s, o_stride_h, o_stride_s};
+    hipStream_t st = resolve_stream(s);
+    PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_window", return (sdpa_window_dispatch<T>(q, k, v, out, hq, hkv, q_len, kv_len, d, window, scale, sd, st)));
+    return PGK_OK;
+}
+
+const char* pgk_sdpa_window_plan(int hq, int hkv, int q_len, int kv_len, int d, int window, pgk_dtype dt, int aligned, int* nsplit) {
+    if (hq <= 0 || hkv <= 0 || hq % hkv || q_len < 1 || kv_len < q_len || d < 1 || window < 1 || !is_float_dtype(dt)) {
+        set_error(PGK_ERR_INVALID, "pgk_sdpa_window_plan: needs Hq %% Hkv == 0, kv_len >= q_len >= 1, head_dim >= 1, window >= 1 and a float dtype "
+                  "(got heads %d/%d, q_len %d, kv_len %d, D %d, window %d, dtype %d)", hq, hkv, q_len, kv_len, d, window, (int)dt);
+        return nullptr;
+    }
+    // aligned: q / k / v on 16 bytes, out on 8, strides multiples of 8 elements - a contiguous [H, S, D] call
+    const FlashStrides sd{8, 8, 8, 8, 8, 8};
+    const SdpaKernel pick = sdpa_window_pick(dt != PGK_F32, d, aligned != 0, aligned != 0, sd, !flash_attention_off());
+    if (nsplit) {
+        const int w = window < kv_len ? window : kv_len;
+        *nsplit = pick == SDPA_FLASH2 ? flash_plan(hq, hkv, q_len, kv_len, window_kv_seen(kv_len, w), d, device_cu_count()).nsplit : 1;
+    }
+    return window_leaf(pick);
+}
+
+pgk_status pgk_sdpa_window_fixed_cache(const void* q, const void* k_cache, const void* v_cache, void* out, int hq, int hc, int capacity, int d,
+                                       int window, int ring, float scale, int h_context_len, const int32_t* ctx_buf, void* workspace,
+                                       pgk_dtype dt, pgk_stream s) {
+    PGK_REQUIRE(q && k_cache && v_cache && out, "pgk_sdpa_window_fixed_cache: null pointer");
+    PGK_REQUIRE(hq > 0 && hc > 0 && hq % hc == 0, "pgk_sdpa_window_fixed_cache: n_heads mismatch (Hq=%d, cache heads=%d)", hq, hc);
+    PGK_REQUIRE(capacity > 0 && d > 0 && window >= 1, "pgk_sdpa_window_fixed_cache: bad shape rows=%d D=%d window=%d", capacity, d, window);
+    // a ring of C rows holds the last C positions: enough when the window fits, or while the context has not wrapped yet
+    PGK_REQUIRE(ctx_buf || (h_context_len > 0 && (h_context_len <= capacity || (ring && window <= capacity))),
+                "pgk_sdpa_window_fixed_cache: invalid context_len %d (cache rows %d, window %d, ring %d)", h_context_len, capacity, window, ring);
+    PGK_REQUIRE(!(ring && ctx_buf) || window <= capacity, "pgk_sdpa_window_fixed_cache: a ring read through ctx_buf needs window %d <= rows %d",
+                window, capacity);
+    if (scale <= 0.f) scale = 1.0f / sqrtf((float)d);
+    hipStream_t st = resolve_stream(s);
+    if (decode_fast(1, d, workspace != nullptr, aligned16(q) && aligned16(k_cache) && aligned16(v_cache), flash_decoding_off(), ctx_buf != nullptr)) {
+        const DecodeWindow ex{h_context_len, ctx_buf, scale, window, ring != 0};
+        const int rows = decode_window_rows(capacity, window);
+        PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_window_fixed_cache", {
+            if (d == 128) return (launch_split_decode<T, 128>(q, k_cache, v_cache, out, workspace, hq, hc, capacity, ex, st, rows));
+            return (launch_split_decode<T, 64>(q, k_cache, v_cache, out, workspace, hq, hc, capacity, ex, st, rows));
+        });
+    }
+    // general path (other head dims, no workspace, unaligned): the window op over the prefix of a linear cache, host length only
+    PGK_REQUIRE(!ctx_buf && !ring, "pgk_sdpa_window_fixed_cache: context_len_buf and ring caches require head_dim 64/128, aligned buffers and a workspace");
+    const FlashStrides sd{d, d, (long long)capacity * d, d, d, d};
+    PGK_DISPATCH_FLOAT(dt, "pgk_sdpa_window_fixed_cache",
+                       return (sdpa_window_dispatch<T>(q, k_cache, v_cache, out, hq, hc, 1, h_context_len, d, window, scale, sd, st)));
     return PGK_OK;
 }
 

@@ -12,6 +12,8 @@
 // ever above a diagonal; q_len may be smaller or larger than kv_len and any q_len >= 1 takes this kernel.
 // With a FlashRelBias it is sdpa_relbias (pgk_sdpa_relbias, ops_relbias.hip): FlashFull's mask, and the accumulators of S^T start
 // at table[head][clamp(kv_pos - q_pos, -R, R) + R] - the head's row staged once into LDS behind the K / V images.
+// With a FlashWindow it is sdpa_sliding_window (pgk_sdpa_window, ops_attention.hip): FlashPlain's mask offset and a lower diagonal
+// `window` keys below it; the tile walk is flash_walk_band (flash_core.hip.h), which starts at the first tile the query tile sees.
 
 #include "flash_core.hip.h"
 
@@ -23,6 +25,7 @@ template <int D> __device__ __forceinline__ int fl_k_off(int r, int c) { return 
 // X = FlashPlain: sdpa_causal.  X = FlashIrope: sdpa_irope - the two differences are `if constexpr (IROPE)` below.
 // X = FlashAlibi: sdpa_alibi - the head's slope and the start value of the score accumulators, `if constexpr (ALIBI)`.
 // X = FlashRelBias: sdpa_relbias - FlashFull's mask offset, the staged table row and the start value, `if constexpr (RELBIAS)`.
+// X = FlashWindow: sdpa_sliding_window - the band walk in place of flash_walk, `if constexpr (WINDOW)`; nothing else differs.
 template <class T, int D, class X = FlashPlain>
 __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, const T* k, const T* vt, T* out, int hq, int hkv,
                                                               int q_len, int kv_len, int kv_pad, float scale_log2e, FlashStrides sd,
@@ -31,6 +34,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
     constexpr bool ALIBI = std::is_same<X, FlashAlibi>::value;
     constexpr bool RELBIAS = std::is_same<X, FlashRelBias>::value;
     constexpr bool FULL = std::is_same<X, FlashFull>::value || RELBIAS;
+    constexpr bool WINDOW = std::is_same<X, FlashWindow>::value;
     constexpr int NC = D / 8;            // 16-byte chunks per K row
     constexpr int KS = D / 16;           // k-steps of Q.K^T
     constexpr int DT = D / 32;           // 32-row tiles of O^T
@@ -180,8 +184,12 @@ __global__ __launch_bounds__(FL_THREADS, 2) void flash_fwd_kernel(const T* q, co
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) asm volatile("" ::"v"(qf[ks].x), "v"(qf[ks].y), "v"(qf[ks].z), "v"(qf[ks].w));
     };
-    flash_walk<T, DT, false>(wk, vst, vt + (size_t)wk.kvh * D * kv_pad, q_len, kv_len, sp.nsplit, ql, h, fl_smem + 2 * K_BYTES, o, m_run, l_run, 1.0f, load_k,
-                             store_k, retire_q, qk);
+    if constexpr (WINDOW)
+        flash_walk_band<T, DT>(wk, ex.window, vst, vt + (size_t)wk.kvh * D * kv_pad, q_len, kv_len, sp.nsplit, ql, h, fl_smem + 2 * K_BYTES, o, m_run,
+                               l_run, load_k, store_k, retire_q, qk);
+    else
+        flash_walk<T, DT, false>(wk, vst, vt + (size_t)wk.kvh * D * kv_pad, q_len, kv_len, sp.nsplit, ql, h, fl_smem + 2 * K_BYTES, o, m_run, l_run, 1.0f, load_k,
+                                 store_k, retire_q, qk);
 
     float inv;
     const float l_tot = flash_row_sum(l_run, inv);
@@ -293,6 +301,14 @@ pgk_status flash_prefill_alibi(const void* q, const void* k, const void* v, cons
 pgk_status flash_prefill_relbias(const void* q, const void* k, const void* v, const float* table, void* out, int hq, int hkv, int q_len,
                                  int kv_len, int d, int radius, float scale, const FlashStrides& sd, int dt16, hipStream_t st) {
     return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, scale, sd, st, FlashRelBias{table, radius}, kv_len);
+}
+
+// kv_len >= q_len, window >= 1.  Past the first window / 128 query tiles every query tile walks the keys of its band, at most
+// window + 127 of them, so that - not kv_len - is what the split is sized by (attn_plan.h: window_kv_seen)
+pgk_status flash_prefill_window(const void* q, const void* k, const void* v, void* out, int hq, int hkv, int q_len, int kv_len, int d,
+                                int window, float scale, const FlashStrides& sd, int dt16, hipStream_t st) {
+    const int w = window < kv_len ? window : kv_len;
+    return flash_launch_any(dt16, d, q, k, v, out, hq, hkv, q_len, kv_len, scale, sd, st, FlashWindow{w}, window_kv_seen(kv_len, w));
 }
 
 // engine entry (fp8 x fp8 prefill, bf16, head_dim 128, q_len > 128): causal attention whose result leaves as the o_proj's fp8

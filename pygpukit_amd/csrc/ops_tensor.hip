@@ -105,6 +105,25 @@ __global__ void kv_write_kernel(const V* new_kv, V* cache, int seq, int hkv, int
     }
 }
 
+// Rolling cache [hc][cap][D]: position p lives in row p % cap (pgk_kv_cache_write_ring; seq <= cap, so no two rows collide)
+template <class V>
+__global__ void kv_write_ring_kernel(const V* new_kv, V* cache, int seq, int hkv, int hc, int cap, int dvecs, int host_pos,
+                                     const int32_t* pos_buf) {
+    const int pos = max(pos_buf ? pos_buf[0] : host_pos, 0);
+    const int rep = hc / hkv;
+    const int row0 = pos % cap;        // one modulo per thread: row0 + s < 2 cap
+    const size_t total = (size_t)seq * hc * dvecs;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int v = (int)(i % dvecs);
+        const size_t t = i / dvecs;
+        const int h = (int)(t % hc);
+        const int s = (int)(t / hc);
+        const int row = row0 + s < cap ? row0 + s : row0 + s - cap;
+        cache[((size_t)h * cap + row) * dvecs + v] = new_kv[((size_t)s * hkv + h / rep) * dvecs + v];
+    }
+}
+
 // ---- argmax over each row; ties -> lowest index -------------------------------------------
 __device__ __forceinline__ void argmax_combine(float& bv, int& bi, float v, int i) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
@@ -265,6 +284,23 @@ pgk_status pgk_kv_cache_write(const void* new_kv, void* cache, int seq, int hkv,
     const int grid = cap_grid((size_t)seq * hc * dvecs);
     PGK_BY_VEC(w, kv_write_kernel<V><<<grid, TN_BLOCK, 0, st>>>((const V*)new_kv, (V*)cache, seq, hkv, hc, max_seq, dvecs,
                                                           h_pos, pos_buf));
+    PGK_LAUNCH_CHECK();
+    return PGK_OK;
+}
+
+pgk_status pgk_kv_cache_write_ring(const void* new_kv, void* cache, int seq, int hkv, int hc, int capacity, int d, int itemsize, int h_pos,
+                                   const int32_t* pos_buf, pgk_stream s) {
+    PGK_REQUIRE(new_kv && cache, "pgk_kv_cache_write_ring: null pointer");
+    PGK_REQUIRE(hkv > 0 && hc > 0 && hc % hkv == 0, "pgk_kv_cache_write_ring: cache heads %d not a multiple of kv heads %d", hc, hkv);
+    PGK_REQUIRE(capacity > 0 && seq >= 0 && seq <= capacity, "pgk_kv_cache_write_ring: %d rows do not fit a ring of %d", seq, capacity);
+    PGK_REQUIRE(pos_buf || (h_pos >= 0 && (long long)h_pos + seq <= INT32_MAX), "pgk_kv_cache_write_ring: bad position %d", h_pos);
+    if (!seq) return PGK_OK;
+    hipStream_t st = resolve_stream(s);
+    const size_t row_bytes = (size_t)d * itemsize;
+    const int w = pick_vec_bytes(row_bytes, addr_bits({new_kv, cache}));
+    const int dvecs = (int)(row_bytes / w);
+    const int grid = cap_grid((size_t)seq * hc * dvecs);
+    PGK_BY_VEC(w, kv_write_ring_kernel<V><<<grid, TN_BLOCK, 0, st>>>((const V*)new_kv, (V*)cache, seq, hkv, hc, capacity, dvecs, h_pos, pos_buf));
     PGK_LAUNCH_CHECK();
     return PGK_OK;
 }

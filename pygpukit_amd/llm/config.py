@@ -134,6 +134,9 @@ def detect_model_spec(tensor_names: list[str]) -> ModelSpec:
     raise ValueError(f"Cannot detect model type from tensor names. First 10 names: {list(tensor_names)[:10]}")
 
 
+LAYER_TYPES = ("sliding_attention", "full_attention")
+
+
 @dataclass
 class TransformerConfig:
     """config.py:440-507.  head_dim defaults to hidden_size // num_heads unless _head_dim is given
@@ -157,8 +160,17 @@ class TransformerConfig:
     norm_eps: float = 1e-5
     rope_theta: float = 10000.0
     tie_word_embeddings: bool = True
+    # Sliding-window attention (Mistral, Qwen2's use_sliding_window, Gemma's local layers): a windowed layer's row sees `sliding_window`
+    # keys, its own included.  layer_types follows HF ("sliding_attention" / "full_attention" per layer); None = every layer.
+    sliding_window: int | None = None
+    layer_types: list[str] | None = None
 
     def __post_init__(self):
+        if self.sliding_window is not None and (isinstance(self.sliding_window, bool) or int(self.sliding_window) < 1):
+            raise ValueError(f"sliding_window must be an integer >= 1 or None, got {self.sliding_window!r}")
+        if self.layer_types is not None:
+            if len(self.layer_types) != self.num_layers or any(t not in LAYER_TYPES for t in self.layer_types):
+                raise ValueError(f"layer_types must name {self.num_layers} layers, each one of {LAYER_TYPES}; got {self.layer_types}")
         if self.num_kv_heads is None:
             self.num_kv_heads = self.num_heads
         if self.intermediate_size is None:
@@ -177,6 +189,34 @@ class TransformerConfig:
     @property
     def num_kv_groups(self) -> int:
         return self.num_heads // self.num_kv_heads
+
+    def layer_window(self, layer: int) -> int | None:
+        """The window of layer `layer`, None for a full-attention layer."""
+        if self.sliding_window is None or (self.layer_types is not None and self.layer_types[layer] != "sliding_attention"):
+            return None
+        return int(self.sliding_window)
+
+    @property
+    def min_window(self) -> int | None:
+        """The smallest window any layer applies, None when every layer sees the whole context."""
+        ws = [w for w in (self.layer_window(i) for i in range(self.num_layers)) if w is not None]
+        return min(ws) if ws else None
+
+
+def sliding_window_fields(hf_config: dict, num_layers: int) -> dict:
+    """sliding_window / layer_types of a HF config.json, as TransformerConfig keywords.  Mistral: `sliding_window` (null = none) on
+    every layer.  `layer_types`, where given, is taken as is.  Qwen2: nothing unless `use_sliding_window`, then the layers from
+    `max_window_layers` on are windowed and the ones below it are not."""
+    w = hf_config.get("sliding_window")
+    if w is None or hf_config.get("use_sliding_window") is False:
+        return {}
+    types = hf_config.get("layer_types")
+    if types is None and "max_window_layers" in hf_config and "use_sliding_window" in hf_config:
+        first = int(hf_config["max_window_layers"])
+        types = ["sliding_attention" if i >= first else "full_attention" for i in range(num_layers)]
+    if types is not None and "sliding_attention" not in types:
+        return {}
+    return dict(sliding_window=int(w), layer_types=list(types) if types is not None else None)
 
 
 # ---- legacy per-family configs (config.py:515-620): HF-style field names, converted to TransformerConfig ----------

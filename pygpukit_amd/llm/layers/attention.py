@@ -25,6 +25,7 @@ from pygpukit_amd.core.factory import from_numpy, zeros
 from pygpukit_amd.ops.basic import (bias_add_inplace, concat_axis0, kv_cache_prefill_gqa, kv_cache_update_gqa, rmsnorm,
                                    rope_inplace, rope_inplace_f32table, sdpa_causal_fixed_cache, sdpa_causal_strided,
                                    split_qkv_batch)
+from pygpukit_amd.ops.nn.window import kv_cache_update_ring, sdpa_sliding_window_fixed_cache, sdpa_sliding_window_strided
 
 from .linear import LinearBF16, LinearFP8
 from .norm import Norm
@@ -37,8 +38,11 @@ if TYPE_CHECKING:
 class Attention:
     def __init__(self, q_proj, k_proj, v_proj, o_proj, config: "TransformerConfig", q_bias: GPUArray | None = None,
                  k_bias: GPUArray | None = None, v_bias: GPUArray | None = None, o_bias: GPUArray | None = None,
-                 q_norm: Norm | None = None, k_norm: Norm | None = None):
+                 q_norm: Norm | None = None, k_norm: Norm | None = None, window: int | None = None):
         self.config = config
+        # sliding-window layer: a row sees `window` keys, its own included (TransformerConfig.layer_window); None = full causal
+        self.window = window
+        self._rolling = False
         self.head_dim = config.head_dim
         self.num_heads = config.num_heads
         self.num_kv_heads: int = config.num_kv_heads
@@ -82,9 +86,12 @@ class Attention:
         self._logical_pos = 0
 
     # ------------------------------------------------------------------ caches / rope tables
-    def init_fixed_cache(self, max_seq_len: int, dtype: str = "float16") -> None:
-        """Fixed-length KV cache [num_kv_heads, max_seq_len, head_dim] (attention.py:128-146, un-expanded here)."""
-        shape = (self.num_kv_heads, max_seq_len, self.head_dim)
+    def init_fixed_cache(self, max_seq_len: int, dtype: str = "float16", rolling: bool = False) -> None:
+        """Fixed-length KV cache [num_kv_heads, max_seq_len, head_dim] (attention.py:128-146, un-expanded here).  rolling=True on a
+        windowed layer: min(max_seq_len, window) rows, position p in row p % rows (a full-attention layer keeps max_seq_len rows)."""
+        self._rolling = bool(rolling) and self.window is not None
+        rows = min(max_seq_len, self.window) if self._rolling else max_seq_len
+        shape = (self.num_kv_heads, rows, self.head_dim)
         self._k_cache = zeros(shape, dtype)
         self._v_cache = zeros(shape, dtype)
         self._max_cache_len = max_seq_len
@@ -175,8 +182,22 @@ class Attention:
         present_kv = (k3, v3) if use_cache else None
         kv_len = k3.shape[0]
         attn = GPUArray((S, Hq * D), x.dtype)
-        sdpa_causal_strided(q3, k3, v3, attn, Hq, Hkv, S, kv_len, D, (D, Hq * D), (D, Hkv * D), (D, Hq * D))
+        if self.window is None:
+            sdpa_causal_strided(q3, k3, v3, attn, Hq, Hkv, S, kv_len, D, (D, Hq * D), (D, Hkv * D), (D, Hq * D))
+        else:
+            sdpa_sliding_window_strided(q3, k3, v3, attn, Hq, Hkv, S, kv_len, D, self.window, (D, Hq * D), (D, Hkv * D), (D, Hq * D))
         return self.o_proj(attn), present_kv
+
+    def write_prompt_kv(self, k: GPUArray, v: GPUArray) -> None:
+        """K / V [S, Hkv, D] of a prompt that starts at position 0 -> the fixed caches; a rolling cache keeps the last `rows`."""
+        S, rows = k.shape[0], self._k_cache.shape[1]
+        for new, cache in ((k, self._k_cache), (v, self._v_cache)):
+            if not self._rolling:
+                kv_cache_prefill_gqa(new, cache, self.num_heads, 0)
+            else:
+                n = min(S, rows)
+                tail = new._view((S - n) * self.num_kv_heads * self.head_dim, (n, self.num_kv_heads, self.head_dim))
+                kv_cache_update_ring(tail, cache, self.num_heads, S - n)
 
     # ------------------------------------------------------------------ fixed cache decode
     def forward_fixed_cache(self, x: GPUArray, position: int, context_len: int, *, out: GPUArray | None = None) -> GPUArray:
@@ -191,10 +212,17 @@ class Attention:
         if self.config.use_rope:
             cos, sin = self._rope_rows(position, 1)
             self._apply_rope(q3, k3, cos, sin)
-        kv_cache_update_gqa(k3, self._k_cache, Hq, position)
-        kv_cache_update_gqa(v3, self._v_cache, Hq, position)
         attn_out = out if out is not None else GPUArray((Hq, 1, D), x.dtype)
-        sdpa_causal_fixed_cache(q.view((Hq, 1, D)), self._k_cache, self._v_cache, attn_out, context_len)
+        if self.window is None:
+            kv_cache_update_gqa(k3, self._k_cache, Hq, position)
+            kv_cache_update_gqa(v3, self._v_cache, Hq, position)
+            sdpa_causal_fixed_cache(q.view((Hq, 1, D)), self._k_cache, self._v_cache, attn_out, context_len)
+        else:
+            write = kv_cache_update_ring if self._rolling else kv_cache_update_gqa
+            write(k3, self._k_cache, Hq, position)
+            write(v3, self._v_cache, Hq, position)
+            sdpa_sliding_window_fixed_cache(q.view((Hq, 1, D)), self._k_cache, self._v_cache, attn_out, context_len, self.window,
+                                            ring=self._rolling)
         return self.o_proj(attn_out.view((1, Hq * D)))
 
     def forward_fixed_cache_batch(self, x: GPUArray, start_position: int, context_len: int) -> GPUArray:
@@ -204,17 +232,29 @@ class Attention:
         if S == 1:
             return self.forward_fixed_cache(x, start_position, context_len)
         Hq, Hkv, D = self.num_heads, self.num_kv_heads, self.head_dim
+        if self._rolling and start_position != 0:
+            raise NotImplementedError("a rolling cache takes one prompt chunk from position 0, then single tokens: rows that a later chunk "
+                                      "needs have been overwritten")
         q, k, v = self._project_qkv(x)
         self._qk_norm(q, k, S)
         q3, k3, v3 = q.view((S, Hq, D)), k.view((S, Hkv, D)), v.view((S, Hkv, D))
         if self.config.use_rope:
             cos, sin = self._rope_rows(start_position, S)
             self._apply_rope(q3, k3, cos, sin)
+        attn = GPUArray((S, Hq * D), x.dtype)
+        if self._rolling:
+            # the prompt attends its own projections (any length); only the last `rows` positions reach the ring
+            self.write_prompt_kv(k3, v3)
+            sdpa_sliding_window_strided(q3, k3, v3, attn, Hq, Hkv, S, S, D, self.window, (D, Hq * D), (D, Hkv * D), (D, Hq * D))
+            return self.o_proj(attn)
         kv_cache_prefill_gqa(k3, self._k_cache, Hq, start_position)
         kv_cache_prefill_gqa(v3, self._v_cache, Hq, start_position)
-        attn = GPUArray((S, Hq * D), x.dtype)
         M = self._max_cache_len
-        sdpa_causal_strided(q3, self._k_cache, self._v_cache, attn, Hq, Hkv, S, context_len, D, (D, Hq * D), (M * D, D), (D, Hq * D))
+        if self.window is None:
+            sdpa_causal_strided(q3, self._k_cache, self._v_cache, attn, Hq, Hkv, S, context_len, D, (D, Hq * D), (M * D, D), (D, Hq * D))
+        else:
+            sdpa_sliding_window_strided(q3, self._k_cache, self._v_cache, attn, Hq, Hkv, S, context_len, D, self.window, (D, Hq * D),
+                                        (M * D, D), (D, Hq * D))
         return self.o_proj(attn)
 
     def forward_fixed_cache_batch_zero_alloc(self, x: GPUArray, start_position: int, context_len: int, buffers=None,

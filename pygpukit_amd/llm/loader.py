@@ -18,7 +18,7 @@ from pygpukit_amd.core.array import GPUArray
 from pygpukit_amd.core.dtypes import bfloat16, float16, float32, uint8
 from pygpukit_amd.core.factory import from_numpy
 from pygpukit_amd.llm.config import (GPT2_SPEC, LLAMA_SPEC, MIXTRAL_SPEC, QWEN3_MOE_SPEC, QWEN3_SPEC, ModelSpec,
-                                     TransformerConfig, detect_model_spec)
+                                     TransformerConfig, detect_model_spec, sliding_window_fields)
 from pygpukit_amd.llm.layers import MLP, Attention, MoELayer, Norm, TransformerBlock
 from pygpukit_amd.llm.layers.linear import LinearBF16, LinearFP8
 from pygpukit_amd.llm.models.causal import CausalTransformerModel
@@ -65,9 +65,10 @@ def load_model_from_safetensors(model_path: str, dtype: str = "bfloat16", spec: 
     if target is None:
         raise ValueError(f"load_model_from_safetensors: unsupported dtype {dtype}")
     target_dt, target_id, target_np = target
-    if spec is None:
-        spec = detect_model_spec(st.tensor_names)
     hf_config = _read_config(model_path)
+    if spec is None:
+        # a Mistral checkpoint carries Llama's tensor names; its window comes from config.json below
+        spec = LLAMA_SPEC if hf_config.get("model_type") == "mistral" else detect_model_spec(st.tensor_names)
     fp8 = FP8QuantConfig.from_config(hf_config)
 
     def load_tensor(name: str, do_transpose: bool = False) -> GPUArray:
@@ -158,7 +159,8 @@ def load_model_from_safetensors(model_path: str, dtype: str = "bfloat16", spec: 
                             activation=spec.activation, use_rope=spec.use_rope,
                             max_position_embeddings=int(hf_config.get("max_position_embeddings", hf_config.get("n_positions", 2048))),
                             norm_eps=float(hf_config.get("rms_norm_eps", hf_config.get("layer_norm_epsilon", spec.default_norm_eps))),
-                            rope_theta=float(hf_config.get("rope_theta", spec.default_rope_theta)), **moe)
+                            rope_theta=float(hf_config.get("rope_theta", spec.default_rope_theta)),
+                            **sliding_window_fields(hf_config, num_layers), **moe)
     eps = cfg.norm_eps
 
     blocks = []
@@ -178,11 +180,12 @@ def load_model_from_safetensors(model_path: str, dtype: str = "bfloat16", spec: 
             biases = [None] * 3 if b is None else [_to_device(np.ascontiguousarray(b[i * hidden_size:(i + 1) * hidden_size]), target_id, target_np)
                                                    for i in range(3)]
             o = load_linear(nm(spec.o_proj, layer), nm(spec.o_bias, layer), spec.weight_transpose)
-            attn = Attention(parts[0], parts[1], parts[2], o, cfg, q_bias=biases[0], k_bias=biases[1], v_bias=biases[2])
+            attn = Attention(parts[0], parts[1], parts[2], o, cfg, q_bias=biases[0], k_bias=biases[1], v_bias=biases[2],
+                             window=cfg.layer_window(layer))
         else:
             attn = Attention(load_linear(nm(spec.q_proj, layer), nm(spec.q_bias, layer)), load_linear(nm(spec.k_proj, layer), nm(spec.k_bias, layer)),
                              load_linear(nm(spec.v_proj, layer), nm(spec.v_bias, layer)), load_linear(nm(spec.o_proj, layer), nm(spec.o_bias, layer)),
-                             cfg, q_norm=qn, k_norm=kn)
+                             cfg, q_norm=qn, k_norm=kn, window=cfg.layer_window(layer))
         if spec.is_moe:
             def ex(pattern: str, e: int, layer=layer):
                 w = load_linear(pattern.format(layer=layer, expert=e))

@@ -132,10 +132,11 @@ class CausalTransformerModel:
                 return
 
     # ------------------------------------------------------------------ fixed-cache decode (eager ops path)
-    def init_fixed_cache(self, max_seq_len: int, dtype: str | None = None) -> None:
+    def init_fixed_cache(self, max_seq_len: int, dtype: str | None = None, rolling: bool = False) -> None:
+        """rolling=True: the windowed layers keep min(max_seq_len, window) rows as a ring (Attention.init_fixed_cache)."""
         dt = dtype or str(self.embed_tokens.dtype)
         for block in self.blocks:
-            block.attn.init_fixed_cache(max_seq_len, dt)
+            block.attn.init_fixed_cache(max_seq_len, dt, rolling=rolling)
 
     def _mlp_forward_zero_alloc(self, mlp: MLP, x: GPUArray, buffers: DecodeBuffers) -> None:
         """MLP of one token into buffers.hidden using the pre-allocated buffers (causal.py:489-514)."""
@@ -170,12 +171,9 @@ class CausalTransformerModel:
     def prefill_fixed_cache(self, input_ids: list[int]) -> GPUArray:
         """Prefill that leaves K/V in the fixed caches (the chat flow's prefill + kv_cache_prefill_gqa,
         examples/chat/chat_cli.py:531-534) -> logits [S, V]."""
-        from pygpukit_amd.ops.basic import kv_cache_prefill_gqa
-
         hidden, present = self(list(input_ids), use_cache=True)
         for block, (k, v) in zip(self.blocks, present):
-            kv_cache_prefill_gqa(k, block.attn._k_cache, block.attn.num_heads, 0)
-            kv_cache_prefill_gqa(v, block.attn._v_cache, block.attn.num_heads, 0)
+            block.attn.write_prompt_kv(k, v)
         return self.get_logits(hidden)
 
     def snapshot_kv_cache(self) -> list[tuple[np.ndarray, np.ndarray]]:
@@ -198,6 +196,9 @@ class CausalTransformerModel:
         c = self.config
         if c.is_moe:
             raise NotImplementedError("the native engine covers dense models")
+        if c.min_window is not None and c.min_window < max_seq_len:
+            raise NotImplementedError(f"the native engine has no sliding-window mask: a window of {c.min_window} keys is smaller than "
+                                      f"max_seq_len {max_seq_len} (use the operator-surface model, or max_seq_len <= the window)")
         if c.norm_type != "rmsnorm" or c.activation != "silu" or not c.use_rope or self.position_embed is not None:
             raise NotImplementedError("the native engine covers RMSNorm + SwiGLU + RoPE models (Llama / Qwen families)")
         if self.embed_tokens.dtype != bfloat16:

@@ -50,8 +50,9 @@ def build_engine_from_weights(cfg: dict, weights: dict, *, max_seq_len: int = 51
                   max_batch=max_batch, weight_format=weight_format, use_qk_norm="q_norm" in weights["layers"][0])
 
 
-def build_model_from_weights(cfg: dict, weights: dict, *, dtype: str = "bfloat16", max_pos: int = 2048):
-    """CausalTransformerModel (Qwen3-style) on the GPU from the oracle weight dict."""
+def build_model_from_weights(cfg: dict, weights: dict, *, dtype: str = "bfloat16", max_pos: int = 2048,
+                             sliding_window: int | None = None, layer_types: list[str] | None = None):
+    """CausalTransformerModel (Qwen3-style) on the GPU from the oracle weight dict; sliding_window / layer_types as TransformerConfig's."""
     from pygpukit_amd.llm.config import QWEN3_SPEC, TransformerConfig
     from pygpukit_amd.llm.layers import MLP, Attention, Norm, TransformerBlock
     from pygpukit_amd.llm.models.causal import CausalTransformerModel
@@ -62,12 +63,13 @@ def build_model_from_weights(cfg: dict, weights: dict, *, dtype: str = "bfloat16
     c = TransformerConfig(vocab_size=cfg["vocab_size"], hidden_size=cfg["hidden_size"], num_layers=cfg["num_layers"],
                           num_heads=cfg["num_heads"], num_kv_heads=cfg["num_kv_heads"], intermediate_size=cfg["intermediate_size"],
                           _head_dim=cfg["head_dim"], norm_type="rmsnorm", activation="silu", use_rope=True,
-                          max_position_embeddings=max_pos, norm_eps=cfg["norm_eps"], rope_theta=cfg["rope_theta"])
+                          max_position_embeddings=max_pos, norm_eps=cfg["norm_eps"], rope_theta=cfg["rope_theta"],
+                          sliding_window=sliding_window, layer_types=layer_types)
     eps = cfg["norm_eps"]
     blocks = []
-    for lw in weights["layers"]:
+    for i, lw in enumerate(weights["layers"]):
         attn = Attention(W(lw["q"]), W(lw["k"]), W(lw["v"]), W(lw["o"]), c, q_norm=Norm(W(lw["q_norm"]), None, "rmsnorm", eps),
-                         k_norm=Norm(W(lw["k_norm"]), None, "rmsnorm", eps))
+                         k_norm=Norm(W(lw["k_norm"]), None, "rmsnorm", eps), window=c.layer_window(i))
         mlp = MLP(c, gate_proj=W(lw["gate"]), up_proj=W(lw["up"]), down_proj=W(lw["down"]))
         blocks.append(TransformerBlock(Norm(W(lw["attn_norm"]), None, "rmsnorm", eps), attn,
                                        Norm(W(lw["mlp_norm"]), None, "rmsnorm", eps), mlp))

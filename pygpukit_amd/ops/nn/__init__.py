@@ -13,6 +13,8 @@ from pygpukit_amd.ops.nn.norm import group_norm, group_norm_plan, group_norm_sil
 from pygpukit_amd.ops.nn.relpos import (relbias_plan, relpos_bias_table, relpos_bucket, relpos_compute_bias, sdpa_relbias,
                                         sdpa_relbias_strided)
 from pygpukit_amd.ops.nn.recurrent import lstm_bidirectional, lstm_forward, lstm_plan
+from pygpukit_amd.ops.nn.window import (kv_cache_update_ring, kv_cache_update_ring_ptr, sdpa_sliding_window, sdpa_sliding_window_fixed_cache,
+                                        sdpa_sliding_window_fixed_cache_ptr, sdpa_sliding_window_strided, sdpa_window_plan)
 from pygpukit_amd.ops.nn.rope import (alibi_add_bias, alibi_compute_bias, alibi_init_slopes, pope_init_encoding, pope_inplace,
                                       rope_init_linear, rope_init_ntk_aware, rope_init_yarn, rope_inplace, rope_inplace_f32table)
 
@@ -26,4 +28,6 @@ __all__ = ["gelu", "silu", "sigmoid", "tanh", "relu2", "sdpa_causal", "sdpa_caus
            "alibi_add_bias", "sdpa_alibi", "sdpa_alibi_strided", "sdpa_alibi_fixed_cache", "sdpa_alibi_fixed_cache_ptr",
            "lstm_forward", "lstm_bidirectional", "lstm_plan", "sdpa_noncausal", "sdpa_noncausal_strided", "ln_linear",
            "ln_linear_plan", "ln_linear_qkv_cache_ptr", "embed_token_position_ptr", "group_norm", "group_norm_silu", "group_norm_plan",
-           "relpos_bucket", "relpos_bias_table", "relpos_compute_bias", "sdpa_relbias", "sdpa_relbias_strided", "relbias_plan", "quick_gelu"]
+           "relpos_bucket", "relpos_bias_table", "relpos_compute_bias", "sdpa_relbias", "sdpa_relbias_strided", "relbias_plan", "quick_gelu",
+           "sdpa_sliding_window", "sdpa_sliding_window_strided", "sdpa_sliding_window_fixed_cache", "sdpa_sliding_window_fixed_cache_ptr",
+           "kv_cache_update_ring", "kv_cache_update_ring_ptr", "sdpa_window_plan"]
