@@ -673,6 +673,22 @@ pgk_status pgk_engine_attn_plan(pgk_engine e, int batch, int max_position, char*
  * K rows, chunk 0's V rows; [3] tiles of 16 rows the wave stages at c0 (0 where c0 >= c1); [4] requests allowed outstanding at
  * the wait for their K rows.  A tile is 4 K and 4 V requests; chunk 0 is always 3 tiles per wave. */
 pgk_status pgk_attn_mfma_plan(int c1, int c0, int wave, int pre, int32_t* out);
+/* The same for any instantiated chunk length (192: 3 tiles per wave; 256: 4, the single-pass kernel of 193..256 cached rows)
+ * and any chunk start c0 >= 0 (a multiple of `chunk`; chunk 0 is staged whole).  out[7 + T]: [0..4] as above; [5] requests
+ * per wave and image of the issue phase; [6] tiles per wave T; [7 + u] 16-bit mask of the rows of the wave's u-th tile
+ * (chunk tile wave + 4 u) that are cached rows - every other staged row carries weight zero. */
+pgk_status pgk_attn_chunk_plan(int chunk, int c1, int c0, int wave, int pre, int32_t* out);
+/* Read-only, no device: out[0] the chunk length a fused single-sequence step with `rows` cached rows takes at a GQA group of G
+ * query heads per kv head (256 for 193..256 rows where that kernel's LDS fits a CU, else 192); out[1], out[2] the LDS bytes
+ * of a workgroup at 192 / 256 rows; out[3] the LDS bytes of a CU. */
+pgk_status pgk_attn_chunk_pick(int G, int rows, int32_t* out);
+/* Read-only: rows per staged chunk of the MFMA attention kernel in one decode step of `batch` sequences with largest position
+ * max_position: 192 or 256 for the fused kernel of one sequence, 192 for its batch form, 0 where the step runs neither.
+ * Eager steps and replays choose with the same function. */
+pgk_status pgk_engine_attn_chunk(pgk_engine e, int batch, int max_position, int* chunk);
+/* Read-only: out[0] chunk length of the last step enqueued or replayed (0: no MFMA attention kernel), out[1] steps on the
+ * 256-row chunk since the engine was created. */
+pgk_status pgk_engine_attn_chunk_state(pgk_engine e, int64_t* out);
 /* Read-only: the PROJECTION launches (w_qkv, w_o, w_gate_up, w_down, lm_head), computed by the functions the launchers
  * themselves call; no device work, no state change.
  * prefill_n == 0: one decode step of `batch` sequences whose largest position is `max_position`.  Per chunk one line

@@ -404,10 +404,12 @@ static pgk_status decode_step(Engine* e, int batch, hipStream_t st, int* launche
 static pgk_status enqueue_step(Engine* e, int batch, hipStream_t st, int advance, int* launches = nullptr, Probe* probe = nullptr) {
     int n = 0;
     e->step_span = span_for(e);
+    e->step_rows = e->pos_hi;
     g_probe = probe;
     const pgk_status r = decode_step(e, batch, st, &n, step_is_short(e, batch));
     g_probe = nullptr;
     if (launches) *launches = n;
+    note_chunk(e, step_chunk_at(e, batch, e->pos_hi));
     if (e->pos_hi >= 0) e->pos_hi += advance;
     return r;
 }
@@ -418,7 +420,18 @@ static void drop_graphs(Engine* e) {
         if (t.graph) (void)hipGraphDestroy(t.graph);
     }
     e->tiers.clear();
+    if (e->short_wide.exec) (void)hipGraphExecDestroy(e->short_wide.exec);
+    if (e->short_wide.graph) (void)hipGraphDestroy(e->short_wide.graph);
+    e->short_wide = Engine::Tier{};
     e->graph_batch = 0;
+}
+
+// The captured step the next replay launches: pick_tier's, or - on exactly the steps an eager step would run the fused
+// kernel's 256-row chunk (step_chunk_at) - the short-context sequence captured with that chunk.
+static const Engine::Tier& pick_graph(const Engine* e) {
+    const size_t ti = pick_tier(e);
+    const bool wide = ti == 0 && e->tiers[0].span == 0 && e->short_wide.exec && step_chunk_at(e, e->graph_batch, e->pos_hi) == AM_CHUNK_WIDE;
+    return wide ? e->short_wide : e->tiers[ti];
 }
 
 }  // namespace pgk
@@ -789,19 +802,26 @@ pgk_status pgk_engine_capture(pgk_engine eh, int batch, pgk_stream s) {
         for (int sp = 1024; sp < e->cfg.max_seq_len; sp *= 2) spans.push_back(sp);
         spans.push_back(e->cfg.max_seq_len);
     }
+    // ... and the short-context sequence a second time where its steps at 193..256 cached rows take the fused kernel's 256-row
+    // chunk (one sequence; a cache that holds such a step): span -1 here, Engine::short_wide
+    if (e->short_path && e->cfg.max_seq_len > AM_CHUNK + 1 && step_chunk_at(e, batch, AM_CHUNK + 1) == AM_CHUNK_WIDE) spans.push_back(-1);
     for (int span : spans) {
         PGK_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
         int launches = 0;
-        e->step_span = span;
-        pgk_status r = decode_step(e, batch, st, &launches, span == 0);
+        const bool wide = span < 0;
+        e->step_span = wide ? 0 : span;
+        e->step_rows = wide ? AM_CHUNK + 1 : 0;     // the chunk choice's input: a row count of the tier (0 rows: the default chunk)
+        pgk_status r = decode_step(e, batch, st, &launches, span <= 0);
         hipGraph_t g = nullptr;
         hipError_t he = hipStreamEndCapture(st, &g);
         if (r != PGK_OK) { if (g) (void)hipGraphDestroy(g); drop_graphs(e); return r; }
         if (he != hipSuccess || !g) { drop_graphs(e); return set_error(PGK_ERR_HIP, "pgk_engine_capture: hipStreamEndCapture: %s", hipGetErrorString(he)); }
         Engine::Tier t;
-        t.span = span; t.graph = g; t.launches = launches;
+        t.span = wide ? 0 : span; t.graph = g; t.launches = launches;
+        t.chunk = span <= 0 ? step_chunk_at(e, batch, e->step_rows) : 0;
         he = hipGraphInstantiate(&t.exec, g, nullptr, nullptr, 0);
-        e->tiers.push_back(t);      // owned from here on (drop_graphs)
+        if (wide) e->short_wide = t;
+        else e->tiers.push_back(t);      // owned from here on (drop_graphs)
         if (he != hipSuccess) { drop_graphs(e); return set_error(PGK_ERR_HIP, "pgk_engine_capture: hipGraphInstantiate: %s", hipGetErrorString(he)); }
     }
     e->graph_batch = batch;
@@ -815,9 +835,10 @@ pgk_status pgk_engine_replay(pgk_engine eh, int n_steps, pgk_stream s) {
     PGK_REQUIRE(!e->tiers.empty(), "pgk_engine_replay: no captured graph (call pgk_engine_capture first)");
     hipStream_t st = resolve_stream(s);
     for (int i = 0; i < n_steps; ++i) {
-        const auto& t = e->tiers[pick_tier(e)];
+        const auto& t = pick_graph(e);
         PGK_CHECK_HIP(hipGraphLaunch(t.exec, st));
         e->launches_per_step = t.launches;
+        note_chunk(e, t.chunk);
         if (e->pos_hi >= 0) ++e->pos_hi;
     }
     return PGK_OK;
@@ -958,7 +979,7 @@ pgk_status pgk_engine_attn_plan(pgk_engine eh, int batch, int max_position, char
     for (int b0 = 0; b0 < batch;) {
         const ChunkChoice ch = next_chunk(e, batch - b0);
         const AttnFlags af = attn_flags(e, ch.form, ch.m, short_ctx);
-        const AttnChoice pick = attn_choice(e, ch.m, step_span, af);
+        const AttnChoice pick = attn_choice(e, ch.m, step_span, af, max_position);
         char heads[64];
         size_t hu = 0;
         for (int off = 0; off < G; off += head_chunk(G, off))
@@ -969,6 +990,68 @@ pgk_status pgk_engine_attn_plan(pgk_engine eh, int batch, int max_position, char
         used += (size_t)w;
         b0 += ch.m;
     }
+    return PGK_OK;
+}
+
+// Read-only: the rows per staged chunk of the MFMA attention kernel in ONE decode step of `batch` sequences whose largest
+// position is `max_position` (pgk_engine_attn_plan's step), from the function the eager step, the capture and the replay call
+// (step_chunk_at); 0 where the step runs neither the fused kernel nor its batch form.
+pgk_status pgk_engine_attn_chunk(pgk_engine eh, int batch, int max_position, int* chunk) {
+    PGK_REQUIRE(eh && chunk, "pgk_engine_attn_chunk: null argument");
+    const Engine* e = (const Engine*)eh;
+    PGK_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch, "pgk_engine_attn_chunk: batch %d outside [1,%d]", batch, e->cfg.max_batch);
+    PGK_REQUIRE(max_position >= 0 && max_position < e->cfg.max_seq_len, "pgk_engine_attn_chunk: position %d outside cache of %d", max_position,
+                e->cfg.max_seq_len);
+    *chunk = step_chunk_at(e, batch, max_position);
+    return PGK_OK;
+}
+
+// Read-only: out[0] = the chunk length of the last step enqueued or replayed (0: it ran no MFMA attention kernel),
+// out[1] = the steps enqueued or replayed on the 256-row chunk since the engine was created.
+pgk_status pgk_engine_attn_chunk_state(pgk_engine eh, int64_t* out) {
+    PGK_REQUIRE(eh && out, "pgk_engine_attn_chunk_state: null argument");
+    const Engine* e = (const Engine*)eh;
+    out[0] = e->last_chunk;
+    out[1] = e->wide_steps;
+    return PGK_OK;
+}
+
+// Read-only, no device: the chunk length a fused single-sequence step of `rows` cached rows takes at a GQA group of G
+// (am_pick_chunk: what attn_chunk_for returns on the fused MFMA path), and the LDS bytes of a workgroup at G per chunk length.
+//   out[0] chunk   [1] LDS bytes at 192 rows   [2] LDS bytes at 256 rows   [3] LDS bytes of a CU
+pgk_status pgk_attn_chunk_pick(int G, int rows, int32_t* out) {
+    PGK_REQUIRE(out && G >= 1 && G <= 64, "pgk_attn_chunk_pick: bad argument");
+    out[0] = am_pick_chunk(G, rows);
+    out[1] = am_lds_bytes(G, AM_CHUNK);
+    out[2] = am_lds_bytes(G, AM_CHUNK_WIDE);
+    out[3] = AM_LDS_CU;
+    return PGK_OK;
+}
+
+// Read-only, no device: pgk_attn_mfma_plan for any instantiated chunk length, and for chunk 0 too (c0 = 0: staged whole).
+//   out[0..2] waits of the issue phase   [3] tiles staged at c0   [4] wait for their K   [5] requests per wave and image of the
+//   issue phase   [6] tiles per wave T   [7 .. 7 + T) per tile u of the wave (chunk tile wave + 4 u): 16-bit mask of its live rows
+pgk_status pgk_attn_chunk_plan(int chunk, int c1, int c0, int wave, int pre, int32_t* out) {
+    PGK_REQUIRE(out && am_chunk_valid(chunk) && c1 >= 0 && wave >= 0 && wave < AM_WAVES && c0 >= 0 && c0 % chunk == 0 && (pre == 0 || pre == 4),
+                "pgk_attn_chunk_plan: bad argument");
+    auto fill = [&](auto cc) {
+        constexpr int CH = decltype(cc)::value, T = am_tiles_per_wave<CH>();
+        const int n = c0 == 0 ? T : (c0 < c1 ? am_live_tiles<CH>(c0, c1, wave) : 0);
+        out[0] = am_wait_new<CH>(pre);
+        out[1] = am_wait_k0<CH>(pre);
+        out[2] = am_wait_v0(pre);
+        out[3] = n;
+        out[4] = am_wait_k(n);
+        out[5] = T * AM_TILE_REQ;
+        out[6] = T;
+        for (int u = 0; u < T; ++u) {
+            int mask = 0;
+            for (int rl = 0; rl < 16; ++rl) mask |= am_row_live(c0, c1, wave + AM_WAVES * u, rl >> 2, rl & 3) ? 1 << rl : 0;
+            out[7 + u] = mask;
+        }
+    };
+    if (chunk == AM_CHUNK_WIDE) fill(std::integral_constant<int, AM_CHUNK_WIDE>{});
+    else fill(std::integral_constant<int, AM_CHUNK>{});
     return PGK_OK;
 }
 

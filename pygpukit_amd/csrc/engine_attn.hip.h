@@ -416,8 +416,12 @@ __device__ __forceinline__ void am_wait_vm() {
     static_assert(N >= 0 && N <= 63, "vmcnt holds 6 bits");
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-template <int (*COUNT)(int)>
+template <int (*COUNT)(int), int T = 3>
 __device__ __forceinline__ void am_wait_vm_tiles(int n) {
+    static_assert(T == 3 || T == 4, "three or four tiles per wave");
+    if constexpr (T == 4) {
+        if (n >= 4) { am_wait_vm<COUNT(4)>(); return; }
+    }
     if (n >= 3) am_wait_vm<COUNT(3)>();
     else if (n == 2) am_wait_vm<COUNT(2)>();
     else if (n == 1) am_wait_vm<COUNT(1)>();
@@ -438,7 +442,7 @@ __device__ __forceinline__ int am_voff(int row, int ch) { return row * 256 + ((c
 // consumers are the position load, the V requests and the W_o preloads.
 // Grid: fused form (Hkv, H / rows_per_block, 1) - kv head in x, row slice in y: no division, and the linear workgroup id
 // (kv head fastest: XCD-aware, attn_oproj_kernel) is what it was; batch form (Hkv, 1, B).
-template <int G, bool OPROJ = true>
+template <int G, bool OPROJ = true, int CHUNK = AM_CHUNK>
 __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_, bf16* kcache_, const float* rope_cos_, const float* rope_sin_,
                                                               const bf16* q_gamma_, const bf16* k_gamma_, int hkv_, int max_seq_,
                                                               unsigned long long* tl, AttnArgs a) {
@@ -448,9 +452,10 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
     typedef short am_v4s __attribute__((ext_vector_type(4)));
     constexpr int D = 128, NWV = 4, LPR = 16, RS = D + 4;   // a state record: o[128], then m, l (16-byte aligned rows)
     constexpr int GD = G * D, LPW = GD / 8, RPP = NWV * 64 / LPW, PRE = OPROJ ? 4 : 0;
-    extern __shared__ __attribute__((aligned(16))) char am_lds[];          // K image | V image (AM_CHUNK rows x 256 bytes each)
+    constexpr int T = am_tiles_per_wave<CHUNK>();                          // tiles per wave and chunk
+    extern __shared__ __attribute__((aligned(16))) char am_lds[];          // K image | V image (CHUNK rows x 256 bytes each)
     char* k_lds = am_lds;
-    char* v_lds = am_lds + AM_CHUNK * 256;
+    char* v_lds = am_lds + CHUNK * 256;
     __shared__ __attribute__((aligned(16))) float part[NWV + 1][G][RS];    // (o[128], m, l) of the four waves + the new token
     __shared__ __attribute__((aligned(16))) float attn[GD];
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -519,16 +524,16 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
             voff[r] = wq + 1024 * r + ((uint32_t)(l15 ^ (4 * q4 + r)) << 4);
         }
     }
-    static_assert(AM_CHUNK == 16 * 3 * NWV, "a chunk is three 16-row tiles per wave: 12 K and 12 V requests per wave");
-    constexpr int NREQ = AM_CHUNK / 4 / NWV;              // requests per wave and image
-    // ntile: the wave's first ntile tiles only (wave-uniform; chunk 0: the constant 3) - its last row is below c0 + 64 ntile,
+    static_assert(CHUNK == 16 * T * NWV && (T == 3 || T == 4), "a chunk is T 16-row tiles per wave: 4 T K and 4 T V requests per wave");
+    constexpr int NREQ = CHUNK / 4 / NWV;                 // requests per wave and image
+    // ntile: the wave's first ntile tiles only (wave-uniform; chunk 0: the constant T) - its last row is below c0 + 64 ntile,
     // which is what (a) asks of the cache.
     auto stage_image = [&](const bf16* head, const uint32_t (&off)[4], uint32_t lds_img, int c0, int ntile) {
         const bf16* base = head + (size_t)c0 * D;
         const uint32_t dst = lds_img + wid * 4096;
         if (c0 + 64 * ntile <= max_seq_) {                // (a)
 #pragma unroll
-            for (int u = 0; u < 3; ++u)
+            for (int u = 0; u < T; ++u)
                 if (u < ntile) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) lds_dma16_so(base + u * 64 * D, off[r], dst + u * 16384 + r * 1024);
@@ -536,21 +541,21 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
         } else {                                          // (b)
             const uint32_t last = (uint32_t)(max_seq_ - 1 - c0) << 8;
 #pragma unroll
-            for (int u = 0; u < 3; ++u)
+            for (int u = 0; u < T; ++u)
                 if (u < ntile) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) lds_dma16_so(base, min(off[r] + 16384u * u, last | (off[r] & 0xF0u)), dst + u * 16384 + r * 1024);
                 }
         }
     };
-    stage_image(kc, koff, lds_addr_of(k_lds), 0, 3);
+    stage_image(kc, koff, lds_addr_of(k_lds), 0, T);
     __builtin_amdgcn_sched_barrier(0);
     // From here on the struct.  The position first: read through the constant address space it is a scalar load the compiler
     // counts itself - issued here, ahead of the V requests, waited for where the value is first used (positions[] is not
     // written by this launch, and the dispatch invalidated the scalar cache, which load_uniform_i32 relies on too).
     const int pos = *(const __attribute__((address_space(4))) int32_t*)(a.positions + b);
     const bf16* vc = a.vcache + head_off;
-    stage_image(vc, voff, lds_addr_of(v_lds), 0, 3);
+    stage_image(vc, voff, lds_addr_of(v_lds), 0, T);
     const int r0 = rb * a.rows_per_block;
     const int npass = a.rows_per_block / RPP;
     const bf16* wbase = a.w_o + (size_t)kvh * GD + lr * 8;
@@ -564,14 +569,17 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
     // loads.  A wait for "at most n outstanding" therefore means: everything but the n youngest has landed.  The counts are
     // attn_tail_plan.h's: am_wait_new = the whole chunk + W_o, am_wait_k0 = chunk 0's V rows + W_o, am_wait_v0 = W_o; later
     // chunks (W_o long landed - it is older) am_wait_k = the V rows of the wave's live tiles, then 0.
-    static_assert(NREQ == 3 * AM_TILE_REQ && am_wait_new(PRE) == 2 * NREQ + PRE && am_wait_k0(PRE) == NREQ + PRE && am_wait_v0(PRE) == PRE &&
-                      am_wait_k(3) == NREQ && am_wait_k(2) == 8 && am_wait_k(1) == 4 && am_wait_k(0) == 0,
+    static_assert(NREQ == T * AM_TILE_REQ && am_wait_new<CHUNK>(PRE) == 2 * NREQ + PRE && am_wait_k0<CHUNK>(PRE) == NREQ + PRE && am_wait_v0(PRE) == PRE &&
+                      am_wait_k(T) == NREQ && am_wait_k(3) == 12 && am_wait_k(2) == 8 && am_wait_k(1) == 4 && am_wait_k(0) == 0,
                   "wait counts follow the request order above");
-    am_wait_vm<am_wait_new(PRE)>();
+    am_wait_vm<am_wait_new<CHUNK>(PRE)>();
     // The new token's G + 2 head vectors (q heads, k, v) are SPLIT over the waves - item i goes to wave i % 4 - instead of
     // every wave normalising and rotating all of them (0.74 us of ALU per wave in attn_oproj_kernel): each wave reads its
     // item from its own copy of the inputs, and the results meet in LDS behind the barrier that the cache chunk needs anyway.
     __shared__ __attribute__((aligned(16))) uint4 q_sh[G][16], k_sh[16], v_sh[16];   // bf16, 16 chunks of 8 dims per vector
+    static_assert(2 * CHUNK * 256 + sizeof(part) + sizeof(attn) + sizeof(raw_lds) + sizeof(q_sh) + sizeof(k_sh) + sizeof(v_sh) == am_lds_bytes(G, CHUNK) &&
+                      am_chunk_fits(G, CHUNK),
+                  "attn_tail_plan.h counts this kernel's LDS, and the chunk length fits the CU");
     {
         const char* slot = &raw_lds[wid][0];
         const int sub = l15;                                 // the lane's 8 dims: sub * 8 .. + 8 (all four lane quarters compute the same)
@@ -626,7 +634,7 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
 #pragma unroll
     for (int i = 0; i < D / 16; ++i) o[i] = am_f32x4{0.f, 0.f, 0.f, 0.f};
     const int tq = l15 >> 2, tp = l15 & 3;
-    for (int c0 = 0; c0 == 0 || c0 < c1; c0 += AM_CHUNK) {
+    for (int c0 = 0; c0 == 0 || c0 < c1; c0 += CHUNK) {
         if (c0 > 0) {
             // The position is long known: a wave requests only its live tiles - the test the consumer below makes - so a
             // context that ends early in the chunk costs the requests of what it holds, not 24 per wave (context 194 against
@@ -634,13 +642,13 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
             // Dead tiles keep the previous chunk's rows: finite cache rows under weights of zero, as the clamped rows were.
             // no barrier: a wave overwrites only the image rows it alone reads, and its reads of the previous chunk have
             // returned (their values went through the MFMAs above; the asm statements keep the compiler's order)
-            const int nlive = __builtin_amdgcn_readfirstlane(am_live_tiles(c0, c1, wid));
+            const int nlive = __builtin_amdgcn_readfirstlane(am_live_tiles<CHUNK>(c0, c1, wid));
             stage_image(kc, koff, lds_addr_of(k_lds), c0, nlive);
             stage_image(vc, voff, lds_addr_of(v_lds), c0, nlive);
-            am_wait_vm_tiles<am_wait_k>(nlive);
+            am_wait_vm_tiles<am_wait_k, T>(nlive);
         } else {
             __syncthreads();                               // publishes q_sh / k_sh / v_sh; in front of the waits, so no wave idles at it with its rows landed
-            am_wait_vm<am_wait_k0(PRE)>();
+            am_wait_vm<am_wait_k0<CHUNK>(PRE)>();
         }
         __builtin_amdgcn_sched_barrier(0);
         if (c0 == 0) {
@@ -676,10 +684,10 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
             }
         }
         // S^T tiles of this wave: rows = positions c0 + 16 t + 4 q4 + r, column = head l15
-        am_f32x4 s[3];
+        am_f32x4 s[T];
         float mx = -INFINITY;
 #pragma unroll
-        for (int u = 0; u < 3; ++u) {
+        for (int u = 0; u < T; ++u) {
             const int tile = wid + NWV * u;
             s[u] = am_f32x4{0.f, 0.f, 0.f, 0.f};
             if (c0 + 16 * tile < c1) {                     // wave-uniform
@@ -691,7 +699,7 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const bool ok = c0 + 16 * tile + 4 * q4 + r < c1;
+                const bool ok = am_row_live(c0, c1, tile, q4, r);
                 s[u][r] = ok ? s[u][r] : -INFINITY;
                 mx = fmaxf(mx, s[u][r]);
             }
@@ -701,9 +709,9 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
         const float m_new = fmaxf(m_run, mx);
         const float alpha = (m_new == -INFINITY) ? 1.f : __expf(m_run - m_new);
         float ls = 0.f;
-        uint32_t pk[3][2];
+        uint32_t pk[T][2];
 #pragma unroll
-        for (int u = 0; u < 3; ++u) {
+        for (int u = 0; u < T; ++u) {
             float p[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) p[r] = (m_new == -INFINITY) ? 0.f : __expf(s[u][r] - m_new);
@@ -719,15 +727,21 @@ __global__ __launch_bounds__(256) void attn_oproj_mfma_kernel(const float* qkv_,
         for (int i = 0; i < D / 16; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[i][r] *= alpha;
-        // O^T += V^T . P^T: step 0 pairs tiles (wid, wid + 4), step 1 tile wid + 8 with zeros - all three this wave's own requests
+        // O^T += V^T . P^T: step 0 pairs tiles (wid, wid + 4), step 1 tile wid + 8 with zeros (T = 3) or with tile wid + 12
+        // (T = 4) - all of them this wave's own requests
         if (c0 > 0) am_wait_vm<0>();
         else am_wait_vm<am_wait_v0(PRE)>();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int st2 = 0; st2 < 2; ++st2) {
-            const int ta = wid + NWV * (2 * st2), tb = (st2 == 0) ? wid + NWV : ta;     // tb of step 1: any staged tile (weights zero)
+            const int ta = wid + NWV * (2 * st2);
+            int tb;
+            if constexpr (T == 3) tb = (st2 == 0) ? wid + NWV : ta;     // tb of step 1: any staged tile (weights zero)
+            else tb = ta + NWV;
             if (c0 + 16 * ta < c1) {                       // wave-uniform
-                const uint4 pf = make_uint4(pk[2 * st2][0], pk[2 * st2][1], st2 == 0 ? pk[1][0] : 0u, st2 == 0 ? pk[1][1] : 0u);
+                uint4 pf;
+                if constexpr (T == 3) pf = make_uint4(pk[2 * st2][0], pk[2 * st2][1], st2 == 0 ? pk[1][0] : 0u, st2 == 0 ? pk[1][1] : 0u);
+                else pf = make_uint4(pk[2 * st2][0], pk[2 * st2][1], pk[2 * st2 + 1][0], pk[2 * st2 + 1][1]);
                 const int ra = 16 * ta + 4 * q4 + tq, rbv = 16 * tb + 4 * q4 + tq;
 #pragma unroll
                 for (int i = 0; i < D / 16; ++i) {
@@ -941,19 +955,19 @@ __global__ __launch_bounds__(256) void attn_merge_oproj_kernel(unsigned long lon
     tls.end();
 }
 
-template <int G, bool OPROJ = true>
+template <int G, bool OPROJ = true, int CHUNK = AM_CHUNK>
 static hipError_t launch_attn_mfma(dim3 grid, hipStream_t st, const AttnArgs& a) {
-    constexpr int lds = 2 * AM_CHUNK * 256;
+    constexpr int lds = 2 * CHUNK * 256;
     static bool attr = false;
     if (!attr) {
-        const hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_oproj_mfma_kernel<G, OPROJ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        const hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_oproj_mfma_kernel<G, OPROJ, CHUNK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (he != hipSuccess) return he;
         attr = true;
     }
     // what the kernel derives instead of fetching: its GQA group is the whole of G, and the qkv row is q, k, v back to back
     if (a.hq != G * a.hkv || a.g_total != G || a.g_off != 0 || a.qkv_ld != (a.hq + 2 * a.hkv) * 128) return hipErrorInvalidValue;
     // the eight leading arguments fill the 14 preloaded dwords; the timeline pointer is the ninth
-    return launch_k<8>(attn_oproj_mfma_kernel<G, OPROJ>, grid, dim3(256), lds, st, a.qkv, a.kcache, a.rope_cos, a.rope_sin, a.q_gamma, a.k_gamma, a.hkv, a.max_seq, a);
+    return launch_k<8>(attn_oproj_mfma_kernel<G, OPROJ, CHUNK>, grid, dim3(256), lds, st, a.qkv, a.kcache, a.rope_cos, a.rope_sin, a.q_gamma, a.k_gamma, a.hkv, a.max_seq, a);
 }
 
 // f(std::integral_constant<int, G>) for the GQA group sizes the attention kernels are instantiated for
@@ -972,8 +986,10 @@ static hipError_t launch_attn_decode(bool direct, dim3 grid, hipStream_t st, con
 // place where this is decided.  launch_attn_d executes the choice; pgk_engine_attn_plan prints it.
 enum AttnKernel { AK_FUSED_MFMA = 0, AK_FUSED_DOT2, AK_DIRECT_MFMA, AK_DIRECT, AK_SPLIT };
 enum AttnTail { AT_NONE = 0, AT_MERGE, AT_MERGE_OPROJ_BF16, AT_MERGE_OPROJ_FP8 };
-struct AttnChoice { AttnKernel kernel; AttnTail tail; int nsplit, span; bool out_bf16; };
-inline AttnChoice attn_choice(const Engine* e, int m, int step_span, const AttnFlags& f) {
+struct AttnChoice { AttnKernel kernel; AttnTail tail; int nsplit, span; bool out_bf16; int chunk; };   // chunk: rows per staged chunk of the MFMA kernels (0: another kernel)
+// step_rows: the host-side bound of the step's cached rows (Engine::pos_hi; -1 unknown).  Only the fused kernel of one
+// sequence has a second chunk length (attn_tail_plan.h: am_pick_chunk); the batch form stays on 192 rows.
+inline AttnChoice attn_choice(const Engine* e, int m, int step_span, const AttnFlags& f, int step_rows) {
     const auto& c = e->cfg;
     const int D = c.head_dim, G = c.num_heads / c.num_kv_heads;
     AttnChoice ch{};
@@ -994,9 +1010,24 @@ inline AttnChoice attn_choice(const Engine* e, int m, int step_span, const AttnF
     else if (f.fused) ch.kernel = (D == 128 && e->attn_mfma) ? AK_FUSED_MFMA : AK_FUSED_DOT2;
     else if (f.direct) ch.kernel = (D == 128 && e->attn_mfma && m * (int)c.num_kv_heads <= e->cu_count) ? AK_DIRECT_MFMA : AK_DIRECT;
     else ch.kernel = AK_SPLIT;
+    ch.chunk = ch.kernel == AK_FUSED_MFMA ? attn_chunk_for(e, m, f, step_rows) : (ch.kernel == AK_DIRECT_MFMA ? AM_CHUNK : 0);
     const bool f8 = c.weight_format == 1 || c.weight_format == 2;
     ch.tail = f.merged ? (f8 ? AT_MERGE_OPROJ_FP8 : AT_MERGE_OPROJ_BF16) : ((!f.fused && !f.direct) ? AT_MERGE : AT_NONE);
     return ch;
+}
+
+// Rows per staged chunk of the MFMA attention kernels in a whole step of `batch` sequences at the position bound pos_hi, from
+// the choice every chunk of the step makes (0: no chunk of the step runs them).  Eager steps, the capture and the replay ask this.
+inline int step_chunk_at(const Engine* e, int batch, int pos_hi) {
+    const bool short_ctx = step_is_short_at(e, batch, pos_hi);
+    int chunk = 0;
+    for (int b0 = 0; b0 < batch;) {
+        const ChunkChoice ch = next_chunk(e, batch - b0);
+        const AttnChoice pick = attn_choice(e, ch.m, span_for_at(e, pos_hi), attn_flags(e, ch.form, ch.m, short_ctx), pos_hi);
+        chunk = pick.chunk > chunk ? pick.chunk : chunk;
+        b0 += ch.m;
+    }
+    return chunk;
 }
 
 // `fused`: attention + o_proj partials in one kernel (one sequence at short context); `direct`: one workgroup per
@@ -1022,7 +1053,7 @@ static pgk_status launch_attn_d(const StepCtx& cx, int layer, const AttnFlags& a
     a.kcache = e->kcache + lofs; a.vcache = e->vcache + lofs;
     a.positions = e->positions + b0;
     a.hq = c.num_heads; a.hkv = c.num_kv_heads; a.max_seq = c.max_seq_len;
-    const AttnChoice pick = attn_choice(e, m, e->step_span, af);
+    const AttnChoice pick = attn_choice(e, m, e->step_span, af, e->step_rows);
     a.span = pick.span;
     a.scale = 1.0f / sqrtf((float)D);
     a.part = e->part + (size_t)b0 * c.num_heads * e->nsplit * (D + 2);
@@ -1053,7 +1084,13 @@ static pgk_status launch_attn_d(const StepCtx& cx, int layer, const AttnFlags& a
         he = with_group(G, [&](auto g) {
             constexpr int GG = decltype(g)::value;
             if constexpr (D == 128) {
-                if (pick.kernel == AK_FUSED_MFMA) return launch_attn_mfma<GG>(dim3(c.num_kv_heads, c.hidden_size / e->oproj_rows, m), st, a);   // kv head in x, row slice in y
+                if (pick.kernel == AK_FUSED_MFMA) {
+                    const dim3 fg(c.num_kv_heads, c.hidden_size / e->oproj_rows, m);      // kv head in x, row slice in y
+                    if constexpr (am_chunk_fits(GG, AM_CHUNK_WIDE)) {
+                        if (pick.chunk == AM_CHUNK_WIDE) return launch_attn_mfma<GG, true, AM_CHUNK_WIDE>(fg, st, a);
+                    }
+                    return pick.chunk == AM_CHUNK ? launch_attn_mfma<GG>(fg, st, a) : hipErrorInvalidValue;
+                }
                 if (pick.kernel == AK_DIRECT_MFMA) return launch_attn_mfma<GG, false>(dim3(c.num_kv_heads, 1, m), st, a);
             }
             if (pick.kernel == AK_FUSED_DOT2) return launch_k(attn_oproj_kernel<D, GG>, grid, dim3(256), 0, st, a);

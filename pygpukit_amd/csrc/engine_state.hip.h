@@ -6,6 +6,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "attn_tail_plan.h"
 #include "engine_common.hip.h"
 
 namespace pgk {
@@ -13,6 +14,7 @@ namespace pgk {
 constexpr int SHORT_CTX = 512;   // contexts up to here take the whole-context attention kernels (direct batch attention); one sequence: SHORT_CTX_B1
 constexpr int SHORT_CTX_B1 = 384; // a single sequence's fused attention + o_proj kernel walks the context in chunks of 192 rows (AM_CHUNK) in EVERY one of its
                                   // 256 workgroups: two chunks still beat the split-KV sequence (context 300: 0.616 vs 0.625 ms per step), three do not (400: 0.678 vs 0.627)
+                                  // (193..256 cached rows: ONE chunk of 256 rows where that kernel fits, attn_chunk_for)
 
 struct Engine {
     pgk_model_config_t cfg;
@@ -70,10 +72,16 @@ struct Engine {
     int pf_tokens_cap = 0;
     // captured steps: tier 0 = the short-context sequence (span 0); the others = the split-KV sequence with its slices cut for
     // contexts up to `span` positions (1024, 2048, ... and the cache length).  pgk_engine_replay picks per step (pick_tier).
-    struct Tier { int span = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int launches = 0; };
+    // short_wide: the short-context sequence once more with the fused kernel's 256-row chunk, where a step can take it
+    // (attn_chunk_for); replay takes it instead of tier 0 on exactly those steps (pick_graph).
+    struct Tier { int span = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int launches = 0; int chunk = 0; };
     std::vector<Tier> tiers;
+    Tier short_wide;
     int graph_batch = 0;
     int step_span = 0;          // the split-KV slicing of the step being enqueued (launch_attn); 0: the whole cache
+    int step_rows = -1;         // the bound on the cached rows of the step being enqueued (pos_hi then; a capture: a row count of the tier); -1: unknown
+    int last_chunk = 0;         // chunk length of the MFMA attention kernel in the last step enqueued or replayed (0: the step ran another kernel)
+    long long wide_steps = 0;   // steps enqueued or replayed on the 256-row chunk so far
     int launches_per_step = 0;
     std::vector<void*> allocs;
 
@@ -167,6 +175,22 @@ inline AttnFlags attn_flags(const Engine* e, ChunkForm form, int M, bool short_c
     // long contexts (or fp8 W_o): split-KV slices, then merge + o_proj partials in one launch; the gate/up prologue adds them
     const bool merged = !fused && !direct && M <= 2 && e->merged_oproj;
     return {fused, direct, false, merged};
+}
+
+// Rows per staged chunk of the fused MFMA attention of one sequence whose step has `rows` cached rows (the host-side bound: the
+// new token's position; -1 unknown): 256 where one pass then covers a context that takes two passes of 192 (193..256 rows), the
+// kernel is the MFMA one and its LDS fits at this GQA group; 192 otherwise.  Like the tier, a speed hint: either kernel is
+// correct at any context.
+inline bool attn_fused_mfma(const Engine* e, int M, const AttnFlags& f) {
+    const int G = e->cfg.num_heads / e->cfg.num_kv_heads;
+    return f.fused && M == 1 && e->cfg.head_dim == 128 && e->attn_mfma && (G == 1 || G == 2 || G == 4);
+}
+inline int attn_chunk_for(const Engine* e, int M, const AttnFlags& f, int rows) {
+    return attn_fused_mfma(e, M, f) ? am_pick_chunk(e->cfg.num_heads / e->cfg.num_kv_heads, rows) : AM_CHUNK;
+}
+inline void note_chunk(Engine* e, int chunk) {
+    e->last_chunk = chunk;
+    if (chunk == AM_CHUNK_WIDE) ++e->wide_steps;
 }
 
 // GQA groups other than the instantiated 1 / 2 / 4 query heads per kv head run as several launches over head chunks of

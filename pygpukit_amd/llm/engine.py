@@ -247,6 +247,20 @@ class Engine:
             out.append({k: int(v) if k in ("b0", "m", "nsplit", "span") else v for k, v in d.items()})
         return out
 
+    def attn_chunk(self, batch: int = 1, max_position: int = 0) -> int:
+        """Rows per staged chunk of the fused MFMA attention kernel in one decode step of `batch` sequences with largest
+        position `max_position` (192 or 256; 0 where the step runs neither that kernel nor its batch form).  Read-only, like attn_plan."""
+        n = C.c_int()
+        _hip.call("pgk_engine_attn_chunk", self.handle, batch, max_position, C.byref(n))
+        return n.value
+
+    def attn_chunk_state(self) -> tuple[int, int]:
+        """(chunk length of the last step enqueued or replayed - 0: it ran no MFMA attention kernel -, steps run on the
+        256-row chunk since the engine was created)."""
+        out = (C.c_int64 * 2)()
+        _hip.call("pgk_engine_attn_chunk_state", self.handle, out)
+        return int(out[0]), int(out[1])
+
     @staticmethod
     def _plan_fields(line: str) -> dict:
         d = dict(kv.split("=", 1) for kv in line.split()[1:])
