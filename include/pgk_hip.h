@@ -560,6 +560,28 @@ pgk_status pgk_sdpa_window_fixed_cache(const void* q, const void* k_cache, const
 pgk_status pgk_kv_cache_write_ring(const void* new_kv, void* cache, int seq, int hkv, int hc, int capacity, int d, int itemsize, int h_pos,
                                    const int32_t* pos_buf, pgk_stream s);
 
+/* ---- FP8 (OCP e4m3) KV cache (ops_kv_fp8.hip) --------------------------------------------------------------------------------
+ * Cache [hkv, max_seq, d] in uint8, un-expanded only; k_scale[hkv] / v_scale[hkv] fp32 on the device, value = e4m3(code) * scale.
+ * code = rne_e4m3(clamp(x / scale, +-448)): x widened to fp32, a correctly rounded fp32 division, the clamp in fp32 BEFORE the
+ * conversion (0x7F / 0xFF are never written), -0 stays 0x80.  d 64 / 128, 16-bit new_kv / q / out, 16-byte aligned buffers. */
+/* new_kv [seq, hkv, d] (bf16 / f16: dt) -> rows pos .. pos + seq - 1 of `cache` with the per-head `scales`; pos = pos_buf[0]
+ * (device int32; rows outside the cache are not stored) when pos_buf is non-NULL, else h_pos.  seq = 1 and a prompt are one kernel. */
+pgk_status pgk_kv_cache_write_fp8(const void* new_kv, void* cache, const float* scales, int seq, int hkv, int max_seq, int d, int h_pos,
+                                  const int32_t* pos_buf, pgk_dtype dt, pgk_stream s);
+/* scales[h] = max |x[:, h, :]| / 224 of x [seq, hkv, d] (half of the e4m3 range stays as headroom for later tokens); 1 for an
+ * all-zero head. */
+pgk_status pgk_kv_fp8_absmax_scales(const void* x, float* scales, int seq, int hkv, int d, pgk_dtype dt, pgk_stream s);
+/* One query row Q [hq, 1, d]: softmax(scale * q . K^T) . V over rows 0 .. ctx - 1 of the dequantised caches; ctx = ctx_buf[0] when
+ * ctx_buf is non-NULL, else h_context_len, clamped to max_seq as pgk_sdpa_fixed_cache clamps it.  Rows at and beyond ctx are
+ * never read: they may hold any bytes, the NaN codes included.  workspace: pgk_sdpa_decode_workspace_bytes(hq, d, max_seq).
+ * There is no other path: what pgk_sdpa_kv_fp8_plan rejects is PGK_ERR_INVALID here. */
+pgk_status pgk_sdpa_fixed_cache_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out,
+                                    int hq, int hkv, int max_seq, int d, float scale, int h_context_len, const int32_t* ctx_buf, void* workspace,
+                                    pgk_dtype dt, pgk_stream s);
+/* Host-only: "kv_fp8_split" and through *nsplit (may be NULL) the chunks per kv head; NULL (and pgk_last_error) for what
+ * pgk_sdpa_fixed_cache_fp8 rejects: hq % hkv, d outside {64, 128}, max_seq < 1, dt outside {bf16, f16}, unaligned buffers. */
+const char* pgk_sdpa_kv_fp8_plan(int hq, int hkv, int d, int max_seq, pgk_dtype dt, int aligned, int* nsplit);
+
 /* ---------------------------------------------------------------------- engine ------ */
 /* Native decode/prefill launcher: one C call (or one hipGraph launch) per token step instead of
  * ~21 Python-dispatched launches per layer.  Replaces the device-dispatch half

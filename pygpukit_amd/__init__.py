@@ -30,3 +30,5 @@ from pygpukit_amd.ops.nn.relpos import (relbias_plan, relpos_bias_table, relpos_
 from pygpukit_amd.ops.nn.window import (kv_cache_update_ring, kv_cache_update_ring_ptr, sdpa_sliding_window,  # noqa: F401,E402
                                         sdpa_sliding_window_fixed_cache, sdpa_sliding_window_fixed_cache_ptr, sdpa_sliding_window_strided,
                                         sdpa_window_plan)
+from pygpukit_amd.ops.nn.kvfp8 import (kv_cache_prefill_gqa_fp8, kv_cache_update_gqa_fp8, kv_cache_update_gqa_fp8_ptr, kv_fp8_scales, sdpa_causal_fixed_cache_fp8,  # noqa: F401,E402
+                                       sdpa_causal_fixed_cache_fp8_ptr, sdpa_kv_fp8_plan)

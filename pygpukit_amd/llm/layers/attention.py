@@ -25,6 +25,7 @@ from pygpukit_amd.core.factory import from_numpy, zeros
 from pygpukit_amd.ops.basic import (bias_add_inplace, concat_axis0, kv_cache_prefill_gqa, kv_cache_update_gqa, rmsnorm,
                                    rope_inplace, rope_inplace_f32table, sdpa_causal_fixed_cache, sdpa_causal_strided,
                                    split_qkv_batch)
+from pygpukit_amd.ops.nn.kvfp8 import kv_cache_prefill_gqa_fp8, kv_fp8_scales, sdpa_causal_fixed_cache_fp8
 from pygpukit_amd.ops.nn.window import kv_cache_update_ring, sdpa_sliding_window_fixed_cache, sdpa_sliding_window_strided
 
 from .linear import LinearBF16, LinearFP8
@@ -43,6 +44,10 @@ class Attention:
         # sliding-window layer: a row sees `window` keys, its own included (TransformerConfig.layer_window); None = full causal
         self.window = window
         self._rolling = False
+        self._kv_fp8 = False                # init_fixed_cache(kv_dtype="fp8"): uint8 caches and the two scale arrays below
+        self._k_scale: GPUArray | None = None
+        self._v_scale: GPUArray | None = None
+        self._scales_from_prompt = False    # kv_scales="prompt": write_prompt_kv sets the scales from the first prompt chunk
         self.head_dim = config.head_dim
         self.num_heads = config.num_heads
         self.num_kv_heads: int = config.num_kv_heads
@@ -86,9 +91,28 @@ class Attention:
         self._logical_pos = 0
 
     # ------------------------------------------------------------------ caches / rope tables
-    def init_fixed_cache(self, max_seq_len: int, dtype: str = "float16", rolling: bool = False) -> None:
+    def init_fixed_cache(self, max_seq_len: int, dtype: str = "float16", rolling: bool = False, kv_dtype: str | None = None,
+                         kv_scales="unit") -> None:
         """Fixed-length KV cache [num_kv_heads, max_seq_len, head_dim] (attention.py:128-146, un-expanded here).  rolling=True on a
-        windowed layer: min(max_seq_len, window) rows, position p in row p % rows (a full-attention layer keeps max_seq_len rows)."""
+        windowed layer: min(max_seq_len, window) rows, position p in row p % rows (a full-attention layer keeps max_seq_len rows).
+        kv_dtype="fp8": uint8 caches of OCP e4m3 codes with one float32 scale per KV head for K and for V (ops/nn/kvfp8.py).
+        kv_scales: "unit" (all 1.0), "prompt" (absmax / 224 of the first prompt chunk, set by write_prompt_kv) or a pair
+        (k_scale, v_scale) of float32 arrays [num_kv_heads]."""
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"init_fixed_cache: kv_dtype {kv_dtype!r} not in (None, 'fp8')")
+        self._kv_fp8 = kv_dtype == "fp8"
+        if self._kv_fp8:
+            if self.window is not None or rolling:
+                raise NotImplementedError("an fp8 KV cache has no sliding-window decode kernel: use kv_dtype=None on windowed layers")
+            if isinstance(kv_scales, str):
+                if kv_scales not in ("unit", "prompt"):
+                    raise ValueError(f"init_fixed_cache: kv_scales {kv_scales!r} not in ('unit', 'prompt', (k_scale, v_scale))")
+                self._k_scale, self._v_scale = (from_numpy(np.ones(self.num_kv_heads, np.float32)) for _ in range(2))
+            else:
+                self._k_scale, self._v_scale = (s if isinstance(s, GPUArray) else from_numpy(np.ascontiguousarray(s, np.float32))
+                                                for s in kv_scales)
+            self._scales_from_prompt = kv_scales == "prompt" if isinstance(kv_scales, str) else False
+            dtype = "uint8"
         self._rolling = bool(rolling) and self.window is not None
         rows = min(max_seq_len, self.window) if self._rolling else max_seq_len
         shape = (self.num_kv_heads, rows, self.head_dim)
@@ -191,6 +215,12 @@ class Attention:
     def write_prompt_kv(self, k: GPUArray, v: GPUArray) -> None:
         """K / V [S, Hkv, D] of a prompt that starts at position 0 -> the fixed caches; a rolling cache keeps the last `rows`."""
         S, rows = k.shape[0], self._k_cache.shape[1]
+        if self._kv_fp8:
+            for new, cache, scales in ((k, self._k_cache, self._k_scale), (v, self._v_cache, self._v_scale)):
+                if self._scales_from_prompt:
+                    kv_fp8_scales(new, self.num_kv_heads, out=scales)
+                kv_cache_prefill_gqa_fp8(new, cache, scales, 0)
+            return
         for new, cache in ((k, self._k_cache), (v, self._v_cache)):
             if not self._rolling:
                 kv_cache_prefill_gqa(new, cache, self.num_heads, 0)
@@ -213,7 +243,11 @@ class Attention:
             cos, sin = self._rope_rows(position, 1)
             self._apply_rope(q3, k3, cos, sin)
         attn_out = out if out is not None else GPUArray((Hq, 1, D), x.dtype)
-        if self.window is None:
+        if self._kv_fp8:
+            kv_cache_prefill_gqa_fp8(k3, self._k_cache, self._k_scale, position)
+            kv_cache_prefill_gqa_fp8(v3, self._v_cache, self._v_scale, position)
+            sdpa_causal_fixed_cache_fp8(q.view((Hq, 1, D)), self._k_cache, self._v_cache, self._k_scale, self._v_scale, attn_out, context_len)
+        elif self.window is None:
             kv_cache_update_gqa(k3, self._k_cache, Hq, position)
             kv_cache_update_gqa(v3, self._v_cache, Hq, position)
             sdpa_causal_fixed_cache(q.view((Hq, 1, D)), self._k_cache, self._v_cache, attn_out, context_len)
@@ -232,6 +266,9 @@ class Attention:
         if S == 1:
             return self.forward_fixed_cache(x, start_position, context_len)
         Hq, Hkv, D = self.num_heads, self.num_kv_heads, self.head_dim
+        if self._kv_fp8:
+            raise NotImplementedError("an fp8 KV cache takes one prompt chunk from position 0 (prefill_fixed_cache), then single tokens: "
+                                      "no kernel reads it with a query of several rows")
         if self._rolling and start_position != 0:
             raise NotImplementedError("a rolling cache takes one prompt chunk from position 0, then single tokens: rows that a later chunk "
                                       "needs have been overwritten")

@@ -92,10 +92,21 @@ class CausalTransformerModel:
 
     def generate(self, input_ids: list[int], max_new_tokens: int = 20, temperature: float = 1.0, top_k: int = 50,
                  top_p: float = 0.9, eos_token_id: int | None = None, use_cache: bool = True,
-                 gpu_sampling: bool = False) -> list[int]:
-        """causal.py:179-255: prefill, sample from the last row, then one-token steps with past_key_values."""
+                 gpu_sampling: bool = False, kv_dtype: str | None = None, kv_scales="unit") -> list[int]:
+        """causal.py:179-255: prefill, sample from the last row, then one-token steps with past_key_values.  kv_dtype="fp8" (with
+        use_cache): the steps run against fixed fp8 caches of len(input_ids) + max_new_tokens rows instead (init_fixed_cache)."""
         tokens = list(input_ids)
-        if use_cache:
+        if kv_dtype is not None:
+            if not use_cache:
+                raise ValueError("generate: kv_dtype needs use_cache=True")
+            self.init_fixed_cache(len(tokens) + max_new_tokens, kv_dtype=kv_dtype, kv_scales=kv_scales)
+            logits = self.prefill_fixed_cache(tokens)
+            for _ in range(max_new_tokens):
+                tokens.append(self._sample(logits, temperature, top_k, top_p, gpu_sampling))
+                if (eos_token_id is not None and tokens[-1] == eos_token_id) or len(tokens) == len(input_ids) + max_new_tokens:
+                    break
+                logits = self.get_logits(self._decode_step_fixed_cache(tokens[-1], len(tokens) - 1, len(tokens)))
+        elif use_cache:
             hidden, past = self(tokens, use_cache=True)
             nxt = self._sample(self.get_logits(hidden), temperature, top_k, top_p, gpu_sampling)
             tokens.append(nxt)
@@ -132,11 +143,14 @@ class CausalTransformerModel:
                 return
 
     # ------------------------------------------------------------------ fixed-cache decode (eager ops path)
-    def init_fixed_cache(self, max_seq_len: int, dtype: str | None = None, rolling: bool = False) -> None:
-        """rolling=True: the windowed layers keep min(max_seq_len, window) rows as a ring (Attention.init_fixed_cache)."""
+    def init_fixed_cache(self, max_seq_len: int, dtype: str | None = None, rolling: bool = False, kv_dtype: str | None = None,
+                         kv_scales="unit") -> None:
+        """rolling=True: the windowed layers keep min(max_seq_len, window) rows as a ring (Attention.init_fixed_cache).
+        kv_dtype="fp8": every layer keeps an OCP e4m3 cache; kv_scales "unit", "prompt" or one (k_scale, v_scale) pair per layer."""
         dt = dtype or str(self.embed_tokens.dtype)
-        for block in self.blocks:
-            block.attn.init_fixed_cache(max_seq_len, dt, rolling=rolling)
+        for i, block in enumerate(self.blocks):
+            block.attn.init_fixed_cache(max_seq_len, dt, rolling=rolling, kv_dtype=kv_dtype,
+                                        kv_scales=kv_scales if isinstance(kv_scales, str) else kv_scales[i])
 
     def _mlp_forward_zero_alloc(self, mlp: MLP, x: GPUArray, buffers: DecodeBuffers) -> None:
         """MLP of one token into buffers.hidden using the pre-allocated buffers (causal.py:489-514)."""
