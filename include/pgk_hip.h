@@ -405,6 +405,48 @@ pgk_status pgk_gemm_fp4_nt(const uint8_t* a_packed, const uint8_t* b_packed, voi
 /* Bytes of the packed A and B of one gemm_nvf4_bf16_sm120 call: (m + n) * Kp/2 (A first, B at m * Kp/2). */
 size_t pgk_gemm_nvf4_workspace_bytes(int m, int n, int k);
 
+/* ------------------------------------------------------------------ int8 / int4 ------ */
+/* gemm_int8_int32_sm120 (native/bindings/gemm/int.cpp:43-74): D[M,N] int32 = A[M,K] int8 . B[N,K]^T int8 on
+ * v_mfma_i32_16x16x64_i8.  Exact: the true sum wherever it fits int32, its two's-complement wrap (the sum mod 2^32) where
+ * it does not.  K % 16 == 0 with 16-byte aligned operands runs the tile kernel (tails in M, N and K are zero-filled in LDS);
+ * any other K or alignment runs a one-output-per-thread kernel with the same result. */
+pgk_status pgk_gemm_int8_nt(const int8_t* a, const int8_t* b, int32_t* d, int m, int n, int k, pgk_stream s);
+/* [build-defined] The same accumulator behind the W8A8 store out[m][n] = (float)acc * a_scale[m] * w_scale[n] (+ bias[n]):
+ * fp32 products evaluated left to right, the bias added last (never fused into a multiply), one rounding to out_dt
+ * (PGK_F32 / PGK_F16 / PGK_BF16).  a_scale fp32 [M], w_scale fp32 [N], bias [N] in out_dt or NULL. */
+pgk_status pgk_gemm_int8_dequant_nt(const int8_t* a, const float* a_scale, const int8_t* w, const float* w_scale, const void* bias,
+                                    void* out, int m, int n, int k, pgk_dtype out_dt, pgk_stream s);
+/* gemm_int4_int32_sm120 / gemm_int4_int8_sm120 (int.cpp:121-234): a [M,K/2], b [N,K/2] packed signed nibbles (-8..7; k even in
+ * the low nibble, k + 1 in the high one).  The accumulator is the exact int32 sum; D = saturate(roundf((float)acc * scale_a *
+ * scale_b * descale_d)) (fp32, left to right, ties away from zero) as int32 (out_int8 = 0) or int8 (out_int8 = 1).  With all
+ * three factors 1.0f the int32 output is the accumulator itself.  Stricter than the reference, whose path rounds through
+ * e4m3 and bf16.  k even; k % 32 == 0 with aligned operands runs the tile kernel. */
+pgk_status pgk_gemm_int4_nt(const uint8_t* a, const uint8_t* b, void* d, int m, int n, int k, float scale_a, float scale_b,
+                            float descale_d, int out_int8, pgk_stream s);
+/* int4_gemv_int32_sm120 (native/ops/matmul/gemv/int4_int4/sm120/int4_gemv.cu:69-82): C[n] int32 = saturate(roundf((float)(sum_k
+ * a[k] * b_nk[n][k]) * scale_a * scale_b)), a [K/2] and b_nk [N,K/2] packed as above, exact int32 sum, no atomics.  k even;
+ * k % 32 == 0 with aligned operands streams the weights with 16-byte loads onto v_dot8_i32_i4. */
+pgk_status pgk_gemv_int4(const uint8_t* a, const uint8_t* b_nk, int32_t* c, int k, int n, float scale_a, float scale_b, pgk_stream s);
+/* quantize_to_int8 (native/ops/quantize/quantize_kernels.cuh:212-310): per ROW s = max|x| / 127 in fp32, floored at 1e-10f;
+ * q = clamp(rint(x / s), -128, 127) with IEEE division of the unrounded fp32 s and ties to even (NaN -> 0); scale[row] = s
+ * rounded to dt.  x [rows, cols] and scale [rows] in dt (PGK_F32 / PGK_F16, and PGK_BF16 as this project's extension). */
+pgk_status pgk_quantize_int8_rows(const void* x, int8_t* q, void* scale, int rows, int cols, pgk_dtype dt, pgk_stream s);
+/* dequantize_int8 (quantize_kernels.cuh:30-65): out[r][c] = (float)q[r][c] * (float)scale[r], one rounding to dt (scale in dt). */
+pgk_status pgk_dequantize_int8_rows(const int8_t* q, const void* scale, void* out, int rows, int cols, pgk_dtype dt, pgk_stream s);
+/* linear_int8 (quantize_kernels.cuh:84-198): out[M,N] = act[M,K] . (w[N,K] int8 * scale[N])^T (+ bias[N]), fp32 accumulate; act,
+ * scale, bias and out in dt (PGK_F16 as the reference, PGK_BF16).  The int8 weights enter the products unscaled (exact) and
+ * scale[n], bias[n] are applied once per output.  m <= 8: a weight-streaming kernel; more rows: the 16-bit MFMA tile loop
+ * with the weights converted on their way into LDS (both need k % 16 == 0 and aligned act / w; anything else runs a simple
+ * kernel). */
+pgk_status pgk_linear_int8(const void* act, const int8_t* w, const void* scale, const void* bias, void* out, int m, int n, int k,
+                           pgk_dtype dt, pgk_stream s);
+/* Host-only: the kernel a call of this family takes, from the functions the launchers switch on (csrc/int8_plan.h).  op =
+ * "gemm_int8" / "gemm_int8_dequant" -> int8_tile128 | int8_tile64 | int8_simple; "gemm_int4" -> int4_tile{128,64}_{planes,ext} |
+ * int4_simple; "gemv_int4" (m ignored) -> gemv_int4_stream_r{1,2,4} | gemv_int4_simple; "linear_int8" ->
+ * linear_int8_stream_m{1,2,4,8} | linear_int8_mfma_{64,128} | linear_int8_simple.  aligned: every operand on a 16-byte boundary.
+ * NULL and pgk_last_error for an unknown op, a bad shape or an odd int4 K.  The buffer is thread-local. */
+const char* pgk_int_gemm_plan(const char* op, int m, int n, int k, int aligned);
+
 /* ------------------------------------------------------------------- attention ------ */
 /* ops.cuh:287-290 sdpa_causal(Q[Hq,q,D], K[Hkv,kv,D], V, scale<=0 -> 1/sqrt(D)), mask
  * kv_pos < (kv_len - q_len) + q_pos + 1.  Strides are in elements so both the reference's

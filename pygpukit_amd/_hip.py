@@ -90,6 +90,10 @@ _PROTOS = {
     "pgk_quantize_fp8_blocks": [_V, _V, _V, _I, _I, _V],
     "pgk_quantize_nvf4": [_V, _V, _V, _I, _I, _V], "pgk_quantize_nvf4_nk": [_V, _V, _V, _I, _I, _V], "pgk_gemv_nvf4_bf16": [_V, _V, _V, _V, _V, _I, _I, _F, _V],
     "pgk_quantize_e2m1_unit": [_V, _V, _I, _I, _I, _V], "pgk_gemm_fp4_nt": [_V, _V, _V, _I, _I, _I, _V],
+    "pgk_gemm_int8_nt": [_V, _V, _V, _I, _I, _I, _V], "pgk_gemm_int8_dequant_nt": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _V],
+    "pgk_gemm_int4_nt": [_V, _V, _V, _I, _I, _I, _F, _F, _F, _I, _V], "pgk_gemv_int4": [_V, _V, _V, _I, _I, _F, _F, _V],
+    "pgk_quantize_int8_rows": [_V, _V, _V, _I, _I, _I, _V], "pgk_dequantize_int8_rows": [_V, _V, _V, _I, _I, _I, _V],
+    "pgk_linear_int8": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _V],
     "pgk_paged_attention_v1": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
     "pgk_paged_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
     "pgk_scatter_last_token_logits": [_V, _V, _V, _V, _I, _I, _I, _V], "pgk_prepare_position_ids": [_V, _V, _V, _V, _V, _I, _V],
@@ -181,6 +185,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_group_norm_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
                "pgk_ln_linear_plan": ([_I, _I, _I, _I, _I, _I], C.c_int),
                "pgk_gemm_plan": ([C.c_char_p, _I, _I, _I, _I, _I], C.c_char_p),
+               "pgk_int_gemm_plan": ([C.c_char_p, _I, _I, _I, _I], C.c_char_p),
                "pgk_base_op_plan": ([C.c_char_p, _Z, _I, _I, _I], C.c_char_p), "pgk_base_op_grid": ([C.c_char_p, _Z, _I, _I, _I], C.c_int),
                "pgk_tensor_op_plan": ([C.c_char_p, _Z, _Z, _Z, _I, C.c_uint], C.c_char_p),
                "pgk_tensor_op_grid": ([C.c_char_p, _Z, _Z, _Z, _I, C.c_uint], C.c_int),

@@ -16,6 +16,11 @@ from pygpukit_amd.ops.matmul import (batched_matmul, gemm_w8a16_init_lut, gemv_b
                                     gemv_nvf4_bf16_sm120, nvf4_bf16_sm120_available, gemm_nvf4_bf16_sm120_available,
                                     gemv_nvf4_available, gemv_nvf4_bf16_sm120_available, nvf4_nk_get_sizes,
                                     quantize_bf16_to_nvf4_nk, quantize_nvf4_nk)
+from pygpukit_amd.ops.matmul import (gemm_int4_int8_sm120, gemm_int4_int32_available, gemm_int4_int32_sm120, gemm_int8_int32_available,
+                                    gemm_int8_int32_sm120, int4_gemm_available, int4_gemm_int8_sm120, int4_gemm_int32_sm120,
+                                    int4_gemv_available, int4_gemv_int32_sm120, int8_native_gemm_available, int8_native_gemm_sm120,
+                                    int_gemm_plan, matmul_int8_dequant)
+from pygpukit_amd.ops.quantize import dequantize_int8, linear_int8, quantize_to_int8
 from pygpukit_amd.ops.moe import (moe_compute_permutation, moe_expand_expert_offsets, moe_gather, moe_scatter, moe_softmax_topk,
                                   moe_topk_softmax, moe_topk_with_indices)
 from pygpukit_amd.ops.nn import (fa3_fp8_available, get_sm_version, quantize_fp8_per_head, sdpa_causal_fp8, sdpa_causal_fp8_strided,

@@ -10,6 +10,10 @@ from pygpukit_amd.ops.matmul.nvf4 import (gemm_nvf4_bf16_sm120, gemm_nvf4_bf16_s
                                           gemv_nvf4_bf16, gemv_nvf4_bf16_sm120, gemv_nvf4_bf16_sm120_available, gemv_nvf4_get_sizes,
                                           matmul_nvf4_bf16_sm120, nvf4_bf16_sm120_available, nvf4_get_sizes, nvf4_nk_get_sizes,
                                           quantize_bf16_to_nvf4, quantize_bf16_to_nvf4_nk, quantize_nvf4_nk)
+from pygpukit_amd.ops.matmul.int8 import (INT_GEMM_PLAN_OPS, gemm_int4_int8_sm120, gemm_int4_int32_available, gemm_int4_int32_sm120,
+                                          gemm_int8_int32_available, gemm_int8_int32_sm120, int4_gemm_available, int4_gemm_int8_sm120,
+                                          int4_gemm_int32_sm120, int4_gemv_available, int4_gemv_int32_sm120, int8_native_gemm_available,
+                                          int8_native_gemm_sm120, int_gemm_plan, matmul_int8_dequant)
 from pygpukit_amd.ops.matmul.generic import GEMM_PLAN_OPS, batched_matmul, gemm_plan, linear_bias_gelu, matmul, matmul_nt, transpose
 from pygpukit_amd.ops.matmul.w8a16 import gemm_w8a16_init_lut, w8a16_gemm, w8a16_gemm_nk, w8a16_gemm_sm120
 
@@ -22,4 +26,7 @@ __all__ = ["matmul", "matmul_nt", "gemm_plan", "GEMM_PLAN_OPS", "transpose", "ba
            "grouped_gemm_init_lut", "grouped_gemm_fp8_bf16", "grouped_gemm_fp8_bf16_sm120", "grouped_gemm_bf16",
            "grouped_gemm_sorted_splits", "nvf4_get_sizes", "nvf4_nk_get_sizes", "quantize_bf16_to_nvf4_nk", "quantize_nvf4_nk", "gemv_nvf4_get_sizes", "quantize_bf16_to_nvf4",
            "matmul_nvf4_bf16_sm120", "gemm_nvf4_bf16_sm120", "gemv_nvf4_bf16", "gemv_nvf4_bf16_sm120", "nvf4_bf16_sm120_available",
-           "gemm_nvf4_bf16_sm120_available", "gemv_nvf4_available", "gemv_nvf4_bf16_sm120_available"]
+           "gemm_nvf4_bf16_sm120_available", "gemv_nvf4_available", "gemv_nvf4_bf16_sm120_available",
+           "INT_GEMM_PLAN_OPS", "int_gemm_plan", "gemm_int8_int32_available", "int8_native_gemm_available", "gemm_int4_int32_available",
+           "int4_gemm_available", "int4_gemv_available", "gemm_int8_int32_sm120", "int8_native_gemm_sm120", "matmul_int8_dequant",
+           "gemm_int4_int32_sm120", "int4_gemm_int32_sm120", "gemm_int4_int8_sm120", "int4_gemm_int8_sm120", "int4_gemv_int32_sm120"]
