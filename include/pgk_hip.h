@@ -298,6 +298,22 @@ pgk_status pgk_paged_attention_v1(const void* q, const void* k_cache, const void
                                   const int32_t* context_lens, void* out, int num_seqs, int num_heads, int num_kv_heads,
                                   int head_dim, int block_size, int max_blocks_per_seq, int max_context, float scale,
                                   void* workspace, pgk_dtype dt, pgk_stream s);
+/* Packed variable-length prefill attention over the paged cache (ops_paged_prefill.hip; no reference counterpart).
+ * q / out [total_tokens, Hq, D]: the rows of sequence b are cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (int32 [num_seqs + 1],
+ * device); caches, block_tables and context_lens as above, context_lens[b] INCLUDING this step's tokens, which the caller has
+ * already written with pgk_paged_cache_write.  Local row i of sequence b sees logical key j iff
+ * j <= context_lens[b] - q_len_b + i; a row that sees no key is zeros; rows of out no sequence owns are not written.
+ * max_query_len (host) bounds every q_len_b and sizes the grid; 0 launches nothing.  dt = PGK_BF16 / PGK_F16, D in {64, 128},
+ * Hq / Hkv in {1, 2, 4, 8}, any block_size >= 1; anything else is PGK_ERR_INVALID (there is no fallback kernel).
+ * scale <= 0 -> 1/sqrt(D).  One launch, no workspace, no KV split: pgk_paged_attention_v1 stays the tool for pure-decode batches.
+ * pgk_paged_prefill_plan: the kernel's name and its grid (x = column tiles, y = kv heads, z = sequences) in grid3, or NULL
+ * with the reason in pgk_last_error(); touches no device. */
+const char* pgk_paged_prefill_plan(int num_seqs, int max_query_len, int num_heads, int num_kv_heads, int head_dim, pgk_dtype dt,
+                                   int* grid3);
+pgk_status pgk_paged_attention_prefill(const void* q, const void* k_cache, const void* v_cache, const int32_t* block_tables,
+                                       const int32_t* context_lens, const int32_t* cu_seqlens_q, void* out, int num_seqs,
+                                       int total_tokens, int max_query_len, int num_heads, int num_kv_heads, int head_dim,
+                                       int block_size, int max_blocks_per_seq, float scale, pgk_dtype dt, pgk_stream s);
 /* ops.cuh:480-502 copy_to_paged_cache / reshape_and_cache (paged_attention.cuh:206-283): K_new/V_new
  * [n_tokens, Hkv, D] rows scattered to slot_mapping[token] = physical_block * block_size + offset (negative: skip). */
 pgk_status pgk_paged_cache_write(const void* k_new, const void* v_new, void* k_cache, void* v_cache,

@@ -95,6 +95,7 @@ _PROTOS = {
     "pgk_quantize_int8_rows": [_V, _V, _V, _I, _I, _I, _V], "pgk_dequantize_int8_rows": [_V, _V, _V, _I, _I, _I, _V],
     "pgk_linear_int8": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _V],
     "pgk_paged_attention_v1": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
+    "pgk_paged_attention_prefill": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _V],
     "pgk_paged_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
     "pgk_scatter_last_token_logits": [_V, _V, _V, _V, _I, _I, _I, _V], "pgk_prepare_position_ids": [_V, _V, _V, _V, _V, _I, _V],
     "pgk_check_eos": [_V, _V, _I, _I, _V], "pgk_exclusive_cumsum_i32": [_V, _V, _I, _V],
@@ -194,6 +195,7 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_flux_qk_norm_rope_plan": ([_I, _I, _I], C.c_char_p),
                "pgk_relbias_plan": ([_I, _I, _I, _I], C.c_char_p),
                "pgk_sdpa_window_plan": ([_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
+               "pgk_paged_prefill_plan": ([_I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
                "pgk_sdpa_kv_fp8_plan": ([_I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),

@@ -46,6 +46,26 @@ inline int paged_nsplit(int max_context) {
     return n < 1 ? 1 : (n > 32 ? 32 : n);
 }
 
+// ---- pgk_paged_attention_prefill (ops_paged_prefill.hip): packed variable-length prefill over the paged cache -------------------
+// A column of the score tile is a (query position, query head of the kv head's group of G) pair - column c is position c / G,
+// head c % G - and a workgroup owns PP_COLS consecutive columns of one (sequence, kv head).  The grid is sized by the host's bound
+// on the longest query run; a workgroup past its own sequence's last column returns at once.  One kernel, no fallback: what it
+// does not serve is refused with the reason below.
+constexpr int PP_COLS = 128, PP_MAX_SEQS = 65535;
+inline const char* paged_prefill_refusal(int hq, int hkv, int d, bool is_16bit) {
+    if (hq < 1 || hkv < 1 || hq % hkv) return "num_heads must be a positive multiple of num_kv_heads";
+    if (!is_16bit) return "bfloat16 / float16 only";
+    if (d != 64 && d != 128) return "head_dim not in {64, 128}";
+    const int G = hq / hkv;
+    if (G != 1 && G != 2 && G != 4 && G != 8) return "query heads per kv head not in {1, 2, 4, 8}";
+    return nullptr;
+}
+inline int paged_prefill_tiles(int max_query_len, int G) { return ceil_div((long long)max_query_len * G, PP_COLS); }
+struct PagedPrefillGrid { int x, y, z; };     // column tiles, kv heads, sequences
+inline PagedPrefillGrid paged_prefill_grid(int max_query_len, int hq, int hkv, int num_seqs) {
+    return PagedPrefillGrid{paged_prefill_tiles(max_query_len, hq / hkv), hkv, num_seqs};
+}
+
 // ---- prefill: which kernel takes an sdpa call ---------------------------------------------------------------------------------
 // first-generation MFMA kernel (flash_prefill_kernel): 16-byte loads of Q, K and V rows.  in_aligned: q, k and v are 16-byte aligned
 inline bool flash1_ok(int d, bool in_aligned, const FlashStrides& sd) {

@@ -37,8 +37,8 @@ from pygpukit_amd.ops.plan import BASE_PLAN_OPS, TENSOR_PLAN_OPS, base_op_grid, 
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis
 from pygpukit_amd.ops.unary import abs, cos, exp, log, neg, relu, rsqrt, sin, sqrt
 from pygpukit_amd.ops.paged import (allocate_kv_cache, argmax_sample, check_eos, compute_cumsum, copy_to_paged_cache, gather_embeddings,
-                                    paged_attention_v1, prepare_batch_inputs, prepare_position_ids, reshape_and_cache,
-                                    scatter_last_token_logits)
+                                    paged_attention_prefill, paged_attention_v1, paged_prefill_plan, prepare_batch_inputs,
+                                    prepare_position_ids, reshape_and_cache, scatter_last_token_logits)
 from pygpukit_amd.ops.sampling import (sample_greedy, sample_multinomial, sample_token_gpu, sample_topk, sample_topk_to_buf_ptr,
                                        sample_topp, set_sampling_seed)
 from pygpukit_amd.ops.tensor import (cast_bf16_to_f32, cast_f16_to_f32, cast_f32_to_bf16, cast_f32_to_f16, concat_axis0,

@@ -9,7 +9,7 @@ import numpy as np
 
 from pygpukit_amd import _hip
 from pygpukit_amd.core.array import GPUArray
-from pygpukit_amd.core.dtypes import bfloat16, float16, int32
+from pygpukit_amd.core.dtypes import as_dtype, bfloat16, float16, int32
 from pygpukit_amd.core.factory import from_numpy, zeros
 from pygpukit_amd.ops._common import call, check_out
 
@@ -49,6 +49,56 @@ def paged_attention_v1(q: GPUArray, k_cache: GPUArray, v_cache: GPUArray, block_
     call("pgk_paged_attention_v1", q._p, k_cache._p, v_cache._p, block_tables._p, context_lens._p, o._p, num_seqs, num_heads,
          num_kv_heads, head_dim, block_size, max_blocks, max_context, C.c_float(scale), ws._p if ws is not None else None,
          q.dtype.code, None)
+    return o
+
+
+def paged_prefill_plan(num_seqs: int, max_query_len: int, num_heads: int, num_kv_heads: int, head_dim: int,
+                       dtype) -> tuple[str, tuple[int, int, int] | None]:
+    """What paged_attention_prefill launches for this batch: ("paged_prefill_mfma", (column tiles, kv heads, sequences)), a
+    column tile being 128 (query position, query head of one kv head) pairs, or (the reason the call is refused, None).  There
+    is no fallback kernel.  Needs no GPU work."""
+    lib = _hip.load()
+    grid = (C.c_int * 3)()
+    name = lib.pgk_paged_prefill_plan(int(num_seqs), int(max_query_len), int(num_heads), int(num_kv_heads), int(head_dim),
+                                      as_dtype(dtype).code, grid)
+    if name is None:
+        msg = lib.pgk_last_error()
+        return (msg.decode(errors="replace") if msg else "pgk_paged_attention_prefill: refused"), None
+    return name.decode(), (grid[0], grid[1], grid[2])
+
+
+def paged_attention_prefill(q: GPUArray, k_cache: GPUArray, v_cache: GPUArray, block_tables: GPUArray, context_lens: GPUArray,
+                            cu_seqlens_q: GPUArray, scale: float = 0.0, *, out: GPUArray | None = None,
+                            max_query_len: int | None = None) -> GPUArray:
+    """Causal attention of a packed batch over a paged cache.  q [total_tokens, num_heads, head_dim] -> same shape; the rows of
+    sequence b are cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (int32 [num_seqs + 1]).  context_lens[b] counts this step's tokens
+    too: write them with reshape_and_cache first.  Local row i of sequence b sees key j iff j <= context_lens[b] - q_len_b + i,
+    so prompts, chunks behind a cached prefix, decode rows (q_len 1) and idle sequences (q_len 0) mix freely; a row that sees
+    no key is zeros and rows no sequence owns are left alone.  max_query_len bounds every q_len_b (default: total_tokens) and
+    only sizes the grid.  bfloat16 / float16, head_dim 64 / 128, num_heads / num_kv_heads in {1, 2, 4, 8}; nothing else has a
+    kernel.  No KV split: paged_attention_v1 stays the tool for pure-decode batches over long contexts."""
+    name = "paged_attention_prefill"
+    _check_cache(k_cache, v_cache, name)
+    if q.ndim != 3 or q.dtype != k_cache.dtype or q.shape[2] != k_cache.shape[3] or q.shape[0] < 1:
+        raise ValueError(f"{name}: q {q.shape} {q.dtype} does not match the cache {k_cache.shape} {k_cache.dtype}")
+    total_tokens, num_heads, head_dim = q.shape
+    _, num_kv_heads, block_size, _ = k_cache.shape
+    if block_tables.dtype != int32 or block_tables.ndim != 2:
+        raise ValueError(f"{name}: block_tables must be int32 [num_seqs, max_blocks_per_seq]")
+    num_seqs, max_blocks = block_tables.shape
+    if context_lens.dtype != int32 or context_lens.size != num_seqs:
+        raise ValueError(f"{name}: context_lens must be int32 [num_seqs]")
+    if cu_seqlens_q.dtype != int32 or cu_seqlens_q.size != num_seqs + 1:
+        raise ValueError(f"{name}: cu_seqlens_q must be int32 [num_seqs + 1]")
+    max_query_len = total_tokens if max_query_len is None else int(max_query_len)
+    if not 0 <= max_query_len <= total_tokens:
+        raise ValueError(f"{name}: max_query_len {max_query_len} outside [0, total_tokens = {total_tokens}]")
+    plan, _ = paged_prefill_plan(num_seqs, max_query_len, num_heads, num_kv_heads, head_dim, q.dtype)
+    if plan != "paged_prefill_mfma":
+        raise ValueError(plan)
+    o = check_out(out, q.shape, q.dtype, name)
+    call("pgk_paged_attention_prefill", q._p, k_cache._p, v_cache._p, block_tables._p, context_lens._p, cu_seqlens_q._p, o._p, num_seqs,
+         total_tokens, max_query_len, num_heads, num_kv_heads, head_dim, block_size, max_blocks, C.c_float(scale), q.dtype.code, None)
     return o
 
 
@@ -147,5 +197,5 @@ def prepare_batch_inputs(token_lists: list[list[int]]) -> tuple[GPUArray, int]:
     return from_numpy(flat), int(flat.size)
 
 
-__all__ = ["allocate_kv_cache", "paged_attention_v1", "copy_to_paged_cache", "reshape_and_cache", "gather_embeddings",
+__all__ = ["allocate_kv_cache", "paged_attention_v1", "paged_attention_prefill", "paged_prefill_plan", "copy_to_paged_cache", "reshape_and_cache", "gather_embeddings",
            "scatter_last_token_logits", "prepare_position_ids", "argmax_sample", "check_eos", "compute_cumsum", "prepare_batch_inputs"]
