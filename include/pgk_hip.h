@@ -314,6 +314,36 @@ pgk_status pgk_paged_attention_prefill(const void* q, const void* k_cache, const
                                        const int32_t* context_lens, const int32_t* cu_seqlens_q, void* out, int num_seqs,
                                        int total_tokens, int max_query_len, int num_heads, int num_kv_heads, int head_dim,
                                        int block_size, int max_blocks_per_seq, float scale, pgk_dtype dt, pgk_stream s);
+/* FP8 (OCP e4m3) paged KV cache (ops_paged_fp8.hip, ops_paged_prefill.hip; no reference counterpart).  K / V cache
+ * [num_blocks, Hkv, block_size, D] in uint8 with one fp32 scale per kv head for K and one for V (k_scale, v_scale [Hkv], device):
+ * value = e4m3(code) * scale, code = rne_e4m3(clamp(x / scale, +-448)) exactly as pgk_kv_cache_write_fp8 (0x7F / 0xFF are never
+ * written, -0 is 0x80).  block_tables, context_lens, cu_seqlens_q and slot_mapping as for the 16-bit pages; q / out and K_new /
+ * V_new are dt = PGK_BF16 / PGK_F16; D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}, any block_size >= 1; anything else is
+ * PGK_ERR_INVALID (there is no fallback).  Bytes at and past context_lens[b] are never read: they may hold the NaN codes.
+ * pgk_paged_cache_write_fp8: K_new / V_new [n_tokens, Hkv, D] quantised and scattered in one launch; a negative slot, or one
+ * past num_blocks * block_size, is skipped.
+ * pgk_paged_attention_v1_fp8: one query row per sequence, q / out [num_seqs, Hq, D]; split-KV over the live context in
+ * paged_nsplit(max_context) slices.  pgk_paged_attention_fp8_workspace_bytes: 0 for a single slice (max_context <= 512: merged
+ * inside the workgroup, workspace may be NULL), else one fp32 record [m, l, o[D]] per (sequence, query head, slice).
+ * pgk_paged_attention_prefill_fp8: pgk_paged_attention_prefill over 8-bit pages, same masks and the same grid.
+ * pgk_paged_kv_fp8_plan (host only): prefill = 0 -> "paged_kv_fp8_split", grid3 = (slices, groups of min(Hq / Hkv, 4) query heads,
+ * sequences), bound = max_context; prefill = 1 -> "paged_kv_fp8_prefill_mfma", grid3 = (column tiles, kv heads, sequences), bound
+ * = max_query_len; NULL with the reason in pgk_last_error() for what the two entries refuse. */
+const char* pgk_paged_kv_fp8_plan(int prefill, int num_seqs, int bound, int num_heads, int num_kv_heads, int head_dim, pgk_dtype dt,
+                                  int* grid3);
+size_t pgk_paged_attention_fp8_workspace_bytes(int num_seqs, int num_heads, int head_dim, int max_context);
+pgk_status pgk_paged_cache_write_fp8(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
+                                     const float* v_scale, const int32_t* slot_mapping, int n_tokens, int num_kv_heads, int num_blocks,
+                                     int block_size, int head_dim, pgk_dtype dt, pgk_stream s);
+pgk_status pgk_paged_attention_v1_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
+                                      const float* v_scale, const int32_t* block_tables, const int32_t* context_lens, void* out,
+                                      int num_seqs, int num_heads, int num_kv_heads, int head_dim, int block_size,
+                                      int max_blocks_per_seq, int max_context, float scale, void* workspace, pgk_dtype dt, pgk_stream s);
+pgk_status pgk_paged_attention_prefill_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale,
+                                           const float* v_scale, const int32_t* block_tables, const int32_t* context_lens,
+                                           const int32_t* cu_seqlens_q, void* out, int num_seqs, int total_tokens, int max_query_len,
+                                           int num_heads, int num_kv_heads, int head_dim, int block_size, int max_blocks_per_seq,
+                                           float scale, pgk_dtype dt, pgk_stream s);
 /* ops.cuh:480-502 copy_to_paged_cache / reshape_and_cache (paged_attention.cuh:206-283): K_new/V_new
  * [n_tokens, Hkv, D] rows scattered to slot_mapping[token] = physical_block * block_size + offset (negative: skip). */
 pgk_status pgk_paged_cache_write(const void* k_new, const void* v_new, void* k_cache, void* v_cache,

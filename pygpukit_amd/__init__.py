@@ -35,6 +35,8 @@ from pygpukit_amd.ops.matmul.int8 import (gemm_int4_int8_sm120, gemm_int4_int32_
                                           int4_gemm_int32_sm120, int4_gemv_available, int4_gemv_int32_sm120, int8_native_gemm_available,
                                           int8_native_gemm_sm120, int_gemm_plan, matmul_int8_dequant)
 from pygpukit_amd.ops.paged import paged_attention_prefill, paged_prefill_plan  # noqa: F401,E402
+from pygpukit_amd.ops.paged import (copy_to_paged_cache_fp8, paged_attention_prefill_fp8, paged_attention_v1_fp8, paged_kv_fp8_plan,  # noqa: F401,E402
+                                    reshape_and_cache_fp8)
 from pygpukit_amd.ops.quantize import dequantize_int8, linear_int8, quantize_to_int8  # noqa: F401,E402
 from pygpukit_amd.ops.nn.kvfp8 import (kv_cache_prefill_gqa_fp8, kv_cache_update_gqa_fp8, kv_cache_update_gqa_fp8_ptr, kv_fp8_scales, sdpa_causal_fixed_cache_fp8,  # noqa: F401,E402
                                        sdpa_causal_fixed_cache_fp8_ptr, sdpa_kv_fp8_plan)

@@ -97,6 +97,9 @@ _PROTOS = {
     "pgk_paged_attention_v1": [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
     "pgk_paged_attention_prefill": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _V],
     "pgk_paged_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
+    "pgk_paged_cache_write_fp8": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _V],
+    "pgk_paged_attention_v1_fp8": [_V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
+    "pgk_paged_attention_prefill_fp8": [_V, _V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _V],
     "pgk_scatter_last_token_logits": [_V, _V, _V, _V, _I, _I, _I, _V], "pgk_prepare_position_ids": [_V, _V, _V, _V, _V, _I, _V],
     "pgk_check_eos": [_V, _V, _I, _I, _V], "pgk_exclusive_cumsum_i32": [_V, _V, _I, _V],
     "pgk_st_open": [C.c_char_p, c_void_pp],
@@ -197,6 +200,8 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_sdpa_window_plan": ([_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
                "pgk_paged_prefill_plan": ([_I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
                "pgk_sdpa_kv_fp8_plan": ([_I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
+               "pgk_paged_kv_fp8_plan": ([_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
+               "pgk_paged_attention_fp8_workspace_bytes": ([_I, _I, _I, _I], C.c_size_t),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),
                "pgk_jit_program_log": ([_V], C.c_char_p), "pgk_jit_program_destroy": ([_V], None),
                "pgk_jit_kernel_destroy": ([_V], None)}

@@ -30,6 +30,26 @@ __device__ __forceinline__ uint32_t kv8_cvt(uint32_t w) {
     return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
 }
 
+// The cache writers' quantiser (kv8_write_kernel, paged_kv8_write_kernel): 16 elements at src -> 16 codes, rne_e4m3(clamp(x / sc,
+// +-448)) with x widened to fp32 and a correctly rounded division.  The clamp runs in fp32 BEFORE the conversion (fmaxf / fminf
+// also turn a NaN into a finite bound): 0x7F / 0xFF are never written; -0 stays -0 through both and converts to 0x80.
+template <class T>
+__device__ __forceinline__ uint4 kv8_quantise16(const T* src, float sc) {
+    constexpr float E4M3_MAX = 448.f;
+    float f[2][8];
+    KVLoad<T>::load8(src, f[0]);
+    KVLoad<T>::load8(src + 8, f[1]);
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float c[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = fminf(fmaxf(__fdiv_rn(f[i >> 1][(4 * i + j) & 7], sc), -E4M3_MAX), E4M3_MAX);
+        w[i] = pack_fp8x4(c[0], c[1], c[2], c[3]);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 constexpr int DPP_ROR4 = 0x124;   // rotate by 4 within each 16
 
 // all-reduce over the LPR = 8 / 4 lanes of a row

@@ -7,11 +7,8 @@
 
 namespace pgk {
 
-constexpr float E4M3_MAX = 448.f;
-
-// One lane = 16 elements of one row of new_kv [S][Hkv][D]: two 16-byte loads, one 16-byte store to cache row pos + s of head h.
-// The clamp runs in fp32 BEFORE the conversion (fmaxf / fminf also turn a NaN into a finite bound): 0x7F / 0xFF are never written;
-// -0 stays -0 through both and converts to 0x80.
+// One lane = 16 elements of one row of new_kv [S][Hkv][D]: two 16-byte loads, one 16-byte store to cache row pos + s of head h
+// (kv8_quantise16, attn_kv_fp8.hip.h).
 template <class T>
 __global__ __launch_bounds__(256) void kv8_write_kernel(const T* new_kv, uint8_t* cache, const float* scales, int seq, int hkv, int max_seq,
                                                         int d, int host_pos, const int32_t* pos_buf) {
@@ -22,19 +19,7 @@ __global__ __launch_bounds__(256) void kv8_write_kernel(const T* new_kv, uint8_t
     const long long row = (long long)(pos_buf ? pos_buf[0] : host_pos) + s;
     if (row < 0 || row >= max_seq) return;                      // a device position outside the cache: not stored (pgk_kv_cache_write's guard)
     const T* src = new_kv + ((size_t)s * hkv + h) * d + sub * 16;
-    float f[2][8];
-    KVLoad<T>::load8(src, f[0]);
-    KVLoad<T>::load8(src + 8, f[1]);
-    const float sc = scales[h];
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float c[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[j] = fminf(fmaxf(__fdiv_rn(f[i >> 1][(4 * i + j) & 7], sc), -E4M3_MAX), E4M3_MAX);
-        w[i] = pack_fp8x4(c[0], c[1], c[2], c[3]);
-    }
-    *reinterpret_cast<uint4*>(cache + ((size_t)h * max_seq + (size_t)row) * d + sub * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    *reinterpret_cast<uint4*>(cache + ((size_t)h * max_seq + (size_t)row) * d + sub * 16) = kv8_quantise16<T>(src, scales[h]);
 }
 
 // One workgroup per KV head: absmax of x[:, h, :] / 224 (half of the e4m3 range is headroom for later tokens), 1 for an all-zero head.

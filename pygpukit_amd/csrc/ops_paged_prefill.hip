@@ -1,4 +1,5 @@
-// Packed variable-length prefill attention over the paged KV cache (bf16 / f16, head_dim 64 or 128, Hq / Hkv in {1, 2, 4, 8}).
+// Packed variable-length prefill attention over the paged KV cache (bf16 / f16 queries over 16-bit or FP8 e4m3 pages, head_dim 64 or
+// 128, Hq / Hkv in {1, 2, 4, 8}).
 //
 // out[row] = softmax(scale . q[row] K^T + causal mask) V for a packed batch q [total_tokens, Hq, D]: the rows of sequence b are
 // cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1, its keys are the first context_lens[b] logical positions of its pages
@@ -21,6 +22,7 @@
 // ROW-MAJOR, [64][D] as well, and becomes the A operand V^T through gfx950's transposing LDS read (ds_read_b64_tr_b16): there is
 // no V^T workspace, no pre-pass and no allocation.  The page numbers of tile t + 2 and the K / V rows of tile t + 1 are in
 // flight (registers) under the MFMAs of tile t; both images are double buffered in LDS (64 KiB at D = 128, 32 KiB at D = 64).
+// The pages hold the kernel's 16-bit type or e4m3 codes (PagedKV16 / PagedKV8 below): one kernel, two stagings.
 // No KV split: a decode row over a very long context is one workgroup's walk (pgk_paged_attention_v1 is the pure-decode tool).
 
 #include "flash_common.hip.h"
@@ -41,15 +43,55 @@ template <int D> __device__ __forceinline__ int pp_v_off(int r, int c) { return 
 
 typedef short pp_v4s __attribute__((ext_vector_type(4)));
 
-template <class T, int D, int G>
-__global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const T* kc, const T* vc, const int32_t* block_tables,
+// What the pages hold: last template argument and last argument of paged_prefill_kernel, as FlashPlain / FlashIrope are
+// flash_fwd_kernel's.  PagedKV16: words of the kernel's own 16-bit type.  PagedKV8 (pgk_paged_attention_prefill_fp8): OCP e4m3
+// codes with one fp32 scale per kv head for K and one for V.  Only the staging differs.  A K / V row is D BYTES in global memory,
+// so a 16-byte load brings 16 codes and a tile needs half as many load instructions (and page lookups): a thread stages D / 64
+// rows per image and tile instead of D / 32, D / 16 threads to a row.  The codes wait in registers under the MFMAs of the tile
+// before (one uint4 per row, half of what the 16-bit words take) and are converted where they are stored: v_cvt_scalef32_pk_bf16_fp8
+// / _pk_f16_fp8 with scale 1 - exact, e4m3 is a subset of both types - give the two 16-byte chunks 2 sc, 2 sc + 1 of the SAME
+// swizzled K image and row-major V image, so the MFMA operand reads and ds_read_b64_tr_b16 do not know the difference.  k_scale
+// joins scale . log2(e) in the Q premultiply and v_scale the final 1 / l; the walk never sees either.
+// Which of its two chunks a thread stores first depends on its row (pp_first): the 16 lanes that share a pass of a 16-byte LDS
+// store then cover 256 different bytes modulo the 64 banks, as the 16-bit staging's 16 consecutive chunks do.  In the K image
+// at D = 128 the row's own XOR already does that (rows r, r + 1 flip the parity of chunk 2 sc); in the V image, whose swizzle moves
+// whole 64-byte segments, and in both images at D = 64, where rows r and r + 2 share a 128-byte half line, it is the row bit that
+// separates the two rows.
+struct PagedKV16 { static constexpr bool fp8 = false; };
+struct PagedKV8 { static constexpr bool fp8 = true; const float* k_scale; const float* v_scale; };
+
+template <class T> __device__ __forceinline__ uint32_t pp_cvt2(uint32_t w, bool hi);
+template <> __device__ __forceinline__ uint32_t pp_cvt2<bf16>(uint32_t w, bool hi) {
+    return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
+              : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+}
+template <> __device__ __forceinline__ uint32_t pp_cvt2<f16>(uint32_t w, bool hi) {
+    return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))
+              : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
+}
+// 8 codes (two dwords) -> one 16-byte chunk of T, element order kept
+template <class T> __device__ __forceinline__ uint4 pp_cvt8(uint32_t a, uint32_t b) {
+    return make_uint4(pp_cvt2<T>(a, false), pp_cvt2<T>(a, true), pp_cvt2<T>(b, false), pp_cvt2<T>(b, true));
+}
+__device__ __forceinline__ uint4 pp_pick(bool second, const uint4& a, const uint4& b) {
+    return make_uint4(second ? b.x : a.x, second ? b.y : a.y, second ? b.z : a.z, second ? b.w : a.w);
+}
+// which chunk of its pair (0: 2 sc, 1: 2 sc + 1) the thread staging row r stores first, K image / V image
+template <int D> __device__ __forceinline__ int pp_first_k(int r) { return D == 128 ? 0 : (r >> 1) & 1; }
+template <int D> __device__ __forceinline__ int pp_first_v(int r) { return D == 128 ? r & 1 : (r >> 1) & 1; }
+
+template <class T, int D, int G, class KV = PagedKV16>
+__global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const typename std::conditional<KV::fp8, uint8_t, T>::type* kc,
+                                                               const typename std::conditional<KV::fp8, uint8_t, T>::type* vc,
+                                                               const int32_t* block_tables,
                                                                const int32_t* context_lens, const int32_t* cu_seqlens_q, T* out,
                                                                int total_tokens, int num_heads, int num_kv_heads, int block_size,
-                                                               int bs_shift, int max_blocks, float scale_log2e) {
-    constexpr int NC = D / 8;            // 16-byte chunks per K / V row
+                                                               int bs_shift, int max_blocks, float scale_log2e, KV kv) {
+    constexpr int EPC = KV::fp8 ? 16 : 8; // cache elements per 16-byte chunk of global memory
+    constexpr int NC = D / EPC;          // 16-byte chunks per K / V row in global memory
     constexpr int KS = D / 16;           // k-steps of K . Q^T
     constexpr int DT = D / 32;           // 32-row tiles of O^T
-    constexpr int CH = DT;               // rows (one chunk of each) a thread stages per image and tile
+    constexpr int CH = NC / 4;           // rows (one chunk of each) a thread stages per image and tile
     constexpr int R_STEP = 256 / NC;     // row distance between a thread's chunks
     constexpr int IMG = 64 * D * 2;      // bytes of one K or V image
     static_assert(D == 64 || D == 128, "head_dim 64 / 128");
@@ -86,6 +128,8 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const
     // Q^T fragments (B operand): lane = column, k = d; premultiplied by scale * log2(e) (one more rounding to 16 bits, as the flash
     // kernel), so the scores leave the MFMA in the exp2 domain
     uint4 qf[KS];
+    float qmul = scale_log2e;
+    if constexpr (KV::fp8) qmul *= kv.k_scale[kvh];
     {
         const T* qrow = q + row_off + 8 * h;
 #pragma unroll
@@ -95,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const
             float f[8];
             v.to_float(f);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] *= scale_log2e;
+            for (int j = 0; j < 8; ++j) f[j] *= qmul;
             v.from_float(f);
             qf[ks] = v.raw;
         }
@@ -110,9 +154,9 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const
     // ---- staging: chunk sc of rows sr + R_STEP i of a tile; their page and row-in-page one tile ahead of their K / V loads --------
     const int sr = tid / NC, sc = tid % NC;
     const int32_t* table = block_tables + (size_t)seq * max_blocks;
-    const size_t page_elems = (size_t)num_kv_heads * block_size * D, head_off = (size_t)kvh * block_size * D + sc * 8;
+    const size_t page_elems = (size_t)num_kv_heads * block_size * D, head_off = (size_t)kvh * block_size * D + sc * EPC;
     // named registers, not arrays: at this register pressure hipcc leaves an array of staged chunks in scratch memory (FlashVStage)
-    static_assert(CH == 2 || CH == 4, "staging is written for D = 64 / 128");
+    static_assert(CH == 1 || CH == 2 || CH == 4, "staging is written for D = 64 / 128");
     int pg0 = 0, pg1 = 0, pg2 = 0, pg3 = 0, pin0 = 0, pin1 = 0, pin2 = 0, pin3 = 0;      // of the tile whose K / V loads are next
     uint4 rk0, rk1, rk2, rk3, rv0, rv1, rv2, rv3;
     auto page_of = [&](int t, int i, int& page, int& in_page) {
@@ -123,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const
     };
     auto load_pages = [&](int t) {
         page_of(t, 0, pg0, pin0);
-        page_of(t, 1, pg1, pin1);
+        if constexpr (CH >= 2) page_of(t, 1, pg1, pin1);
         if constexpr (CH == 4) { page_of(t, 2, pg2, pin2); page_of(t, 3, pg3, pin3); }
     };
     auto row_of = [&](int page, int in_page, uint4& k, uint4& v) {
@@ -133,18 +177,27 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const
     };
     auto load_kv = [&] {
         row_of(pg0, pin0, rk0, rv0);
-        row_of(pg1, pin1, rk1, rv1);
+        if constexpr (CH >= 2) row_of(pg1, pin1, rk1, rv1);
         if constexpr (CH == 4) { row_of(pg2, pin2, rk2, rv2); row_of(pg3, pin3, rk3, rv3); }
     };
     auto store_kv = [&](int buf) {
         char* kb = pp_smem + buf * IMG;
         char* vb = pp_smem + (2 + buf) * IMG;
         auto put = [&](int i, const uint4& k, const uint4& v) {
-            *reinterpret_cast<uint4*>(kb + pp_k_off<D>(sr + R_STEP * i, sc)) = k;
-            *reinterpret_cast<uint4*>(vb + pp_v_off<D>(sr + R_STEP * i, sc)) = v;
+            if constexpr (KV::fp8) {     // R_STEP is a multiple of 4: the row bits of pp_first are the thread's own
+                const int r = sr + R_STEP * i, fk = pp_first_k<D>(sr), fv = pp_first_v<D>(sr);
+                const uint4 k0 = pp_cvt8<T>(k.x, k.y), k1 = pp_cvt8<T>(k.z, k.w), v0 = pp_cvt8<T>(v.x, v.y), v1 = pp_cvt8<T>(v.z, v.w);
+                *reinterpret_cast<uint4*>(kb + pp_k_off<D>(r, 2 * sc + fk)) = pp_pick(fk, k0, k1);
+                *reinterpret_cast<uint4*>(kb + pp_k_off<D>(r, 2 * sc + 1 - fk)) = pp_pick(!fk, k0, k1);
+                *reinterpret_cast<uint4*>(vb + pp_v_off<D>(r, 2 * sc + fv)) = pp_pick(fv, v0, v1);
+                *reinterpret_cast<uint4*>(vb + pp_v_off<D>(r, 2 * sc + 1 - fv)) = pp_pick(!fv, v0, v1);
+            } else {
+                *reinterpret_cast<uint4*>(kb + pp_k_off<D>(sr + R_STEP * i, sc)) = k;
+                *reinterpret_cast<uint4*>(vb + pp_v_off<D>(sr + R_STEP * i, sc)) = v;
+            }
         };
         put(0, rk0, rv0);
-        put(1, rk1, rv1);
+        if constexpr (CH >= 2) put(1, rk1, rv1);
         if constexpr (CH == 4) { put(2, rk2, rv2); put(3, rk3, rv3); }
     };
     // V^T fragment of (k-step s, half u, dim tile i): the 16 lanes of a quarter-wave read the 4 x 16 block of rows
@@ -249,7 +302,8 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const
     // normalise and store: registers 4 g4 .. 4 g4 + 3 of tile i are dims 32 i + 8 g4 + 4 h .. + 3; a column that saw no key has
     // l = 0 and untouched accumulators and stores zeros
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+    float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+    if constexpr (KV::fp8) inv *= kv.v_scale[kvh];
     if (store_ok) {
         T* orow = out + row_off;
 #pragma unroll
@@ -264,17 +318,43 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_kernel(const T* q, const
     }
 }
 
-template <class T, int D, int G>
+template <class T, int D, int G, class KV>
 static pgk_status paged_prefill_launch(const void* q, const void* kc, const void* vc, const int32_t* block_tables, const int32_t* context_lens,
                                        const int32_t* cu_seqlens_q, void* out, const PagedPrefillGrid& g, int total_tokens, int num_heads,
-                                       int num_kv_heads, int block_size, int max_blocks, float scale, hipStream_t st) {
-    constexpr size_t LDS = 4 * (size_t)(64 * D * 2);
+                                       int num_kv_heads, int block_size, int max_blocks, float scale, const KV& kv, hipStream_t st) {
+    using CT = typename std::conditional<KV::fp8, uint8_t, T>::type;
+    constexpr size_t LDS = 4 * (size_t)(64 * D * 2);      // the images hold 16-bit words whatever the pages hold
     int bs_shift = -1;
     if ((block_size & (block_size - 1)) == 0)
         for (bs_shift = 0; (1 << bs_shift) < block_size; ++bs_shift) {}
-    return launch_dyn_lds<paged_prefill_kernel<T, D, G>>(dim3(g.x, g.y, g.z), 256, LDS, LDS > 48 * 1024, st, (const T*)q, (const T*)kc, (const T*)vc,
-                                                         block_tables, context_lens, cu_seqlens_q, (T*)out, total_tokens, num_heads, num_kv_heads,
-                                                         block_size, bs_shift, max_blocks, scale * 1.4426950408889634f);
+    return launch_dyn_lds<paged_prefill_kernel<T, D, G, KV>>(dim3(g.x, g.y, g.z), 256, LDS, LDS > 48 * 1024, st, (const T*)q, (const CT*)kc,
+                                                             (const CT*)vc, block_tables, context_lens, cu_seqlens_q, (T*)out, total_tokens,
+                                                             num_heads, num_kv_heads, block_size, bs_shift, max_blocks,
+                                                             scale * 1.4426950408889634f, kv);
+}
+
+// the two entry points below, after their argument checks; grid3 is what the entry's host-only plan function returned
+template <class KV>
+static pgk_status paged_prefill_dispatch(const char* name, const void* q, const void* k_cache, const void* v_cache, const int32_t* block_tables,
+                                         const int32_t* context_lens, const int32_t* cu_seqlens_q, void* out, const int* grid3, int total_tokens,
+                                         int max_query_len, int num_heads, int num_kv_heads, int head_dim, int block_size, int max_blocks_per_seq,
+                                         float scale, pgk_dtype dt, const KV& kv, pgk_stream s) {
+    if (!(aligned16(q) && aligned16(k_cache) && aligned16(v_cache) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0))
+        return set_error(PGK_ERR_INVALID, "%s: q and the caches must be 16-byte aligned, out 8-byte aligned", name);
+    if (max_query_len == 0) return PGK_OK;       // every sequence idle
+    if (scale <= 0.f) scale = 1.0f / sqrtf((float)head_dim);
+    const PagedPrefillGrid g{grid3[0], grid3[1], grid3[2]};
+    const int G = num_heads / num_kv_heads;
+    hipStream_t st = resolve_stream(s);
+#define PGK_PP(TT, DD, GG)                                                                                                                  \
+    if (head_dim == DD && G == GG)                                                                                                          \
+        return paged_prefill_launch<TT, DD, GG, KV>(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, out, g, total_tokens,   \
+                                                    num_heads, num_kv_heads, block_size, max_blocks_per_seq, scale, kv, st);
+#define PGK_PP_T(TT) PGK_PP(TT, 128, 1) PGK_PP(TT, 128, 2) PGK_PP(TT, 128, 4) PGK_PP(TT, 128, 8) PGK_PP(TT, 64, 1) PGK_PP(TT, 64, 2) PGK_PP(TT, 64, 4) PGK_PP(TT, 64, 8)
+    if (dt == PGK_BF16) { PGK_PP_T(bf16) } else { PGK_PP_T(f16) }
+#undef PGK_PP_T
+#undef PGK_PP
+    return set_error(PGK_ERR_INVALID, "%s: no kernel for D=%d G=%d", name, head_dim, G);
 }
 
 }  // namespace pgk
@@ -310,22 +390,26 @@ pgk_status pgk_paged_attention_prefill(const void* q, const void* k_cache, const
                 max_blocks_per_seq);
     int grid3[3];
     if (!pgk_paged_prefill_plan(num_seqs, max_query_len, num_heads, num_kv_heads, head_dim, dt, grid3)) return PGK_ERR_INVALID;
-    PGK_REQUIRE(aligned16(q) && aligned16(k_cache) && aligned16(v_cache) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0,
-                "pgk_paged_attention_prefill: q and the caches must be 16-byte aligned, out 8-byte aligned");
-    if (max_query_len == 0) return PGK_OK;       // every sequence idle
-    if (scale <= 0.f) scale = 1.0f / sqrtf((float)head_dim);
-    const PagedPrefillGrid g{grid3[0], grid3[1], grid3[2]};
-    const int G = num_heads / num_kv_heads;
-    hipStream_t st = resolve_stream(s);
-#define PGK_PP(TT, DD, GG)                                                                                                                  \
-    if (head_dim == DD && G == GG)                                                                                                          \
-        return paged_prefill_launch<TT, DD, GG>(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, out, g, total_tokens, num_heads, \
-                                                num_kv_heads, block_size, max_blocks_per_seq, scale, st);
-#define PGK_PP_T(TT) PGK_PP(TT, 128, 1) PGK_PP(TT, 128, 2) PGK_PP(TT, 128, 4) PGK_PP(TT, 128, 8) PGK_PP(TT, 64, 1) PGK_PP(TT, 64, 2) PGK_PP(TT, 64, 4) PGK_PP(TT, 64, 8)
-    if (dt == PGK_BF16) { PGK_PP_T(bf16) } else { PGK_PP_T(f16) }
-#undef PGK_PP_T
-#undef PGK_PP
-    return set_error(PGK_ERR_INVALID, "pgk_paged_attention_prefill: no kernel for D=%d G=%d", head_dim, G);
+    return paged_prefill_dispatch("pgk_paged_attention_prefill", q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, out, grid3,
+                                  total_tokens, max_query_len, num_heads, num_kv_heads, head_dim, block_size, max_blocks_per_seq, scale, dt,
+                                  PagedKV16{}, s);
+}
+
+pgk_status pgk_paged_attention_prefill_fp8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale,
+                                           const int32_t* block_tables, const int32_t* context_lens, const int32_t* cu_seqlens_q, void* out,
+                                           int num_seqs, int total_tokens, int max_query_len, int num_heads, int num_kv_heads, int head_dim,
+                                           int block_size, int max_blocks_per_seq, float scale, pgk_dtype dt, pgk_stream s) {
+    PGK_REQUIRE(q && k_cache && v_cache && k_scale && v_scale && block_tables && context_lens && cu_seqlens_q && out,
+                "pgk_paged_attention_prefill_fp8: null pointer");
+    PGK_REQUIRE(total_tokens >= 1 && max_query_len >= 0 && max_query_len <= total_tokens,
+                "pgk_paged_attention_prefill_fp8: bad token counts (total_tokens=%d, max_query_len=%d)", total_tokens, max_query_len);
+    PGK_REQUIRE(block_size >= 1 && max_blocks_per_seq >= 1, "pgk_paged_attention_prefill_fp8: bad paging (block_size=%d, max_blocks=%d)", block_size,
+                max_blocks_per_seq);
+    int grid3[3];
+    if (!pgk_paged_kv_fp8_plan(1, num_seqs, max_query_len, num_heads, num_kv_heads, head_dim, dt, grid3)) return PGK_ERR_INVALID;
+    return paged_prefill_dispatch("pgk_paged_attention_prefill_fp8", q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, out, grid3,
+                                  total_tokens, max_query_len, num_heads, num_kv_heads, head_dim, block_size, max_blocks_per_seq, scale, dt,
+                                  PagedKV8{k_scale, v_scale}, s);
 }
 
 }  // extern "C"

@@ -39,6 +39,8 @@ from pygpukit_amd.ops.unary import abs, cos, exp, log, neg, relu, rsqrt, sin, sq
 from pygpukit_amd.ops.paged import (allocate_kv_cache, argmax_sample, check_eos, compute_cumsum, copy_to_paged_cache, gather_embeddings,
                                     paged_attention_prefill, paged_attention_v1, paged_prefill_plan, prepare_batch_inputs,
                                     prepare_position_ids, reshape_and_cache, scatter_last_token_logits)
+from pygpukit_amd.ops.paged import (copy_to_paged_cache_fp8, paged_attention_prefill_fp8, paged_attention_v1_fp8, paged_kv_fp8_plan,
+                                    reshape_and_cache_fp8)
 from pygpukit_amd.ops.sampling import (sample_greedy, sample_multinomial, sample_token_gpu, sample_topk, sample_topk_to_buf_ptr,
                                        sample_topp, set_sampling_seed)
 from pygpukit_amd.ops.tensor import (cast_bf16_to_f32, cast_f16_to_f32, cast_f32_to_bf16, cast_f32_to_f16, concat_axis0,

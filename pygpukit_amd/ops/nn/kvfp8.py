@@ -9,8 +9,8 @@ code = rne_e4m3(clamp(x / scale, +-448)) with a correctly rounded float32 divisi
   sdpa_causal_fixed_cache_fp8 / _ptr    one query row over rows 0 .. context_len - 1 of the dequantised caches (split-KV)
   sdpa_kv_fp8_plan                      ("kv_fp8_split", chunks per kv head); needs no GPU work
 
-bfloat16 / float16 queries, head_dim 64 or 128.  A query of several rows over an fp8 cache, the window / iRoPE / ALiBi forms, paged
-attention and the native engine have no fp8 kernel."""
+bfloat16 / float16 queries, head_dim 64 or 128.  A query of several rows over this contiguous fp8 cache, the window / iRoPE / ALiBi
+forms and the native engine have no fp8 kernel; fp8 PAGES are ops.paged's (*_fp8)."""
 
 from __future__ import annotations
 

@@ -9,7 +9,7 @@ import numpy as np
 
 from pygpukit_amd import _hip
 from pygpukit_amd.core.array import GPUArray
-from pygpukit_amd.core.dtypes import as_dtype, bfloat16, float16, int32
+from pygpukit_amd.core.dtypes import as_dtype, bfloat16, float16, int32, uint8
 from pygpukit_amd.core.factory import from_numpy, zeros
 from pygpukit_amd.ops._common import call, check_out
 
@@ -130,6 +130,125 @@ def reshape_and_cache(k: GPUArray, v: GPUArray, k_cache: GPUArray, v_cache: GPUA
     _cache_write(k, v, k_cache, v_cache, slot_mapping, "reshape_and_cache")
 
 
+# ---- FP8 (OCP e4m3) pages: uint8 caches [num_blocks, num_kv_heads, block_size, head_dim] (allocate_kv_cache(..., dtype=uint8)) with
+# one float32 scale per kv head for K and one for V; value = e4m3(code) * scale.  bfloat16 / float16 queries and outputs, head_dim
+# 64 / 128, num_heads / num_kv_heads in {1, 2, 4, 8}, any block_size; there is no other path. -----------------------------------
+def _check_fp8_cache(k_cache: GPUArray, v_cache: GPUArray, k_scale: GPUArray, v_scale: GPUArray, name: str) -> None:
+    if k_cache.ndim != 4 or v_cache.shape != k_cache.shape or k_cache.dtype != uint8 or v_cache.dtype != uint8:
+        raise ValueError(f"{name}: K/V caches must be matching uint8 [num_blocks, num_kv_heads, block_size, head_dim] arrays of e4m3 "
+                         f"codes, got {k_cache.shape} {k_cache.dtype} and {v_cache.shape} {v_cache.dtype}")
+    for label, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s.dtype != _f32() or s.ndim != 1 or s.size != k_cache.shape[1]:
+            raise ValueError(f"{name}: {label} must be float32 [num_kv_heads = {k_cache.shape[1]}], got {s.shape} {s.dtype}")
+
+
+def _check_fp8_query(q: GPUArray, k_cache: GPUArray, name: str) -> None:
+    if q.ndim != 3 or q.dtype not in (float16, bfloat16) or q.shape[2] != k_cache.shape[3] or q.shape[0] < 1:
+        raise ValueError(f"{name}: q {q.shape} {q.dtype} must be bfloat16 / float16 [rows, num_heads, head_dim = {k_cache.shape[3]}]")
+
+
+def paged_kv_fp8_plan(op: str, num_seqs: int, bound: int, num_heads: int, num_kv_heads: int, head_dim: int,
+                      dtype) -> tuple[str, tuple[int, int, int] | None]:
+    """What the fp8-page attention ops launch.  op "decode" (bound = max_context): ("paged_kv_fp8_split", (KV slices, groups of
+    min(num_heads / num_kv_heads, 4) query heads, sequences)); op "prefill" (bound = max_query_len): ("paged_kv_fp8_prefill_mfma",
+    (column tiles, kv heads, sequences)); or (the reason the call is refused, None).  Needs no GPU work."""
+    if op not in ("decode", "prefill"):
+        raise ValueError(f"paged_kv_fp8_plan: op must be 'decode' or 'prefill', got {op!r}")
+    lib = _hip.load()
+    grid = (C.c_int * 3)()
+    name = lib.pgk_paged_kv_fp8_plan(int(op == "prefill"), int(num_seqs), int(bound), int(num_heads), int(num_kv_heads), int(head_dim),
+                                     as_dtype(dtype).code, grid)
+    if name is None:
+        msg = lib.pgk_last_error()
+        return (msg.decode(errors="replace") if msg else "paged_kv_fp8_plan: refused"), None
+    return name.decode(), (grid[0], grid[1], grid[2])
+
+
+def _cache_write_fp8(k: GPUArray, v: GPUArray, k_cache: GPUArray, v_cache: GPUArray, slot_mapping: GPUArray, k_scale: GPUArray,
+                     v_scale: GPUArray, name: str) -> None:
+    _check_fp8_cache(k_cache, v_cache, k_scale, v_scale, name)
+    if k.ndim != 3 or v.shape != k.shape or k.dtype not in (float16, bfloat16) or v.dtype != k.dtype:
+        raise ValueError(f"{name}: K/V must be matching bfloat16 / float16 [tokens, num_kv_heads, head_dim] arrays")
+    if k.shape[1] != k_cache.shape[1] or k.shape[2] != k_cache.shape[3]:
+        raise ValueError(f"{name}: K {k.shape} does not match the cache {k_cache.shape}")
+    if slot_mapping.dtype != int32 or slot_mapping.size != k.shape[0]:
+        raise ValueError(f"{name}: slot_mapping must be int32 [tokens]")
+    call("pgk_paged_cache_write_fp8", k._p, v._p, k_cache._p, v_cache._p, k_scale._p, v_scale._p, slot_mapping._p, k.shape[0], k.shape[1],
+         k_cache.shape[0], k_cache.shape[2], k.shape[2], k.dtype.code, None)
+
+
+def reshape_and_cache_fp8(k: GPUArray, v: GPUArray, k_cache: GPUArray, v_cache: GPUArray, slot_mapping: GPUArray, k_scale: GPUArray,
+                          v_scale: GPUArray) -> None:
+    """reshape_and_cache into uint8 pages: code = rne_e4m3(clamp(x / scale[head], +-448)); K and V in one launch; a negative slot
+    is skipped."""
+    _cache_write_fp8(k, v, k_cache, v_cache, slot_mapping, k_scale, v_scale, "reshape_and_cache_fp8")
+
+
+def copy_to_paged_cache_fp8(k_new: GPUArray, v_new: GPUArray, k_cache: GPUArray, v_cache: GPUArray, slot_mapping: GPUArray,
+                            k_scale: GPUArray, v_scale: GPUArray) -> None:
+    """copy_to_paged_cache into uint8 pages (the same scatter as reshape_and_cache_fp8)."""
+    _cache_write_fp8(k_new, v_new, k_cache, v_cache, slot_mapping, k_scale, v_scale, "copy_to_paged_cache_fp8")
+
+
+def paged_attention_v1_fp8(q: GPUArray, k_cache: GPUArray, v_cache: GPUArray, k_scale: GPUArray, v_scale: GPUArray,
+                           block_tables: GPUArray, context_lens: GPUArray, scale: float = 0.0, *, out: GPUArray | None = None,
+                           max_context: int | None = None) -> GPUArray:
+    """paged_attention_v1 over uint8 pages of e4m3 codes.  q [num_seqs, num_heads, head_dim] (bfloat16 / float16) -> same shape; a
+    sequence with context_lens <= 0 gets zeros.  max_context bounds context_lens (default: every page of the table) and only sizes
+    the KV split; up to 512 is one slice with no workspace and one launch."""
+    name = "paged_attention_v1_fp8"
+    _check_fp8_cache(k_cache, v_cache, k_scale, v_scale, name)
+    _check_fp8_query(q, k_cache, name)
+    num_seqs, num_heads, head_dim = q.shape
+    _, num_kv_heads, block_size, _ = k_cache.shape
+    if block_tables.dtype != int32 or block_tables.ndim != 2 or block_tables.shape[0] != num_seqs:
+        raise ValueError(f"{name}: block_tables must be int32 [num_seqs, max_blocks_per_seq]")
+    if context_lens.dtype != int32 or context_lens.size != num_seqs:
+        raise ValueError(f"{name}: context_lens must be int32 [num_seqs]")
+    max_blocks = block_tables.shape[1]
+    max_context = max_blocks * block_size if max_context is None else int(max_context)
+    plan, _ = paged_kv_fp8_plan("decode", num_seqs, max_context, num_heads, num_kv_heads, head_dim, q.dtype)
+    if plan != "paged_kv_fp8_split":
+        raise ValueError(plan)
+    o = check_out(out, q.shape, q.dtype, name)
+    ws_bytes = _hip.load().pgk_paged_attention_fp8_workspace_bytes(num_seqs, num_heads, head_dim, max_context)
+    ws = GPUArray((ws_bytes // 4,), _f32()) if ws_bytes else None
+    call("pgk_paged_attention_v1_fp8", q._p, k_cache._p, v_cache._p, k_scale._p, v_scale._p, block_tables._p, context_lens._p, o._p,
+         num_seqs, num_heads, num_kv_heads, head_dim, block_size, max_blocks, max_context, C.c_float(scale),
+         ws._p if ws is not None else None, q.dtype.code, None)
+    return o
+
+
+def paged_attention_prefill_fp8(q: GPUArray, k_cache: GPUArray, v_cache: GPUArray, k_scale: GPUArray, v_scale: GPUArray,
+                                block_tables: GPUArray, context_lens: GPUArray, cu_seqlens_q: GPUArray, scale: float = 0.0, *,
+                                out: GPUArray | None = None, max_query_len: int | None = None) -> GPUArray:
+    """paged_attention_prefill over uint8 pages of e4m3 codes: the same packed batch, masks and grid; write this step's K / V with
+    reshape_and_cache_fp8 first."""
+    name = "paged_attention_prefill_fp8"
+    _check_fp8_cache(k_cache, v_cache, k_scale, v_scale, name)
+    _check_fp8_query(q, k_cache, name)
+    total_tokens, num_heads, head_dim = q.shape
+    _, num_kv_heads, block_size, _ = k_cache.shape
+    if block_tables.dtype != int32 or block_tables.ndim != 2:
+        raise ValueError(f"{name}: block_tables must be int32 [num_seqs, max_blocks_per_seq]")
+    num_seqs, max_blocks = block_tables.shape
+    if context_lens.dtype != int32 or context_lens.size != num_seqs:
+        raise ValueError(f"{name}: context_lens must be int32 [num_seqs]")
+    if cu_seqlens_q.dtype != int32 or cu_seqlens_q.size != num_seqs + 1:
+        raise ValueError(f"{name}: cu_seqlens_q must be int32 [num_seqs + 1]")
+    max_query_len = total_tokens if max_query_len is None else int(max_query_len)
+    if not 0 <= max_query_len <= total_tokens:
+        raise ValueError(f"{name}: max_query_len {max_query_len} outside [0, total_tokens = {total_tokens}]")
+    plan, _ = paged_kv_fp8_plan("prefill", num_seqs, max_query_len, num_heads, num_kv_heads, head_dim, q.dtype)
+    if plan != "paged_kv_fp8_prefill_mfma":
+        raise ValueError(plan)
+    o = check_out(out, q.shape, q.dtype, name)
+    call("pgk_paged_attention_prefill_fp8", q._p, k_cache._p, v_cache._p, k_scale._p, v_scale._p, block_tables._p, context_lens._p,
+         cu_seqlens_q._p, o._p, num_seqs, total_tokens, max_query_len, num_heads, num_kv_heads, head_dim, block_size, max_blocks,
+         C.c_float(scale), q.dtype.code, None)
+    return o
+
+
 def gather_embeddings(token_ids: GPUArray, embeddings: GPUArray, total_tokens: int) -> GPUArray:
     if token_ids.dtype != int32 or token_ids.size < total_tokens or embeddings.ndim != 2:
         raise ValueError("gather_embeddings: need int32 ids [total_tokens] and a 2D table")
@@ -197,5 +316,6 @@ def prepare_batch_inputs(token_lists: list[list[int]]) -> tuple[GPUArray, int]:
     return from_numpy(flat), int(flat.size)
 
 
-__all__ = ["allocate_kv_cache", "paged_attention_v1", "paged_attention_prefill", "paged_prefill_plan", "copy_to_paged_cache", "reshape_and_cache", "gather_embeddings",
+__all__ = ["allocate_kv_cache", "paged_attention_v1", "paged_attention_prefill", "paged_prefill_plan", "copy_to_paged_cache", "reshape_and_cache",
+           "paged_kv_fp8_plan", "reshape_and_cache_fp8", "copy_to_paged_cache_fp8", "paged_attention_v1_fp8", "paged_attention_prefill_fp8", "gather_embeddings",
            "scatter_last_token_logits", "prepare_position_ids", "argmax_sample", "check_eos", "compute_cumsum", "prepare_batch_inputs"]
