@@ -670,6 +670,27 @@ pgk_status pgk_sdpa_fixed_cache_fp8(const void* q, const void* k_cache, const vo
  * pgk_sdpa_fixed_cache_fp8 rejects: hq % hkv, d outside {64, 128}, max_seq < 1, dt outside {bf16, f16}, unaligned buffers. */
 const char* pgk_sdpa_kv_fp8_plan(int hq, int hkv, int d, int max_seq, pgk_dtype dt, int aligned, int* nsplit);
 
+/* ---- Multi-head latent attention (DeepSeek MLA, absorbed decode form; ops_mla.hip) ----------------------------------------------
+ * Latent cache [max_seq, 576] (bf16 / f16: dt): row r = [c_r (512): the RMS-normed compressed latent | kpe_r (64): the roped shared
+ * key], one row for all heads.  Every buffer 16-byte aligned. */
+/* kv_a [seq, 576] -> rows pos .. pos + seq - 1 of `cache`: columns 0..511 = rmsnorm(kv_a[:, :512], gamma[512], eps), columns 512..575 =
+ * rotate-half RoPE of kv_a[:, 512:] with row pos + s of cos / sin [table_rows, 64] (dt, or fp32 when f32_table); the bits are those of
+ * pgk_rmsnorm + pgk_rope_inplace + a copy.  pos = pos_buf[0] (device int32; rows outside the cache or the table are not stored) when
+ * pos_buf is non-NULL, else h_pos. */
+pgk_status pgk_mla_cache_write(const void* kv_a, const void* gamma, const void* cos, const void* sin, void* cache, int seq, int max_seq,
+                               int table_rows, float eps, int h_pos, const int32_t* pos_buf, int f32_table, pgk_dtype dt, pgk_stream s);
+/* q [q_len, num_heads, 576] = [q_abs (512) | q_pe (64)] with W_UK absorbed, out [q_len, num_heads, 512]:
+ * out[i][h] = sum_r softmax_r(scale * <q[i][h], cache[r]>) * cache[r][:512] over r <= ctx - q_len + i.  ctx = ctx_buf[0] clamped to
+ * [0, max_seq] when ctx_buf is non-NULL (the grid depends on max_seq only), else h_context_len in [q_len, max_seq].  Rows at and
+ * beyond ctx are never read.  1 <= num_heads <= 128, scale > 0 (no default).  workspace: pgk_sdpa_mla_workspace_bytes, may be NULL
+ * when that is 0 (one chunk). */
+pgk_status pgk_sdpa_mla_fixed_cache(const void* q, const void* cache, void* out, int num_heads, int q_len, int max_seq, float scale,
+                                    int h_context_len, const int32_t* ctx_buf, void* workspace, pgk_dtype dt, pgk_stream s);
+size_t pgk_sdpa_mla_workspace_bytes(int num_heads, int q_len, int max_seq);
+/* Host-only: "mla_latent_mfma", through *cols the (query row, head) columns of a query tile and through *chunks the cache chunks
+ * (either may be NULL); NULL (and pgk_last_error) for what pgk_sdpa_mla_fixed_cache rejects. */
+const char* pgk_sdpa_mla_plan(int num_heads, int q_len, int max_seq, pgk_dtype dt, int* cols, int* chunks);
+
 /* ---------------------------------------------------------------------- engine ------ */
 /* Native decode/prefill launcher: one C call (or one hipGraph launch) per token step instead of
  * ~21 Python-dispatched launches per layer.  Replaces the device-dispatch half

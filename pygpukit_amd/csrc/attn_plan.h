@@ -40,6 +40,30 @@ inline bool decode_fast(int q_len, int d, bool has_workspace, bool ptrs_aligned,
     return q_len == 1 && (d == 128 || d == 64) && has_workspace && ptrs_aligned && !(flash_decoding_off && !device_ctx);
 }
 
+// ---- pgk_sdpa_mla_fixed_cache (ops_mla.hip): multi-head latent attention over ONE shared row of 576 per position ---------------
+// A column of the score tile is a (query row, head) pair - column c is row c / H, head c % H - and a workgroup owns MLA_COLS
+// consecutive columns x one chunk of the cache.  There is one "kv head", so the chunks are what fills the chip: enough of them
+// for two workgroups per CU (the kernel's occupancy) over the column tiles there are, never shorter than MLA_MIN_CHUNK rows at
+// full context (four KV tiles: below that the partial record, 514 floats per column, costs more than the rows it covers), and one
+// chunk for a cache that short.  Fixed by max_seq, so a captured graph keeps its grid and its workspace while the context grows;
+// the live chunk length follows the context (decode_chunk_len with whole KV tiles, attn_core.hip.h).
+constexpr int MLA_LATENT = 512, MLA_ROPE = 64, MLA_WIDTH = MLA_LATENT + MLA_ROPE, MLA_MAX_HEADS = 128;
+constexpr int MLA_COLS = 32, MLA_KEYS = 32, MLA_MIN_CHUNK = 128, MLA_MAX_CHUNKS = 128;
+inline const char* mla_refusal(int heads, int q_len, int max_seq, bool is_16bit) {
+    if (heads < 1 || heads > MLA_MAX_HEADS) return "num_heads must be 1 .. 128";
+    if (!is_16bit) return "bfloat16 / float16 only";
+    if (max_seq < 1) return "cache rows < 1";
+    if (q_len < 1 || q_len > max_seq) return "q_len must be 1 .. max_seq";
+    return nullptr;
+}
+inline int mla_col_tiles(int heads, int q_len) { return ceil_div((long long)heads * q_len, MLA_COLS); }
+// 512 workgroups: two for each of the MI355X's 256 CUs - a constant, not a device query, so the plan is the same on every host
+inline int mla_chunks(int heads, int q_len, int max_seq) {
+    const int by_rows = max_seq / MLA_MIN_CHUNK, by_fill = ceil_div(512, mla_col_tiles(heads, q_len));
+    const int n = by_rows < by_fill ? by_rows : by_fill;
+    return n < 1 ? 1 : (n > MLA_MAX_CHUNKS ? MLA_MAX_CHUNKS : n);
+}
+
 // ---- pgk_paged_attention_v1: slices of ~512 positions per (sequence, kv head); 1 = no workspace, no combine launch ------------
 inline int paged_nsplit(int max_context) {
     const int n = (max_context + 511) / 512;

@@ -1,0 +1,106 @@
+"""[build-defined] Multi-head latent attention layer (DeepSeek-V2 / V3 / R1, Kimi-K2) over a fixed latent cache, absorbed form.
+
+Constructed from the HF-named weights, RoPE rows already in this project's half layout:
+  q_proj [H * (nope + 64), hidden]   or   q_a_proj [q_lora, hidden] / q_a_layernorm [q_lora] / q_b_proj [H * (nope + 64), q_lora]
+  kv_a_proj_with_mqa [512 + 64, hidden], kv_a_layernorm [512], kv_b_proj [H * (nope + v), 512], o_proj [hidden, H * v]
+At load kv_b_proj is split once, on the device, into W_UK [H, nope, 512] and W_UV [H, v, 512] (and W_UV^T [H, 512, v], the operand of
+the output GEMM), and the query projection's rows into the heads' no-position rows and their rope rows, so both come out contiguous.
+
+forward_fixed_cache(x [S, hidden], start_position): the query projections; q_abs = q_nope . W_UK per head (batched_matmul) and
+rope_inplace on q_pe; ONE SMALL PACK of both into the [S, H, 576] query buffer (transposes and a row concatenation of existing ops: no
+op here writes a strided output); mla_cache_write; sdpa_mla_fixed_cache; o = out . W_UV^T per head; o_proj.  Only existing ops run
+around the two new ones.  Out of scope: INTEGRATION.md."""
+
+from __future__ import annotations
+
+import numpy as np
+
+from pygpukit_amd import _hip
+from pygpukit_amd.core.array import GPUArray
+from pygpukit_amd.core.factory import from_numpy, zeros
+from pygpukit_amd.ops.matmul import batched_matmul, transpose
+from pygpukit_amd.ops.nn.mla import LATENT, ROPE, WIDTH, mla_cache_write, sdpa_mla_fixed_cache
+from pygpukit_amd.ops.nn.norm import rmsnorm
+from pygpukit_amd.ops.nn.rope import rope_inplace_f32table
+from pygpukit_amd.ops.tensor import concat_axis0, transpose_3d_012, transpose_3d_021
+
+from .linear import LinearBF16
+from .rope import precompute_freqs_cis
+
+
+def _gather_rows(src: GPUArray, dst: GPUArray, heads: int, src_head_rows: int, first: int, count: int) -> None:
+    """dst [heads * count, cols] <- rows first .. first + count - 1 of each head's src_head_rows rows of src: one device copy per head."""
+    row = src.shape[-1] * src.itemsize
+    for h in range(heads):
+        _hip.call("pgk_memcpy_d2d", dst.data_ptr() + h * count * row, src.data_ptr() + (h * src_head_rows + first) * row, count * row, None)
+
+
+class MLAttention:
+    def __init__(self, *, num_heads: int, qk_nope_head_dim: int, v_head_dim: int, softmax_scale: float, kv_a_proj_with_mqa: GPUArray,
+                 kv_a_layernorm: GPUArray, kv_b_proj: GPUArray, o_proj: GPUArray, q_proj: GPUArray | None = None,
+                 q_a_proj: GPUArray | None = None, q_a_layernorm: GPUArray | None = None, q_b_proj: GPUArray | None = None,
+                 qk_rope_head_dim: int = ROPE, kv_lora_rank: int = LATENT, max_position_embeddings: int = 4096, rope_theta: float = 10000.0,
+                 norm_eps: float = 1e-6):
+        if qk_rope_head_dim != ROPE or kv_lora_rank != LATENT:
+            raise ValueError(f"MLAttention: qk_rope_head_dim must be {ROPE} and kv_lora_rank {LATENT} (the latent cache row is {WIDTH} wide)")
+        if (q_proj is None) == (q_a_proj is None) or (q_a_proj is not None and (q_a_layernorm is None or q_b_proj is None)):
+            raise ValueError("MLAttention: give q_proj, or q_a_proj with q_a_layernorm and q_b_proj")
+        if not softmax_scale > 0:
+            raise ValueError(f"MLAttention: softmax_scale must be positive, got {softmax_scale}")
+        H, nope, v = num_heads, qk_nope_head_dim, v_head_dim
+        qw = q_proj if q_proj is not None else q_b_proj
+        if qw.shape[0] != H * (nope + ROPE) or kv_a_proj_with_mqa.shape[0] != WIDTH or kv_b_proj.shape != (H * (nope + v), LATENT) \
+                or o_proj.shape[1] != H * v or kv_a_layernorm.shape != (LATENT,):
+            raise ValueError("MLAttention: weight shapes do not match num_heads / qk_nope_head_dim / v_head_dim")
+        self.num_heads, self.qk_nope_head_dim, self.v_head_dim, self.softmax_scale, self.norm_eps = H, nope, v, float(softmax_scale), norm_eps
+        self.q_a_proj = LinearBF16(q_a_proj) if q_a_proj is not None else None
+        self.q_a_layernorm = q_a_layernorm
+        # the query projection's rows, regrouped: every head's no-position rows, then every head's rope rows
+        q_nope_w, q_pe_w = GPUArray((H * nope, qw.shape[1]), qw.dtype), GPUArray((H * ROPE, qw.shape[1]), qw.dtype)
+        _gather_rows(qw, q_nope_w, H, nope + ROPE, 0, nope)
+        _gather_rows(qw, q_pe_w, H, nope + ROPE, nope, ROPE)
+        self.q_nope_proj, self.q_pe_proj = LinearBF16(q_nope_w), LinearBF16(q_pe_w)
+        self.kv_a_proj_with_mqa, self.kv_a_layernorm, self.o_proj = LinearBF16(kv_a_proj_with_mqa), kv_a_layernorm, LinearBF16(o_proj)
+        self.w_uk, self.w_uv = GPUArray((H, nope, LATENT), kv_b_proj.dtype), GPUArray((H, v, LATENT), kv_b_proj.dtype)
+        _gather_rows(kv_b_proj, self.w_uk, H, nope + v, 0, nope)
+        _gather_rows(kv_b_proj, self.w_uv, H, nope + v, nope, v)
+        self._w_uv_t = transpose_3d_012(self.w_uv)          # W_UV^T per head [H, 512, v]: the [K, N] operand of out . W_UV^T
+        cos, sin = precompute_freqs_cis(ROPE, max_position_embeddings, rope_theta)
+        self._cos, self._sin = from_numpy(cos.astype(np.float32)), from_numpy(sin.astype(np.float32))
+        self._cache: GPUArray | None = None
+
+    def init_fixed_cache(self, max_seq: int, dtype: str = "bfloat16") -> None:
+        """One latent cache [max_seq, 576] for all heads."""
+        if max_seq > self._cos.shape[0]:
+            raise ValueError(f"init_fixed_cache: {max_seq} rows beyond max_position_embeddings {self._cos.shape[0]}")
+        self._cache = zeros((max_seq, WIDTH), dtype)
+
+    def forward_fixed_cache(self, x: GPUArray, start_position: int) -> GPUArray:
+        """x [S, hidden], a prompt chunk or one token at positions start_position ..: writes their latent rows, attends rows
+        0 .. start_position + S - 1, returns [S, hidden]."""
+        if self._cache is None:
+            raise RuntimeError("MLAttention: init_fixed_cache first")
+        S, H, nope, v = x.shape[0], self.num_heads, self.qk_nope_head_dim, self.v_head_dim
+        if start_position < 0 or start_position + S > self._cache.shape[0]:
+            raise ValueError(f"forward_fixed_cache: positions {start_position}..{start_position + S - 1} outside the cache of {self._cache.shape[0]} rows")
+        xq = x if self.q_a_proj is None else rmsnorm(self.q_a_proj(x), self.q_a_layernorm, self.norm_eps)
+        q_nope = self.q_nope_proj(xq).view((S, H, nope))
+        q_pe = self.q_pe_proj(xq).view((S, H, ROPE))
+        cos, sin = self._cos._view(start_position * ROPE, (S, ROPE)), self._sin._view(start_position * ROPE, (S, ROPE))
+        rope_inplace_f32table(q_pe, q_pe._view(0, (S, 0, ROPE)), cos, sin)
+        # [S, H, *] and [H, S, *] are the same bytes for one token
+        q_nope_h = q_nope.view((H, 1, nope)) if S == 1 else transpose_3d_021(q_nope)
+        q_abs = batched_matmul(q_nope_h, self.w_uk)                                  # [H, S, 512]
+        q_abs = q_abs.view((H * S, LATENT)) if S == 1 else transpose_3d_021(q_abs).view((S * H, LATENT))
+        # the pack: [q_abs | q_pe] per (row, head) = rows of [576, S H] concatenated, transposed back
+        q = transpose(concat_axis0(transpose(q_abs), transpose(q_pe.view((S * H, ROPE))))).view((S, H, WIDTH))
+        mla_cache_write(self.kv_a_proj_with_mqa(x), self.kv_a_layernorm, self._cos, self._sin, self._cache, start_position, self.norm_eps)
+        out = GPUArray((S, H, LATENT), x.dtype)
+        sdpa_mla_fixed_cache(q, self._cache, out, start_position + S, self.softmax_scale)
+        out_h = out.view((H, 1, LATENT)) if S == 1 else transpose_3d_021(out)
+        o = batched_matmul(out_h, self._w_uv_t)                                      # [H, S, v]
+        o = o.view((1, H * v)) if S == 1 else transpose_3d_021(o).view((S, H * v))
+        return self.o_proj(o)
+
+
+__all__ = ["MLAttention"]

@@ -1,0 +1,118 @@
+"""[build-defined] Multi-head latent attention (DeepSeek-V2 / V3 / R1, Kimi-K2) in its absorbed decode form.
+
+Latent cache [max_seq, 576], one row for ALL heads: row r = [c_r (512): the RMS-normed compressed latent | kpe_r (64): the roped
+shared key].  The same 512 latent columns are the keys and the values.
+
+  mla_cache_write / _ptr        kv_a [S, 576] (kv_a_proj_with_mqa's output) -> rows position ..: rmsnorm of the first 512 columns,
+                                rotate-half RoPE of the last 64 at rows position + s of cos / sin [max_pos, 64]; one launch, the bits
+                                of rmsnorm + rope_inplace (rope_inplace_f32table for float32 tables) + a copy
+  sdpa_mla_fixed_cache / _ptr   q [q_len, H, 576] = [q_abs | q_pe] with W_UK absorbed -> out [q_len, H, 512]:
+                                out[i, h] = sum_r softmax_r(scale <q[i, h], cache[r]>) cache[r, :512], r <= context_len - q_len + i
+  sdpa_mla_plan                 ("mla_latent_mfma", query-tile columns, cache chunks); needs no GPU work
+
+bfloat16 / float16, 1 <= H <= 128.  `scale` is required and positive: the model's is mscale^2 / sqrt(192), not 1 / sqrt(576)."""
+
+from __future__ import annotations
+
+import ctypes as C
+
+from pygpukit_amd import _hip
+from pygpukit_amd.core.array import GPUArray
+from pygpukit_amd.core.dtypes import as_dtype, bfloat16, float16, float32, int32
+from pygpukit_amd.ops._common import call
+
+LATENT, ROPE, WIDTH, MAX_HEADS = 512, 64, 576, 128
+_ws_cache: dict[tuple[int, int, int], GPUArray] = {}
+
+
+def _check_write(kv_a, gamma, cos, sin, cache, name: str) -> int:
+    if kv_a.ndim != 2 or kv_a.shape[1] != WIDTH or kv_a.dtype not in (bfloat16, float16):
+        raise ValueError(f"{name}: kv_a must be bfloat16 / float16 [S, {WIDTH}], got {kv_a.shape}/{kv_a.dtype}")
+    if cache.ndim != 2 or cache.shape[1] != WIDTH or cache.dtype != kv_a.dtype:
+        raise ValueError(f"{name}: cache must be {kv_a.dtype} [max_seq, {WIDTH}], got {cache.shape}/{cache.dtype}")
+    if gamma.shape != (LATENT,) or gamma.dtype != kv_a.dtype:
+        raise ValueError(f"{name}: gamma must be {kv_a.dtype} [{LATENT}], got {gamma.shape}/{gamma.dtype}")
+    if cos.ndim != 2 or cos.shape[1] != ROPE or sin.shape != cos.shape or cos.dtype != sin.dtype or cos.dtype not in (float32, kv_a.dtype):
+        raise ValueError(f"{name}: cos / sin must be float32 or {kv_a.dtype} [max_pos, {ROPE}], got {cos.shape}/{cos.dtype} and "
+                         f"{sin.shape}/{sin.dtype}")
+    return int(cos.dtype == float32)
+
+
+def mla_cache_write(kv_a: GPUArray, gamma: GPUArray, cos: GPUArray, sin: GPUArray, cache: GPUArray, position: int, eps: float = 1e-6) -> None:
+    """kv_a [S, 576] -> rows position .. position + S - 1 of the latent cache [max_seq, 576]."""
+    f32_table = _check_write(kv_a, gamma, cos, sin, cache, "mla_cache_write")
+    s = kv_a.shape[0]
+    if position < 0 or position + s > cache.shape[0] or position + s > cos.shape[0]:
+        raise ValueError(f"mla_cache_write: rows {position}..{position + s - 1} outside the cache of {cache.shape[0]} rows or the table of "
+                         f"{cos.shape[0]}")
+    call("pgk_mla_cache_write", kv_a._p, gamma._p, cos._p, sin._p, cache._p, s, cache.shape[0], cos.shape[0], float(eps), int(position), None,
+         f32_table, kv_a.dtype.code, None)
+
+
+def mla_cache_write_ptr(kv_a: GPUArray, gamma: GPUArray, cos: GPUArray, sin: GPUArray, cache: GPUArray, position_buf: GPUArray,
+                        eps: float = 1e-6) -> None:
+    """mla_cache_write (a decode step's single row, or any S) with the position read from a device int32 (graph replay); a row
+    outside the cache or the table is not written."""
+    f32_table = _check_write(kv_a, gamma, cos, sin, cache, "mla_cache_write_ptr")
+    if position_buf.dtype != int32:
+        raise ValueError("mla_cache_write_ptr: position_buf must be int32")
+    call("pgk_mla_cache_write", kv_a._p, gamma._p, cos._p, sin._p, cache._p, kv_a.shape[0], cache.shape[0], cos.shape[0], float(eps), 0,
+         position_buf._p, f32_table, kv_a.dtype.code, None)
+
+
+def _check_sdpa(q, cache, out, scale, name: str) -> tuple[int, int, int]:
+    if q.ndim != 3 or q.shape[2] != WIDTH or q.dtype not in (bfloat16, float16):
+        raise ValueError(f"{name}: q must be bfloat16 / float16 [q_len, H, {WIDTH}], got {q.shape}/{q.dtype}")
+    q_len, heads, _ = q.shape
+    if cache.ndim != 2 or cache.shape[1] != WIDTH or cache.dtype != q.dtype:
+        raise ValueError(f"{name}: cache must be {q.dtype} [max_seq, {WIDTH}], got {cache.shape}/{cache.dtype}")
+    if out.shape != (q_len, heads, LATENT) or out.dtype != q.dtype:
+        raise ValueError(f"{name}: out must be {q.dtype} [{q_len}, {heads}, {LATENT}], got {out.shape}/{out.dtype}")
+    if not 1 <= heads <= MAX_HEADS or not 1 <= q_len <= cache.shape[0]:
+        raise ValueError(f"{name}: needs 1 <= H <= {MAX_HEADS} and 1 <= q_len <= max_seq, got H {heads}, q_len {q_len}, max_seq {cache.shape[0]}")
+    if not scale > 0:
+        raise ValueError(f"{name}: scale must be positive (the model's mscale^2 / sqrt(192) has no default), got {scale}")
+    return heads, q_len, cache.shape[0]
+
+
+def _workspace(heads: int, q_len: int, max_seq: int):
+    key = (heads, q_len, max_seq)
+    if key not in _ws_cache:
+        nbytes = _hip.load().pgk_sdpa_mla_workspace_bytes(heads, q_len, max_seq)
+        _ws_cache[key] = GPUArray((nbytes // 4,), float32) if nbytes else None
+    ws = _ws_cache[key]
+    return ws._p if ws is not None else None
+
+
+def sdpa_mla_fixed_cache(q: GPUArray, cache: GPUArray, out: GPUArray, context_len: int, scale: float) -> None:
+    """Query row i of q [q_len, H, 576] sees cache rows 0 .. context_len - q_len + i; out [q_len, H, 512].  Rows at and beyond
+    context_len are never read."""
+    heads, q_len, max_seq = _check_sdpa(q, cache, out, scale, "sdpa_mla_fixed_cache")
+    if context_len < q_len or context_len > max_seq:
+        raise ValueError(f"sdpa_mla_fixed_cache: invalid context_len {context_len} (q_len {q_len}, cache rows {max_seq})")
+    call("pgk_sdpa_mla_fixed_cache", q._p, cache._p, out._p, heads, q_len, max_seq, float(scale), int(context_len), None,
+         _workspace(heads, q_len, max_seq), q.dtype.code, None)
+
+
+def sdpa_mla_fixed_cache_ptr(q: GPUArray, cache: GPUArray, out: GPUArray, context_len_buf: GPUArray, scale: float) -> None:
+    """As above with context_len read from a device int32 (graph replay) and clamped to the cache; the grid depends on max_seq only."""
+    heads, q_len, max_seq = _check_sdpa(q, cache, out, scale, "sdpa_mla_fixed_cache_ptr")
+    if context_len_buf.dtype != int32:
+        raise ValueError("sdpa_mla_fixed_cache_ptr: context_len_buf must be int32")
+    call("pgk_sdpa_mla_fixed_cache", q._p, cache._p, out._p, heads, q_len, max_seq, float(scale), 0, context_len_buf._p,
+         _workspace(heads, q_len, max_seq), q.dtype.code, None)
+
+
+def sdpa_mla_plan(num_heads: int, q_len: int, max_seq: int, dtype) -> tuple[str, int, int]:
+    """("mla_latent_mfma", columns of a query tile, cache chunks) of sdpa_mla_fixed_cache for this shape; ValueError for what the op
+    rejects.  One chunk: the kernel writes `out` itself; more: a merge launch follows."""
+    lib = _hip.load()
+    cols, chunks = C.c_int(0), C.c_int(0)
+    plan = lib.pgk_sdpa_mla_plan(int(num_heads), int(q_len), int(max_seq), as_dtype(dtype).code, C.byref(cols), C.byref(chunks))
+    if plan is None:
+        msg = lib.pgk_last_error()
+        raise ValueError(msg.decode(errors="replace") if msg else "sdpa_mla_plan: invalid call")
+    return plan.decode(), cols.value, chunks.value
+
+
+__all__ = ["mla_cache_write", "mla_cache_write_ptr", "sdpa_mla_fixed_cache", "sdpa_mla_fixed_cache_ptr", "sdpa_mla_plan"]

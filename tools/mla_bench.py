@@ -1,0 +1,97 @@
+"""Time MLA decode attention, sdpa_mla_fixed_cache, against the composition available without it, in one process with alternating
+windows: per round every variant once, then every variant again (A'), N calls each between device events after a warm-up of all of
+them.  bf16, H = 128 and 16, contexts 512, 4096, 32768 and 131072 (the cache as long as the context), q_len 1 and 4.
+
+  (a) sdpa_mla_fixed_cache: one launch over the latent cache [ctx, 576] (plus the merge launch when the plan has several chunks);
+  (b) matmul_nt -> softmax -> matmul on the same absorbed operands, the [q_len H, ctx] scores in global memory.  (b) is given every
+      advantage: the scale is folded into q beforehand, the latent columns are a contiguous [ctx, 512] copy made beforehand, and at
+      q_len 4 it applies NO causal mask (it computes something slightly different and cheaper).
+
+Prints the median us per call of (a), the ratio a / b, the achieved bytes/s of latent rows (ctx x 1152 B) and FLOP/s
+(2 x cols x ctx x (576 + 512)) of (a), the hardware minimum from the peaks below with which of the two bounds it, (a)'s share of it,
+and the spread of each variant against itself (A' / A: the margin inside which two numbers are "the same").  Not a pass / fail gate.
+
+usage: mla_bench.py [--rounds N] [--out FILE]"""
+import argparse, ctypes as C, os, statistics, sys
+import numpy as np
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from pygpukit_amd import _hip
+from pygpukit_amd.core.array import GPUArray
+from pygpukit_amd.core.dtypes import bfloat16
+from pygpukit_amd.core.factory import from_numpy
+
+PEAK_BYTES, PEAK_FLOPS = 8.0e12, 2.5e15          # MI355X: HBM bytes/s, dense bf16 MFMA FLOP/s
+SCALE = 192 ** -0.5
+LINES = []
+
+
+def say(s=""):
+    print(s, flush=True); LINES.append(s)
+
+
+def bf16(a):
+    return from_numpy(np.ascontiguousarray(a, np.float32)).astype(bfloat16)
+
+
+class Timer:
+    def __init__(self):
+        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
+        _hip.call("pgk_event_create", C.byref(self.e0)); _hip.call("pgk_event_create", C.byref(self.e1))
+
+    def window_us(self, run, n):
+        _hip.call("pgk_event_record", self.e0, None)
+        for _ in range(n): run()
+        _hip.call("pgk_event_record", self.e1, None); _hip.call("pgk_event_sync", self.e1)
+        ms = C.c_float(); _hip.call("pgk_event_elapsed_ms", self.e0, self.e1, C.byref(ms))
+        return ms.value * 1000 / n
+
+
+def measure(timer, variants, rounds, n):
+    """-> ({name: median us}, {name: A' / A}): every variant once per round, then every variant again."""
+    names = list(variants)
+    for k in names: variants[k]()
+    _hip.call("pgk_device_sync")
+    t, again = {k: [] for k in names}, {k: [] for k in names}
+    for _ in range(rounds):
+        for k in names: t[k].append(timer.window_us(variants[k], n))
+        for k in names: again[k].append(timer.window_us(variants[k], n))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    return med, {k: statistics.median(again[k]) / med[k] for k in names}
+
+
+def main():
+    from pygpukit_amd.ops import matmul, matmul_nt, softmax
+    from pygpukit_amd.ops.nn import sdpa_mla_fixed_cache, sdpa_mla_plan
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    timer, rng = Timer(), np.random.default_rng(0)
+    block = rng.standard_normal((512, 576)).astype(np.float32)       # repeated: the time does not depend on the values
+    say("| H | q_len | context | plan (columns, chunks) | (a) us | a / b | latent rows GB/s | TFLOP/s | hardware minimum us (bound) | share of it | A'/A a, b |")
+    say("|---|---|---|---|---|---|---|---|---|---|---|")
+    for ctx in (512, 4096, 32768, 131072):
+        rows = np.tile(block, (ctx // 512, 1))
+        cache, latent = bf16(rows), bf16(rows[:, :512])
+        for heads in (128, 16):
+            for q_len in (1, 4):
+                cols = heads * q_len
+                qh = rng.standard_normal((q_len, heads, 576)).astype(np.float32)
+                q, q_scaled, out = bf16(qh), bf16(qh.reshape(cols, 576) * SCALE), GPUArray((q_len, heads, 512), bfloat16)
+                med, floor = measure(timer, {"a": lambda: sdpa_mla_fixed_cache(q, cache, out, ctx, SCALE),
+                                             "b": lambda: matmul(softmax(matmul_nt(q_scaled, cache)), latent)}, a.rounds, 20 if ctx < 32768 else 5)
+                nbytes, flops = ctx * 1152, 2.0 * cols * ctx * (576 + 512)
+                t_b, t_f = nbytes / PEAK_BYTES * 1e6, flops / PEAK_FLOPS * 1e6
+                ratio = med["a"] / med["b"]
+                spread = max(abs(floor["a"] - 1), abs(floor["b"] - 1))
+                verdict = f"{ratio:.3f}" if ratio < 1 - spread else f"{ratio:.3f} (not faster)"
+                say(f"| {heads} | {q_len} | {ctx} | {sdpa_mla_plan(heads, q_len, ctx, 'bfloat16')[1:]} | {med['a']:.1f} | {verdict} | "
+                    f"{nbytes / med['a'] / 1e3:.0f} | {flops / med['a'] / 1e6:.1f} | {max(t_b, t_f):.2f} ({'bytes' if t_b >= t_f else 'matrix'}) | "
+                    f"{max(t_b, t_f) / med['a']:.3f} | {floor['a']:.3f}, {floor['b']:.3f} |")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
