@@ -690,6 +690,17 @@ size_t pgk_sdpa_mla_workspace_bytes(int num_heads, int q_len, int max_seq);
 /* Host-only: "mla_latent_mfma", through *cols the (query row, head) columns of a query tile and through *chunks the cache chunks
  * (either may be NULL); NULL (and pgk_last_error) for what pgk_sdpa_mla_fixed_cache rejects. */
 const char* pgk_sdpa_mla_plan(int num_heads, int q_len, int max_seq, pgk_dtype dt, int* cols, int* chunks);
+/* MLA prefill, the decompressed form at qk_nope 128 / qk_rope 64 / v 128 (ops_mla_prefill.hip).  q_nope [q_len, num_heads, 128],
+ * q_pe [q_len, num_heads, 64] (roped), kv [kv_len, num_heads, 256] = kv_b_proj of latent rows 0 .. kv_len - 1 ([k_nope (128) | v (128)]
+ * per head), cache [max_seq, 576] of which columns 512..575 of rows 0 .. kv_len - 1 are read, out [q_len, num_heads, 128]:
+ * out[i][h] = sum_j softmax_j(scale * (<q_nope[i][h], kv[j][h][:128]> + <q_pe[i][h], cache[j][512:]>)) * kv[j][h][128:] over
+ * j <= kv_len - q_len + i.  1 <= num_heads <= 128, 1 <= q_len <= kv_len <= max_seq, scale > 0 (no default), bf16 / f16, every buffer
+ * 16-byte aligned.  One launch, no workspace, no KV split: for a few query rows use pgk_sdpa_mla_fixed_cache. */
+pgk_status pgk_sdpa_mla_prefill(const void* q_nope, const void* q_pe, const void* kv, const void* cache, void* out, int num_heads, int q_len,
+                                int kv_len, int max_seq, float scale, pgk_dtype dt, pgk_stream s);
+/* Host-only: "mla_prefill_mfma" and through grid (int[2], may be NULL) the launch grid (query tiles of 128 rows, heads); NULL (and
+ * pgk_last_error) for num_heads outside 1..128, q_len < 1, kv_len < q_len, dt outside {bf16, f16}. */
+const char* pgk_sdpa_mla_prefill_plan(int num_heads, int q_len, int kv_len, pgk_dtype dt, int* grid);
 
 /* ---------------------------------------------------------------------- engine ------ */
 /* Native decode/prefill launcher: one C call (or one hipGraph launch) per token step instead of

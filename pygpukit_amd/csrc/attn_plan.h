@@ -64,6 +64,17 @@ inline int mla_chunks(int heads, int q_len, int max_seq) {
     return n < 1 ? 1 : (n > MLA_MAX_CHUNKS ? MLA_MAX_CHUNKS : n);
 }
 
+// ---- pgk_sdpa_mla_prefill (ops_mla_prefill.hip): MLA's decompressed form, one workgroup per (128 query rows, head) --------------
+constexpr int MLAP_NOPE = 128, MLAP_V = 128, MLAP_QK = MLAP_NOPE + MLA_ROPE, MLAP_BQ = 128, MLAP_BKV = 64;
+inline const char* mla_prefill_refusal(int heads, int q_len, int kv_len, bool is_16bit) {
+    if (heads < 1 || heads > MLA_MAX_HEADS) return "num_heads must be 1 .. 128";
+    if (!is_16bit) return "bfloat16 / float16 only";
+    if (q_len < 1) return "q_len < 1";
+    if (kv_len < q_len) return "kv_len < q_len";
+    return nullptr;
+}
+inline int mla_prefill_tiles(int q_len) { return ceil_div(q_len, MLAP_BQ); }
+
 // ---- pgk_paged_attention_v1: slices of ~512 positions per (sequence, kv head); 1 = no workspace, no combine launch ------------
 inline int paged_nsplit(int max_context) {
     const int n = (max_context + 511) / 512;

@@ -9,6 +9,9 @@ shared key].  The same 512 latent columns are the keys and the values.
   sdpa_mla_fixed_cache / _ptr   q [q_len, H, 576] = [q_abs | q_pe] with W_UK absorbed -> out [q_len, H, 512]:
                                 out[i, h] = sum_r softmax_r(scale <q[i, h], cache[r]>) cache[r, :512], r <= context_len - q_len + i
   sdpa_mla_plan                 ("mla_latent_mfma", query-tile columns, cache chunks); needs no GPU work
+and a prompt chunk in the decompressed (textbook) form at qk_nope 128 / qk_rope 64 / v 128, 3.4 times less arithmetic than the above:
+  sdpa_mla_prefill              q_nope [S, H, 128], q_pe [S, H, 64], kv [T, H, 256] = kv_b_proj of the latent rows -> out [S, H, 128]
+  sdpa_mla_prefill_plan         ("mla_prefill_mfma", (query tiles, heads)); needs no GPU work
 
 bfloat16 / float16, 1 <= H <= 128.  `scale` is required and positive: the model's is mscale^2 / sqrt(192), not 1 / sqrt(576)."""
 
@@ -22,6 +25,7 @@ from pygpukit_amd.core.dtypes import as_dtype, bfloat16, float16, float32, int32
 from pygpukit_amd.ops._common import call
 
 LATENT, ROPE, WIDTH, MAX_HEADS = 512, 64, 576, 128
+PREFILL_NOPE, PREFILL_V = 128, 128          # the head dims sdpa_mla_prefill is built for
 _ws_cache: dict[tuple[int, int, int], GPUArray] = {}
 
 
@@ -115,4 +119,43 @@ def sdpa_mla_plan(num_heads: int, q_len: int, max_seq: int, dtype) -> tuple[str,
     return plan.decode(), cols.value, chunks.value
 
 
-__all__ = ["mla_cache_write", "mla_cache_write_ptr", "sdpa_mla_fixed_cache", "sdpa_mla_fixed_cache_ptr", "sdpa_mla_plan"]
+def sdpa_mla_prefill(q_nope: GPUArray, q_pe: GPUArray, kv: GPUArray, cache: GPUArray, out: GPUArray, kv_len: int, scale: float) -> None:
+    """Causal attention of a prompt chunk in MLA's decompressed form (qk_nope 128, qk_rope 64, v 128), one launch:
+    out[i, h] = sum_j softmax_j(scale (<q_nope[i, h], kv[j, h, :128]> + <q_pe[i, h], cache[j, 512:]>)) kv[j, h, 128:], j <= kv_len - S + i.
+    q_nope [S, H, 128], q_pe [S, H, 64] (roped), kv [kv_len, H, 256] = kv_b_proj of latent rows 0 .. kv_len - 1, cache [max_seq, 576]
+    (only the rope columns of rows below kv_len are read), out [S, H, 128].  kv_len > S: a cached prefix.  There is no KV split: a
+    chunk of a few rows over a long prefix is one workgroup's walk per head - sdpa_mla_fixed_cache is the tool for small q_len."""
+    name = "sdpa_mla_prefill"
+    if q_nope.ndim != 3 or q_nope.shape[2] != PREFILL_NOPE or q_nope.dtype not in (bfloat16, float16):
+        raise ValueError(f"{name}: q_nope must be bfloat16 / float16 [S, H, {PREFILL_NOPE}], got {q_nope.shape}/{q_nope.dtype}")
+    q_len, heads, _ = q_nope.shape
+    if q_pe.shape != (q_len, heads, ROPE) or q_pe.dtype != q_nope.dtype:
+        raise ValueError(f"{name}: q_pe must be {q_nope.dtype} [{q_len}, {heads}, {ROPE}], got {q_pe.shape}/{q_pe.dtype}")
+    if kv.shape != (kv_len, heads, PREFILL_NOPE + PREFILL_V) or kv.dtype != q_nope.dtype:
+        raise ValueError(f"{name}: kv must be {q_nope.dtype} [{kv_len}, {heads}, {PREFILL_NOPE + PREFILL_V}], got {kv.shape}/{kv.dtype}")
+    if cache.ndim != 2 or cache.shape[1] != WIDTH or cache.dtype != q_nope.dtype:
+        raise ValueError(f"{name}: cache must be {q_nope.dtype} [max_seq, {WIDTH}], got {cache.shape}/{cache.dtype}")
+    if out.shape != (q_len, heads, PREFILL_V) or out.dtype != q_nope.dtype:
+        raise ValueError(f"{name}: out must be {q_nope.dtype} [{q_len}, {heads}, {PREFILL_V}], got {out.shape}/{out.dtype}")
+    if not 1 <= heads <= MAX_HEADS or not 1 <= q_len <= kv_len <= cache.shape[0]:
+        raise ValueError(f"{name}: needs 1 <= H <= {MAX_HEADS} and 1 <= S <= kv_len <= max_seq, got H {heads}, S {q_len}, kv_len {kv_len}, "
+                         f"max_seq {cache.shape[0]}")
+    if not scale > 0:
+        raise ValueError(f"{name}: scale must be positive (the model's mscale^2 / sqrt(192) has no default), got {scale}")
+    call("pgk_sdpa_mla_prefill", q_nope._p, q_pe._p, kv._p, cache._p, out._p, heads, q_len, int(kv_len), cache.shape[0], float(scale),
+         q_nope.dtype.code, None)
+
+
+def sdpa_mla_prefill_plan(num_heads: int, q_len: int, kv_len: int, dtype) -> tuple[str, tuple[int, int]]:
+    """("mla_prefill_mfma", (query tiles of 128 rows, heads)) of sdpa_mla_prefill; ValueError for what the op rejects.  No GPU work."""
+    lib = _hip.load()
+    grid = (C.c_int * 2)()
+    plan = lib.pgk_sdpa_mla_prefill_plan(int(num_heads), int(q_len), int(kv_len), as_dtype(dtype).code, grid)
+    if plan is None:
+        msg = lib.pgk_last_error()
+        raise ValueError(msg.decode(errors="replace") if msg else "sdpa_mla_prefill_plan: invalid call")
+    return plan.decode(), (grid[0], grid[1])
+
+
+__all__ = ["mla_cache_write", "mla_cache_write_ptr", "sdpa_mla_fixed_cache", "sdpa_mla_fixed_cache_ptr", "sdpa_mla_plan",
+           "sdpa_mla_prefill", "sdpa_mla_prefill_plan"]

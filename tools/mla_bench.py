@@ -11,7 +11,9 @@ Prints the median us per call of (a), the ratio a / b, the achieved bytes/s of l
 (2 x cols x ctx x (576 + 512)) of (a), the hardware minimum from the peaks below with which of the two bounds it, (a)'s share of it,
 and the spread of each variant against itself (A' / A: the margin inside which two numbers are "the same").  Not a pass / fail gate.
 
-usage: mla_bench.py [--rounds N] [--out FILE]"""
+--prefill times a prompt chunk instead: sdpa_mla_prefill with its kv_b_proj GEMM against the absorbed form (prefill() below).
+
+usage: mla_bench.py [--prefill] [--rounds N] [--out FILE]"""
 import argparse, ctypes as C, os, statistics, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -59,14 +61,48 @@ def measure(timer, variants, rounds, n):
     return med, {k: statistics.median(again[k]) / med[k] for k in names}
 
 
-def main():
+def prefill(a, timer, rng):
+    """--prefill: a prompt chunk S = T of 512, 2048 and 8192 rows, bf16, H = 128 and 16, nope = v = 128.
+      (a) what MLAttention.forward_prefill runs between the cache write and o_proj: the kv_b_proj GEMM [T, 512] -> [T, H 256] and
+          sdpa_mla_prefill;
+      (b) what forward_fixed_cache runs for the same chunk: q_abs = q_nope . W_UK per head (batched_matmul between two
+          transpose_3d_021), the pack of [q_abs | q_pe], sdpa_mla_fixed_cache with q_len = S, out . W_UV^T per head (the same).
+    Share: of the matrix pipe's time for the textbook form's 4 S T / 2 (192 + 128) H flops, for both."""
+    from pygpukit_amd.ops.matmul import batched_matmul, matmul_nt, transpose
+    from pygpukit_amd.ops.nn import sdpa_mla_fixed_cache, sdpa_mla_prefill, sdpa_mla_prefill_plan
+    from pygpukit_amd.ops.tensor import concat_axis0, transpose_3d_021
+    say("| H | S = T | grid | (a) us | (b) us | a / b | matrix-pipe minimum us | share of it a, b | A'/A a, b |")
+    say("|---|---|---|---|---|---|---|---|---|")
+    for heads in (128, 16):
+        w_kvb = bf16(rng.standard_normal((heads * 256, 512)) * 0.05)
+        w_uk, w_uv_t = bf16(rng.standard_normal((heads, 128, 512)) * 0.05), bf16(rng.standard_normal((heads, 512, 128)) * 0.05)
+        qn_block, qp_block = rng.standard_normal((64, heads, 128)), rng.standard_normal((64, heads, 64))
+        for s in (512, 2048, 8192):
+            cache = bf16(np.tile(rng.standard_normal((512, 576)), (s // 512, 1)))
+            latent = bf16(np.tile(rng.standard_normal((512, 512)), (s // 512, 1)))
+            q_nope, q_pe = bf16(np.tile(qn_block, (s // 64, 1, 1))), bf16(np.tile(qp_block, (s // 64, 1, 1)))
+            out_a, out_b = GPUArray((s, heads, 128), bfloat16), GPUArray((s, heads, 512), bfloat16)
+
+            def run_a():
+                sdpa_mla_prefill(q_nope, q_pe, matmul_nt(latent, w_kvb).view((s, heads, 256)), cache, out_a, s, SCALE)
+
+            def run_b():
+                q_abs = transpose_3d_021(batched_matmul(transpose_3d_021(q_nope), w_uk)).view((s * heads, 512))
+                q = transpose(concat_axis0(transpose(q_abs), transpose(q_pe.view((s * heads, 64))))).view((s, heads, 576))
+                sdpa_mla_fixed_cache(q, cache, out_b, s, SCALE)
+                return transpose_3d_021(batched_matmul(transpose_3d_021(out_b), w_uv_t))
+
+            med, floor = measure(timer, {"a": run_a, "b": run_b}, a.rounds, 20 if s < 2048 else (5 if s < 8192 else 2))
+            t_f = 4.0 * s * s / 2 * (192 + 128) * heads / PEAK_FLOPS * 1e6
+            ratio, spread = med["a"] / med["b"], max(abs(floor["a"] - 1), abs(floor["b"] - 1))
+            verdict = f"{ratio:.3f}" if ratio < 1 - spread else f"{ratio:.3f} (not faster)"
+            say(f"| {heads} | {s} | {sdpa_mla_prefill_plan(heads, s, s, 'bfloat16')[1]} | {med['a']:.1f} | {med['b']:.1f} | {verdict} | {t_f:.1f} | "
+                f"{t_f / med['a']:.3f}, {t_f / med['b']:.3f} | {floor['a']:.3f}, {floor['b']:.3f} |")
+
+
+def decode(a, timer, rng):
     from pygpukit_amd.ops import matmul, matmul_nt, softmax
     from pygpukit_amd.ops.nn import sdpa_mla_fixed_cache, sdpa_mla_plan
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    timer, rng = Timer(), np.random.default_rng(0)
     block = rng.standard_normal((512, 576)).astype(np.float32)       # repeated: the time does not depend on the values
     say("| H | q_len | context | plan (columns, chunks) | (a) us | a / b | latent rows GB/s | TFLOP/s | hardware minimum us (bound) | share of it | A'/A a, b |")
     say("|---|---|---|---|---|---|---|---|---|---|---|")
@@ -88,6 +124,15 @@ def main():
                 say(f"| {heads} | {q_len} | {ctx} | {sdpa_mla_plan(heads, q_len, ctx, 'bfloat16')[1:]} | {med['a']:.1f} | {verdict} | "
                     f"{nbytes / med['a'] / 1e3:.0f} | {flops / med['a'] / 1e6:.1f} | {max(t_b, t_f):.2f} ({'bytes' if t_b >= t_f else 'matrix'}) | "
                     f"{max(t_b, t_f) / med['a']:.3f} | {floor['a']:.3f}, {floor['b']:.3f} |")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--prefill", action="store_true", help="time sdpa_mla_prefill against the absorbed form on a prompt chunk instead")
+    a = ap.parse_args()
+    (prefill if a.prefill else decode)(a, Timer(), np.random.default_rng(0))
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")
