@@ -701,6 +701,28 @@ pgk_status pgk_sdpa_mla_prefill(const void* q_nope, const void* q_pe, const void
 /* Host-only: "mla_prefill_mfma" and through grid (int[2], may be NULL) the launch grid (query tiles of 128 rows, heads); NULL (and
  * pgk_last_error) for num_heads outside 1..128, q_len < 1, kv_len < q_len, dt outside {bf16, f16}. */
 const char* pgk_sdpa_mla_prefill_plan(int num_heads, int q_len, int kv_len, pgk_dtype dt, int* grid);
+/* Batched MLA decode over a PAGED latent cache [num_blocks, block_size, 576] (ops_mla_paged.hip): a page row is a row of the cache
+ * above, one per token for all heads.  block_tables [num_seqs, max_blocks_per_seq], context_lens [num_seqs] and slot_mapping
+ * [n_tokens] are the int32 device arrays of pgk_paged_attention_v1 / pgk_paged_cache_write: slot = block * block_size + offset, a
+ * negative slot is skipped, context_lens[b] includes this step's tokens.  Any block_size >= 1. */
+/* kv_a [n_tokens, 576] -> slot slot_mapping[t]: pgk_mla_cache_write's row for position positions[t] (int32 [n_tokens], one per
+ * token), bit for bit.  A negative slot, a slot beyond the pages and a position outside the table [table_rows, 64] write nothing. */
+pgk_status pgk_mla_paged_cache_write(const void* kv_a, const void* gamma, const void* cos, const void* sin, const int32_t* positions, void* cache,
+                                     const int32_t* slot_mapping, int n_tokens, int num_blocks, int block_size, int table_rows, float eps,
+                                     int f32_table, pgk_dtype dt, pgk_stream s);
+/* q [num_seqs, q_len, num_heads, 576], out [num_seqs, q_len, num_heads, 512]: pgk_sdpa_mla_fixed_cache's sum per sequence over the
+ * rows its block table names, r <= context_lens[b] - q_len + i.  One launch for the batch plus the merge when the plan has several
+ * chunks; the grid and the workspace depend on (num_heads, q_len, num_seqs, max_context) only and every length is read on the device
+ * (clamped to max_context and to the table).  context_lens[b] < q_len (0: an idle sequence): its out rows are zeros.  Table entries at
+ * or beyond ceil(context_lens[b] / block_size) and page rows at or beyond the context are never read.  scale > 0 (no default).
+ * workspace: pgk_sdpa_mla_paged_workspace_bytes, may be NULL when that is 0 (one chunk). */
+pgk_status pgk_sdpa_mla_paged(const void* q, const void* cache, const int32_t* block_tables, const int32_t* context_lens, void* out, int num_seqs,
+                              int num_heads, int q_len, int num_blocks, int block_size, int max_blocks_per_seq, int max_context, float scale,
+                              void* workspace, pgk_dtype dt, pgk_stream s);
+size_t pgk_sdpa_mla_paged_workspace_bytes(int num_heads, int q_len, int num_seqs, int max_context);
+/* Host-only: "mla_paged_mfma" and through grid (int[3], may be NULL) the launch grid (column tiles, chunks, sequences); NULL (and
+ * pgk_last_error) for what pgk_sdpa_mla_paged rejects: pgk_sdpa_mla_plan's conditions with max_context for the rows, or num_seqs < 1. */
+const char* pgk_sdpa_mla_paged_plan(int num_heads, int q_len, int num_seqs, int max_context, pgk_dtype dt, int* grid);
 
 /* ---------------------------------------------------------------------- engine ------ */
 /* Native decode/prefill launcher: one C call (or one hipGraph launch) per token step instead of

@@ -40,4 +40,4 @@ from pygpukit_amd.ops.paged import (copy_to_paged_cache_fp8, paged_attention_pre
 from pygpukit_amd.ops.quantize import dequantize_int8, linear_int8, quantize_to_int8  # noqa: F401,E402
 from pygpukit_amd.ops.nn.kvfp8 import (kv_cache_prefill_gqa_fp8, kv_cache_update_gqa_fp8, kv_cache_update_gqa_fp8_ptr, kv_fp8_scales, sdpa_causal_fixed_cache_fp8,  # noqa: F401,E402
                                        sdpa_causal_fixed_cache_fp8_ptr, sdpa_kv_fp8_plan)
-from pygpukit_amd.ops.nn.mla import mla_cache_write, mla_cache_write_ptr, sdpa_mla_fixed_cache, sdpa_mla_fixed_cache_ptr, sdpa_mla_plan, sdpa_mla_prefill, sdpa_mla_prefill_plan  # noqa: F401,E402
+from pygpukit_amd.ops.nn.mla import mla_cache_write, mla_cache_write_ptr, sdpa_mla_fixed_cache, sdpa_mla_fixed_cache_ptr, sdpa_mla_plan, sdpa_mla_prefill, sdpa_mla_prefill_plan, allocate_mla_cache, mla_reshape_and_cache, sdpa_mla_paged, sdpa_mla_paged_plan  # noqa: F401,E402

@@ -140,6 +140,8 @@ _PROTOS = {
     "pgk_mla_cache_write": [_V, _V, _V, _V, _V, _I, _I, _I, _F, _I, _V, _I, _I, _V],
     "pgk_sdpa_mla_fixed_cache": [_V, _V, _V, _I, _I, _I, _F, _I, _V, _V, _I, _V],
     "pgk_sdpa_mla_prefill": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _F, _I, _V],
+    "pgk_mla_paged_cache_write": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _F, _I, _I, _V],
+    "pgk_sdpa_mla_paged": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _F, _V, _I, _V],
     "pgk_pope_inplace": [_V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V], "pgk_alibi_compute_bias": [_V, _V, _I, _I, _I, _V],
     "pgk_alibi_add_bias": [_V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V],
     "pgk_sdpa_alibi": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _I64, _I64, _I64, _I64, _I64, _I64, _I, _V],
@@ -206,6 +208,8 @@ _NON_STATUS = {"pgk_last_error": ([], C.c_char_p), "pgk_version": ([], C.c_char_
                "pgk_sdpa_mla_plan": ([_I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)], C.c_char_p),
                "pgk_sdpa_mla_workspace_bytes": ([_I, _I, _I], C.c_size_t),
                "pgk_sdpa_mla_prefill_plan": ([_I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
+               "pgk_sdpa_mla_paged_plan": ([_I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
+               "pgk_sdpa_mla_paged_workspace_bytes": ([_I, _I, _I, _I], C.c_size_t),
                "pgk_paged_kv_fp8_plan": ([_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)], C.c_char_p),
                "pgk_paged_attention_fp8_workspace_bytes": ([_I, _I, _I, _I], C.c_size_t),
                "pgk_jit_available": ([], C.c_int), "pgk_jit_library_path": ([], C.c_char_p),

@@ -64,6 +64,25 @@ inline int mla_chunks(int heads, int q_len, int max_seq) {
     return n < 1 ? 1 : (n > MLA_MAX_CHUNKS ? MLA_MAX_CHUNKS : n);
 }
 
+// ---- pgk_sdpa_mla_paged (ops_mla_paged.hip): the same walk for a batch of sequences over a paged latent cache -------------------
+// Grid (column tiles, chunks, sequences).  The chunk count is a function of the shape and the host's bound on the contexts alone -
+// never of context_lens, which stay on the device - so the grid and the workspace of a captured graph hold while the lengths move:
+// enough chunks for two workgroups per CU over column tiles x sequences, none shorter than MLA_MIN_CHUNK rows at max_context, one
+// where the bound is that short.  A full batch (32 sequences x 4 column tiles) fills the chip four chunks deep; one sequence gets
+// mla_chunks' split.  The LIVE chunk length follows each sequence's own context (decode_chunk_len, in the kernel).
+constexpr int MLA_PAGED_MAX_SEQS = 65535;       // grid z
+inline const char* mla_paged_refusal(int heads, int q_len, int num_seqs, int max_context, bool is_16bit) {
+    if (const char* why = mla_refusal(heads, q_len, max_context, is_16bit)) return why;
+    if (num_seqs < 1 || num_seqs > MLA_PAGED_MAX_SEQS) return "num_seqs must be 1 .. 65535";
+    return nullptr;
+}
+inline int mla_paged_chunks(int heads, int q_len, int num_seqs, int max_context) {
+    const long long wgs = (long long)mla_col_tiles(heads, q_len) * num_seqs;
+    const int by_rows = max_context / MLA_MIN_CHUNK, by_fill = (int)ceil_div(512LL, wgs);
+    const int n = by_rows < by_fill ? by_rows : by_fill;
+    return n < 1 ? 1 : (n > MLA_MAX_CHUNKS ? MLA_MAX_CHUNKS : n);
+}
+
 // ---- pgk_sdpa_mla_prefill (ops_mla_prefill.hip): MLA's decompressed form, one workgroup per (128 query rows, head) --------------
 constexpr int MLAP_NOPE = 128, MLAP_V = 128, MLAP_QK = MLAP_NOPE + MLA_ROPE, MLAP_BQ = 128, MLAP_BKV = 64;
 inline const char* mla_prefill_refusal(int heads, int q_len, int kv_len, bool is_16bit) {

@@ -13,7 +13,11 @@ around the two new ones.  Out of scope: INTEGRATION.md.
 
 forward_prefill(x, start_position), at nope = v = 128: the same chunk in the decompressed form - one GEMM with the unsplit kv_b_proj over
 the latent rows, then sdpa_mla_prefill (ops_mla_prefill.hip), 3.4 times less attention arithmetic and no per-head matmul, transpose or
-pack.  Both methods write the same cache rows, so prompts go through forward_prefill and decode steps through forward_fixed_cache."""
+pack.  Both methods write the same cache rows, so prompts go through forward_prefill and decode steps through forward_fixed_cache.
+
+forward_paged(x [num_seqs, hidden], positions, slot_mapping, block_tables, context_lens, cache, max_context): one decode token per
+sequence of a batch over a PAGED latent cache the caller owns - mla_reshape_and_cache and sdpa_mla_paged (ops_mla_paged.hip) in the
+places of the two ops above, every length on the device."""
 
 from __future__ import annotations
 
@@ -21,12 +25,15 @@ import numpy as np
 
 from pygpukit_amd import _hip
 from pygpukit_amd.core.array import GPUArray
+from pygpukit_amd.core.dtypes import int32
 from pygpukit_amd.core.factory import from_numpy, zeros
 from pygpukit_amd.ops.matmul import batched_matmul, transpose
 from pygpukit_amd.ops.nn.linear import split_qkv_batch
-from pygpukit_amd.ops.nn.mla import LATENT, PREFILL_NOPE, PREFILL_V, ROPE, WIDTH, mla_cache_write, sdpa_mla_fixed_cache, sdpa_mla_prefill
+from pygpukit_amd.ops.nn.mla import (LATENT, PREFILL_NOPE, PREFILL_V, ROPE, WIDTH, mla_cache_write, mla_reshape_and_cache, sdpa_mla_fixed_cache,
+                                     sdpa_mla_paged, sdpa_mla_prefill)
 from pygpukit_amd.ops.nn.norm import rmsnorm
 from pygpukit_amd.ops.nn.rope import rope_inplace_f32table
+from pygpukit_amd.ops.paged import gather_embeddings
 from pygpukit_amd.ops.tensor import concat_axis0, transpose_3d_012, transpose_3d_021
 
 from .linear import LinearBF16
@@ -86,27 +93,55 @@ class MLAttention:
         0 .. start_position + S - 1, returns [S, hidden]."""
         if self._cache is None:
             raise RuntimeError("MLAttention: init_fixed_cache first")
-        S, H, nope, v = x.shape[0], self.num_heads, self.qk_nope_head_dim, self.v_head_dim
+        S, H = x.shape[0], self.num_heads
         if start_position < 0 or start_position + S > self._cache.shape[0]:
             raise ValueError(f"forward_fixed_cache: positions {start_position}..{start_position + S - 1} outside the cache of {self._cache.shape[0]} rows")
+        cos, sin = self._cos._view(start_position * ROPE, (S, ROPE)), self._sin._view(start_position * ROPE, (S, ROPE))
+        q = self._absorbed_query(x, cos, sin)
+        mla_cache_write(self.kv_a_proj_with_mqa(x), self.kv_a_layernorm, self._cos, self._sin, self._cache, start_position, self.norm_eps)
+        out = GPUArray((S, H, LATENT), x.dtype)
+        sdpa_mla_fixed_cache(q, self._cache, out, start_position + S, self.softmax_scale)
+        return self._project_out(out)
+
+    def _absorbed_query(self, x: GPUArray, cos: GPUArray, sin: GPUArray) -> GPUArray:
+        """x [S, hidden], cos / sin [S, 64] (row s: token s's position) -> q [S, H, 576] = [q_nope . W_UK | RoPE(q_pe)]."""
+        S, H, nope = x.shape[0], self.num_heads, self.qk_nope_head_dim
         xq = x if self.q_a_proj is None else rmsnorm(self.q_a_proj(x), self.q_a_layernorm, self.norm_eps)
         q_nope = self.q_nope_proj(xq).view((S, H, nope))
         q_pe = self.q_pe_proj(xq).view((S, H, ROPE))
-        cos, sin = self._cos._view(start_position * ROPE, (S, ROPE)), self._sin._view(start_position * ROPE, (S, ROPE))
         rope_inplace_f32table(q_pe, q_pe._view(0, (S, 0, ROPE)), cos, sin)
         # [S, H, *] and [H, S, *] are the same bytes for one token
         q_nope_h = q_nope.view((H, 1, nope)) if S == 1 else transpose_3d_021(q_nope)
         q_abs = batched_matmul(q_nope_h, self.w_uk)                                  # [H, S, 512]
         q_abs = q_abs.view((H * S, LATENT)) if S == 1 else transpose_3d_021(q_abs).view((S * H, LATENT))
         # the pack: [q_abs | q_pe] per (row, head) = rows of [576, S H] concatenated, transposed back
-        q = transpose(concat_axis0(transpose(q_abs), transpose(q_pe.view((S * H, ROPE))))).view((S, H, WIDTH))
-        mla_cache_write(self.kv_a_proj_with_mqa(x), self.kv_a_layernorm, self._cos, self._sin, self._cache, start_position, self.norm_eps)
-        out = GPUArray((S, H, LATENT), x.dtype)
-        sdpa_mla_fixed_cache(q, self._cache, out, start_position + S, self.softmax_scale)
+        return transpose(concat_axis0(transpose(q_abs), transpose(q_pe.view((S * H, ROPE))))).view((S, H, WIDTH))
+
+    def _project_out(self, out: GPUArray) -> GPUArray:
+        """The attention's latent output [S, H, 512] -> o = out . W_UV^T per head -> o_proj -> [S, hidden]."""
+        S, H, v = out.shape[0], self.num_heads, self.v_head_dim
         out_h = out.view((H, 1, LATENT)) if S == 1 else transpose_3d_021(out)
         o = batched_matmul(out_h, self._w_uv_t)                                      # [H, S, v]
         o = o.view((1, H * v)) if S == 1 else transpose_3d_021(o).view((S, H * v))
         return self.o_proj(o)
+
+    def forward_paged(self, x: GPUArray, positions: GPUArray, slot_mapping: GPUArray, block_tables: GPUArray, context_lens: GPUArray,
+                      cache: GPUArray, max_context: int) -> GPUArray:
+        """One decode token per sequence of a batch over a paged latent cache (ops.nn.allocate_mla_cache): x [num_seqs, hidden],
+        positions / slot_mapping / context_lens int32 [num_seqs] on the device (context_lens counts this token), block_tables int32
+        [num_seqs, max_blocks_per_seq], max_context the host's bound on context_lens.  The query projections with RoPE at each
+        sequence's own position (the table rows gathered by position), mla_reshape_and_cache, the absorbed query, sdpa_mla_paged,
+        W_UV and o_proj: row b is what forward_fixed_cache returns for sequence b alone.  No length is read on the host, so positions must
+        lie below max_position_embeddings: they index the RoPE tables."""
+        n, H = x.shape[0], self.num_heads
+        if positions.dtype != int32 or positions.ndim != 1 or positions.shape[0] != n:
+            raise ValueError(f"forward_paged: positions must be int32 [{n}], got {positions.shape}/{positions.dtype}")
+        cos, sin = gather_embeddings(positions, self._cos, n), gather_embeddings(positions, self._sin, n)
+        q = self._absorbed_query(x, cos, sin)
+        mla_reshape_and_cache(self.kv_a_proj_with_mqa(x), self.kv_a_layernorm, self._cos, self._sin, positions, cache, slot_mapping, self.norm_eps)
+        out = GPUArray((n, 1, H, LATENT), x.dtype)
+        sdpa_mla_paged(q.view((n, 1, H, WIDTH)), cache, block_tables, context_lens, out, max_context, self.softmax_scale)
+        return self._project_out(out.view((n, H, LATENT)))
 
     def forward_prefill(self, x: GPUArray, start_position: int) -> GPUArray:
         """forward_fixed_cache for a prompt chunk in the decompressed form (qk_nope_head_dim = v_head_dim = 128 only): the query

@@ -33,7 +33,7 @@ from pygpukit_amd.ops.nn import (kv_cache_update_ring, kv_cache_update_ring_ptr,
                                 sdpa_sliding_window_fixed_cache_ptr, sdpa_sliding_window_strided, sdpa_window_plan)
 from pygpukit_amd.ops.nn import (kv_cache_prefill_gqa_fp8, kv_cache_update_gqa_fp8, kv_cache_update_gqa_fp8_ptr, kv_fp8_scales, sdpa_causal_fixed_cache_fp8,
                                 sdpa_causal_fixed_cache_fp8_ptr, sdpa_kv_fp8_plan)
-from pygpukit_amd.ops.nn import mla_cache_write, mla_cache_write_ptr, sdpa_mla_fixed_cache, sdpa_mla_fixed_cache_ptr, sdpa_mla_plan, sdpa_mla_prefill, sdpa_mla_prefill_plan
+from pygpukit_amd.ops.nn import mla_cache_write, mla_cache_write_ptr, sdpa_mla_fixed_cache, sdpa_mla_fixed_cache_ptr, sdpa_mla_plan, sdpa_mla_prefill, sdpa_mla_prefill_plan, allocate_mla_cache, mla_reshape_and_cache, sdpa_mla_paged, sdpa_mla_paged_plan
 from pygpukit_amd.ops.plan import BASE_PLAN_OPS, TENSOR_PLAN_OPS, base_op_grid, base_op_plan, tensor_op_grid, tensor_op_plan
 from pygpukit_amd.ops.reduction import argmax, argmax_int, argmax_rows, max, mean, min, softmax, sum, sum_axis
 from pygpukit_amd.ops.unary import abs, cos, exp, log, neg, relu, rsqrt, sin, sqrt

@@ -17,7 +17,7 @@ from pygpukit_amd.ops.nn.window import (kv_cache_update_ring, kv_cache_update_ri
                                         sdpa_sliding_window_fixed_cache_ptr, sdpa_sliding_window_strided, sdpa_window_plan)
 from pygpukit_amd.ops.nn.kvfp8 import (kv_cache_prefill_gqa_fp8, kv_cache_update_gqa_fp8, kv_cache_update_gqa_fp8_ptr, kv_fp8_scales, sdpa_causal_fixed_cache_fp8,
                                        sdpa_causal_fixed_cache_fp8_ptr, sdpa_kv_fp8_plan)
-from pygpukit_amd.ops.nn.mla import mla_cache_write, mla_cache_write_ptr, sdpa_mla_fixed_cache, sdpa_mla_fixed_cache_ptr, sdpa_mla_plan, sdpa_mla_prefill, sdpa_mla_prefill_plan
+from pygpukit_amd.ops.nn.mla import mla_cache_write, mla_cache_write_ptr, sdpa_mla_fixed_cache, sdpa_mla_fixed_cache_ptr, sdpa_mla_plan, sdpa_mla_prefill, sdpa_mla_prefill_plan, allocate_mla_cache, mla_reshape_and_cache, sdpa_mla_paged, sdpa_mla_paged_plan
 from pygpukit_amd.ops.nn.rope import (alibi_add_bias, alibi_compute_bias, alibi_init_slopes, pope_init_encoding, pope_inplace,
                                       rope_init_linear, rope_init_ntk_aware, rope_init_yarn, rope_inplace, rope_inplace_f32table)
 
@@ -36,4 +36,4 @@ __all__ = ["gelu", "silu", "sigmoid", "tanh", "relu2", "sdpa_causal", "sdpa_caus
            "kv_cache_update_ring", "kv_cache_update_ring_ptr", "sdpa_window_plan", "kv_cache_update_gqa_fp8", "kv_cache_update_gqa_fp8_ptr",
            "kv_cache_prefill_gqa_fp8", "kv_fp8_scales", "sdpa_causal_fixed_cache_fp8", "sdpa_causal_fixed_cache_fp8_ptr", "sdpa_kv_fp8_plan",
            "mla_cache_write", "mla_cache_write_ptr", "sdpa_mla_fixed_cache", "sdpa_mla_fixed_cache_ptr", "sdpa_mla_plan",
-           "sdpa_mla_prefill", "sdpa_mla_prefill_plan"]
+           "sdpa_mla_prefill", "sdpa_mla_prefill_plan", "allocate_mla_cache", "mla_reshape_and_cache", "sdpa_mla_paged", "sdpa_mla_paged_plan"]

@@ -22,6 +22,7 @@ import ctypes as C
 from pygpukit_amd import _hip
 from pygpukit_amd.core.array import GPUArray
 from pygpukit_amd.core.dtypes import as_dtype, bfloat16, float16, float32, int32
+from pygpukit_amd.core.factory import zeros
 from pygpukit_amd.ops._common import call
 
 LATENT, ROPE, WIDTH, MAX_HEADS = 512, 64, 576, 128
@@ -157,5 +158,89 @@ def sdpa_mla_prefill_plan(num_heads: int, q_len: int, kv_len: int, dtype) -> tup
     return plan.decode(), (grid[0], grid[1])
 
 
+# ---- the paged latent cache: [num_blocks, block_size, 576], a page row being a row of the cache above (no head axis); block_tables
+# [num_seqs, max_blocks_per_seq], context_lens [num_seqs] and slot_mapping [n_tokens] are ops.paged's int32 device arrays ----------
+_paged_ws_cache: dict[tuple[int, int, int, int], GPUArray | None] = {}
+
+
+def allocate_mla_cache(num_blocks: int, block_size: int, dtype=bfloat16) -> GPUArray:
+    """[num_blocks, block_size, 576], zero-filled; any block_size >= 1."""
+    dtype = as_dtype(dtype)
+    if num_blocks < 1 or block_size < 1 or dtype not in (bfloat16, float16):
+        raise ValueError(f"allocate_mla_cache: needs num_blocks >= 1, block_size >= 1 and bfloat16 / float16, got {num_blocks}, {block_size}, {dtype}")
+    return zeros((num_blocks, block_size, WIDTH), dtype)
+
+
+def _check_pages(cache, dtype, name: str) -> None:
+    if cache.ndim != 3 or cache.shape[2] != WIDTH or cache.dtype != dtype:
+        raise ValueError(f"{name}: cache must be {dtype} [num_blocks, block_size, {WIDTH}], got {cache.shape}/{cache.dtype}")
+
+
+def mla_reshape_and_cache(kv_a: GPUArray, gamma: GPUArray, cos: GPUArray, sin: GPUArray, positions: GPUArray, cache: GPUArray,
+                          slot_mapping: GPUArray, eps: float = 1e-6) -> None:
+    """kv_a [n_tokens, 576] -> slot slot_mapping[t] of the pages: what mla_cache_write puts into row positions[t] of a contiguous cache,
+    bit for bit (each token has its own position: a decode batch has one per sequence).  One launch; a negative slot writes nothing."""
+    name = "mla_reshape_and_cache"
+    if kv_a.ndim != 2 or kv_a.shape[1] != WIDTH or kv_a.dtype not in (bfloat16, float16):
+        raise ValueError(f"{name}: kv_a must be bfloat16 / float16 [n_tokens, {WIDTH}], got {kv_a.shape}/{kv_a.dtype}")
+    _check_pages(cache, kv_a.dtype, name)
+    if gamma.shape != (LATENT,) or gamma.dtype != kv_a.dtype:
+        raise ValueError(f"{name}: gamma must be {kv_a.dtype} [{LATENT}], got {gamma.shape}/{gamma.dtype}")
+    if cos.ndim != 2 or cos.shape[1] != ROPE or sin.shape != cos.shape or cos.dtype != sin.dtype or cos.dtype not in (float32, kv_a.dtype):
+        raise ValueError(f"{name}: cos / sin must be float32 or {kv_a.dtype} [max_pos, {ROPE}], got {cos.shape}/{cos.dtype} and "
+                         f"{sin.shape}/{sin.dtype}")
+    n = kv_a.shape[0]
+    for label, a in (("positions", positions), ("slot_mapping", slot_mapping)):
+        if a.dtype != int32 or a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"{name}: {label} must be int32 [{n}], got {a.shape}/{a.dtype}")
+    call("pgk_mla_paged_cache_write", kv_a._p, gamma._p, cos._p, sin._p, positions._p, cache._p, slot_mapping._p, n, cache.shape[0],
+         cache.shape[1], cos.shape[0], float(eps), int(cos.dtype == float32), kv_a.dtype.code, None)
+
+
+def sdpa_mla_paged_plan(num_heads: int, q_len: int, num_seqs: int, max_context: int, dtype) -> tuple[str, tuple[int, int, int]]:
+    """("mla_paged_mfma", (column tiles of 32 (query row, head) pairs, KV chunks, sequences)) of sdpa_mla_paged: a function of the
+    shape and the bound alone, never of the lengths.  One chunk: the kernel writes `out` itself; more: a merge launch follows.
+    ValueError for what the op rejects.  No GPU work."""
+    lib = _hip.load()
+    grid = (C.c_int * 3)()
+    plan = lib.pgk_sdpa_mla_paged_plan(int(num_heads), int(q_len), int(num_seqs), int(max_context), as_dtype(dtype).code, grid)
+    if plan is None:
+        msg = lib.pgk_last_error()
+        raise ValueError(msg.decode(errors="replace") if msg else "sdpa_mla_paged_plan: invalid call")
+    return plan.decode(), (grid[0], grid[1], grid[2])
+
+
+def sdpa_mla_paged(q: GPUArray, cache: GPUArray, block_tables: GPUArray, context_lens: GPUArray, out: GPUArray, max_context: int,
+                   scale: float) -> None:
+    """sdpa_mla_fixed_cache for a decode batch straight off the pages, one launch (plus the merge): q [num_seqs, q_len, H, 576],
+    out [num_seqs, q_len, H, 512]; row i of sequence b sees rows 0 .. context_lens[b] - q_len + i of the pages block_tables[b] names.
+    context_lens stays on the device (graph replay): max_context bounds it, sizes the KV split and clamps what the kernel reads.  A
+    sequence with context_lens[b] == 0 is idle and its rows are zeros; so, on the device, is one with fewer rows than q_len, which the
+    host refuses where it can see it (max_context < q_len).  Table entries beyond a sequence's last page are never read."""
+    name = "sdpa_mla_paged"
+    if q.ndim != 4 or q.shape[3] != WIDTH or q.dtype not in (bfloat16, float16):
+        raise ValueError(f"{name}: q must be bfloat16 / float16 [num_seqs, q_len, H, {WIDTH}], got {q.shape}/{q.dtype}")
+    num_seqs, q_len, heads, _ = q.shape
+    _check_pages(cache, q.dtype, name)
+    if out.shape != (num_seqs, q_len, heads, LATENT) or out.dtype != q.dtype:
+        raise ValueError(f"{name}: out must be {q.dtype} [{num_seqs}, {q_len}, {heads}, {LATENT}], got {out.shape}/{out.dtype}")
+    if block_tables.dtype != int32 or block_tables.ndim != 2 or block_tables.shape[0] != num_seqs:
+        raise ValueError(f"{name}: block_tables must be int32 [{num_seqs}, max_blocks_per_seq], got {block_tables.shape}/{block_tables.dtype}")
+    if context_lens.dtype != int32 or context_lens.ndim != 1 or context_lens.shape[0] != num_seqs:
+        raise ValueError(f"{name}: context_lens must be int32 [{num_seqs}], got {context_lens.shape}/{context_lens.dtype}")
+    if not 1 <= heads <= MAX_HEADS or num_seqs < 1 or not 1 <= q_len <= max_context:
+        raise ValueError(f"{name}: needs 1 <= H <= {MAX_HEADS}, num_seqs >= 1 and 1 <= q_len <= max_context, got H {heads}, num_seqs {num_seqs}, "
+                         f"q_len {q_len}, max_context {max_context}")
+    if not scale > 0:
+        raise ValueError(f"{name}: scale must be positive (the model's mscale^2 / sqrt(192) has no default), got {scale}")
+    key = (heads, q_len, num_seqs, int(max_context))
+    if key not in _paged_ws_cache:
+        nbytes = _hip.load().pgk_sdpa_mla_paged_workspace_bytes(*key)
+        _paged_ws_cache[key] = GPUArray((nbytes // 4,), float32) if nbytes else None
+    ws = _paged_ws_cache[key]
+    call("pgk_sdpa_mla_paged", q._p, cache._p, block_tables._p, context_lens._p, out._p, num_seqs, heads, q_len, cache.shape[0], cache.shape[1],
+         block_tables.shape[1], int(max_context), float(scale), ws._p if ws is not None else None, q.dtype.code, None)
+
+
 __all__ = ["mla_cache_write", "mla_cache_write_ptr", "sdpa_mla_fixed_cache", "sdpa_mla_fixed_cache_ptr", "sdpa_mla_plan",
-           "sdpa_mla_prefill", "sdpa_mla_prefill_plan"]
+           "sdpa_mla_prefill", "sdpa_mla_prefill_plan", "allocate_mla_cache", "mla_reshape_and_cache", "sdpa_mla_paged", "sdpa_mla_paged_plan"]

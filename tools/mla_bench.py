@@ -13,7 +13,9 @@ and the spread of each variant against itself (A' / A: the margin inside which t
 
 --prefill times a prompt chunk instead: sdpa_mla_prefill with its kv_b_proj GEMM against the absorbed form (prefill() below).
 
-usage: mla_bench.py [--prefill] [--rounds N] [--out FILE]"""
+--paged times a decode BATCH over a paged latent cache instead (paged() below): sdpa_mla_paged against sdpa_mla_fixed_cache per sequence.
+
+usage: mla_bench.py [--prefill | --paged] [--rounds N] [--out FILE]"""
 import argparse, ctypes as C, os, statistics, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -100,6 +102,79 @@ def prefill(a, timer, rng):
                 f"{t_f / med['a']:.3f}, {t_f / med['b']:.3f} | {floor['a']:.3f}, {floor['b']:.3f} |")
 
 
+def paged(a, timer, rng):
+    """--paged: 32 sequences, q_len 1, block_size 64, bf16, H = 128 and 16; every context 512 / 4096 / 32768, and one ragged batch with
+    the contexts spread geometrically from 64 to 32768.  Pages are dealt out in a random order.
+      (a) sdpa_mla_paged: one launch for the batch (plus the merge), the lengths on the device;
+      (b) ONE gather launch of every sequence's pages into contiguous caches (an embedding lookup over the pages as rows of
+          64 x 576, the cheapest gather the project has), then sdpa_mla_fixed_cache per sequence;
+      (c) sdpa_mla_fixed_cache per sequence on contiguous caches that never were paged (no gather at all).
+    a / b and a / c carry "(not faster)" unless below 1 by more than the larger A'/A spread of the pair.  GB/s: (a)'s latent rows,
+    sum of contexts x 1152 B, and their share of the 8 TB/s peak.  Then the writer: mla_reshape_and_cache against mla_cache_write."""
+    from pygpukit_amd.llm.layers.rope import precompute_freqs_cis
+    from pygpukit_amd.ops.nn import (allocate_mla_cache, mla_cache_write, mla_reshape_and_cache, sdpa_mla_fixed_cache, sdpa_mla_paged,
+                                     sdpa_mla_paged_plan)
+    from pygpukit_amd.ops.paged import gather_embeddings
+    nseq, bs, row_b = 32, 64, 1152
+    block = bf16(rng.standard_normal((4096, 576)))                   # repeated: the time does not depend on the values
+    i32 = lambda x: from_numpy(np.ascontiguousarray(x, np.int32))    # noqa: E731
+    say("| H | contexts | grid (tiles, chunks, seqs) | (a) us | (b) us | (c) us | a / b | a / c | (a) latent rows GB/s | of 8 TB/s | A'/A a, b, c |")
+    say("|---|---|---|---|---|---|---|---|---|---|---|")
+    batches = [(str(c), [c] * nseq) for c in (512, 4096, 32768)] + [("64..32768 ragged", [int(round(64 * 512 ** (i / (nseq - 1)))) for i in range(nseq)])]
+    for label, ctxs in batches:
+        need = [-(-c // bs) for c in ctxs]
+        nblk, bound = sum(need), max(ctxs)
+        pages, perm = allocate_mla_cache(nblk, bs, bfloat16), rng.permutation(nblk).astype(np.int32)
+        for k in range(0, nblk * bs, 4096):                          # fill the pages with the block
+            n = min(4096, nblk * bs - k)
+            _hip.call("pgk_memcpy_d2d", pages.data_ptr() + k * row_b, block.data_ptr(), n * row_b, None)
+        first = np.concatenate([[0], np.cumsum(need)])
+        tables = np.zeros((nseq, max(need)), np.int32)
+        for b in range(nseq): tables[b, :need[b]] = perm[first[b]:first[b + 1]]
+        tables_d, lens_d, ids = i32(tables), i32(ctxs), i32(perm)
+        table2d = pages.view((nblk, bs * 576))
+        flat = [GPUArray((need[b] * bs, 576), bfloat16) for b in range(nseq)]
+        for b in range(nseq):
+            for k in range(0, need[b] * bs, 4096):
+                _hip.call("pgk_memcpy_d2d", flat[b].data_ptr() + k * row_b, block.data_ptr(), min(4096, need[b] * bs - k) * row_b, None)
+        for heads in (128, 16):
+            q = bf16(rng.standard_normal((nseq, 1, heads, 576)))
+            out, qs, outs = GPUArray((nseq, 1, heads, 512), bfloat16), [], []
+            for b in range(nseq):
+                qs.append(q._view(b * heads * 576, (1, heads, 576))); outs.append(out._view(b * heads * 512, (1, heads, 512)))
+
+            def run_b():
+                g = gather_embeddings(ids, table2d, nblk)
+                for b in range(nseq):
+                    sdpa_mla_fixed_cache(qs[b], g._view(int(first[b]) * bs * 576, (need[b] * bs, 576)), outs[b], ctxs[b], SCALE)
+
+            def run_c():
+                for b in range(nseq): sdpa_mla_fixed_cache(qs[b], flat[b], outs[b], ctxs[b], SCALE)
+
+            med, floor = measure(timer, {"a": lambda: sdpa_mla_paged(q, pages, tables_d, lens_d, out, bound, SCALE), "b": run_b, "c": run_c},
+                                 a.rounds, 50 if bound < 32768 else 10)
+
+            def verdict(k):
+                ratio, spread = med["a"] / med[k], max(abs(floor["a"] - 1), abs(floor[k] - 1))
+                return f"{ratio:.3f}" if ratio < 1 - spread else f"{ratio:.3f} (not faster)"
+
+            rate = sum(ctxs) * row_b / med["a"] / 1e3
+            say(f"| {heads} | {label} | {sdpa_mla_paged_plan(heads, 1, nseq, bound, 'bfloat16')[1]} | {med['a']:.1f} | {med['b']:.1f} | {med['c']:.1f} | "
+                f"{verdict('b')} | {verdict('c')} | {rate:.0f} | {rate * 1e9 / PEAK_BYTES:.3f} | {floor['a']:.3f}, {floor['b']:.3f}, {floor['c']:.3f} |")
+        del pages, flat
+    say()
+    say("| tokens | mla_reshape_and_cache us | mla_cache_write us | paged / contiguous | A'/A paged, contiguous |")
+    say("|---|---|---|---|---|")
+    cos, sin = (from_numpy(np.ascontiguousarray(t, np.float32)) for t in precompute_freqs_cis(64, 4096))
+    gamma = bf16(1.0 + 0.1 * rng.standard_normal(512))
+    pages, flat1 = allocate_mla_cache(64, bs, bfloat16), GPUArray((4096, 576), bfloat16)
+    for n in (32, 4096):
+        kv_a, pos, slots = block._view(0, (n, 576)), i32(rng.permutation(4096)[:n]), i32(rng.permutation(4096)[:n])
+        med, floor = measure(timer, {"p": lambda: mla_reshape_and_cache(kv_a, gamma, cos, sin, pos, pages, slots),
+                                     "c": lambda: mla_cache_write(kv_a, gamma, cos, sin, flat1, 0)}, a.rounds, 20)
+        say(f"| {n} | {med['p']:.1f} | {med['c']:.1f} | {med['p'] / med['c']:.3f} | {floor['p']:.3f}, {floor['c']:.3f} |")
+
+
 def decode(a, timer, rng):
     from pygpukit_amd.ops import matmul, matmul_nt, softmax
     from pygpukit_amd.ops.nn import sdpa_mla_fixed_cache, sdpa_mla_plan
@@ -131,8 +206,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--prefill", action="store_true", help="time sdpa_mla_prefill against the absorbed form on a prompt chunk instead")
+    ap.add_argument("--paged", action="store_true", help="time sdpa_mla_paged on a decode batch against sdpa_mla_fixed_cache per sequence instead")
     a = ap.parse_args()
-    (prefill if a.prefill else decode)(a, Timer(), np.random.default_rng(0))
+    (prefill if a.prefill else paged if a.paged else decode)(a, Timer(), np.random.default_rng(0))
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")
